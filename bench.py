@@ -19,11 +19,21 @@ Other workloads the same script measures (each prints ONE JSON line of the same 
     --eval                BASELINE configs[4] per GPU: encode --eval-news news once, score --eval-impressions impressions,
                           ranking metrics on the device (a "step" is one pass over the impression shard)
 
-The JSON line also carries
-  roofline     - the dominant libnrhip kernel of the timed region, timed live with HIP events inside the library
-                 (nr_prof_*), against the MI355X dense-MFMA / HBM peak; "step": the whole step against the binding (MFMA)
-                 bound and its HBM bytes (PMC file) against the fused-minimum bytes of SURVEY §8(d);
-  cpu_baseline - the CPU oracle (a port, torch-CPU fp32) timed on this host on a bounded sample.
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, config); nothing else runs.  Everything beyond that figure is opt-in:
+    --full                also measure, on the same line:
+      roofline     - the dominant libnrhip kernel of the timed region, timed live with HIP events inside the library
+                     (nr_prof_*), against the MI355X dense-MFMA / HBM peak; "step": the whole step against the binding (MFMA)
+                     bound and its HBM bytes (PMC file) against the fused-minimum bytes of SURVEY §8(d); plus
+                     kernel_ms_per_step / kernel_roofline_frac and config.batch_structure;
+      also         - (default 1-GPU train line) the other BASELINE configs: NAML, eval, dense batch, fp32;
+      cpu_baseline - the CPU oracle (a port, torch-CPU fp32) timed on this host on a bounded sample.
+                     --no-prof / --no-also / --no-cpu-baseline / --all-kernels refine what --full adds.
+    --dump-outputs DIR    after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 /
+                          float64): train = the loss and the [B, 1+K] scores the model returned; eval = candidate scores
+                          and the metric sums.  Arrays over 2^20 values are a fixed seeded sample of rows (elements when
+                          1-D).  Inputs, initial weights and dropout seeds are seeded, so two builds can be compared file by
+                          file (to rounding: the default backward accumulates gradients with fp32 atomics).
 """
 import argparse
 import glob
@@ -425,6 +435,38 @@ def cpu_eval_baseline(args, V, n_news, n_imp, seed, budget_s=20.0):
                       f"impressions ({t_imp * 1e3:.2f} ms/impression) to {n_news} news + {n_imp} impressions, {cores} threads"}
 
 
+# ----------------------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_VALUES = 1 << 20          # per array; larger outputs are sampled (seeded) down to this
+DUMP_MAX_BYTES = 64 << 20          # all arrays together
+
+
+def _dump_sample(t, seed):
+    """`t` as a host numpy array: whole when it has at most DUMP_MAX_VALUES values, else a fixed seeded sample of its rows
+    (of its elements when 1-D), in index order.  float64 stays float64, everything else becomes float32."""
+    import numpy as np
+    t = t.detach()
+    t = t.double() if t.dtype == torch.float64 else t.float()
+    if t.numel() > DUMP_MAX_VALUES:
+        rows = t.reshape(t.shape[0], -1) if t.dim() >= 2 else t
+        k = max(1, DUMP_MAX_VALUES // (rows[0].numel() if t.dim() >= 2 else 1))
+        idx = np.sort(np.random.default_rng(seed).choice(rows.shape[0], size=min(k, rows.shape[0]), replace=False))
+        t = rows.index_select(0, torch.as_tensor(idx, device=t.device))
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (see _dump_sample); at most DUMP_MAX_BYTES in all."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {name: _dump_sample(t, seed=zlib.crc32(name.encode())) for name, t in arrays.items()}
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 class ArrayShard:
     """Synthetic stand-in with the field contract of data.IndexedTrainShard / IndexedTestShard (index arrays, no files)."""
 
@@ -442,7 +484,7 @@ class ArrayShard:
 
 
 # ----------------------------------------------------------------------------------------- eval workload
-def run_eval(a, args, device, rank, world, dist_on, steps=None, warmup=None, cpu=True):
+def run_eval(a, args, device, rank, world, dist_on, steps=None, warmup=None, cpu=True, dump=False):
     """BASELINE configs[4], one GPU's share: encode the news corpus once (sharded over the ranks + all_gather when N > 1),
     then score `--eval-impressions` impressions (candidates ~U[2,100]) and rank them, all on the device."""
     import numpy as np
@@ -487,18 +529,17 @@ def run_eval(a, args, device, rank, world, dist_on, steps=None, warmup=None, cpu
 
     def one_pass():
         nv = TR.encode_news(model, comb_in, a.eval_batch, device, shard_over_ranks=dist_on)
-        scores, sums = TR.score_shard(model, nv, sh, a.eval_batch, device)
-        return sums
+        return TR.score_shard(model, nv, sh, a.eval_batch, device)
 
     for _ in range(a.warmup):
         one_pass()
     fence()
-    prof_on = (not a.no_prof) and rank == 0
+    prof_on = a.full and (not a.no_prof) and rank == 0
     if prof_on:
         _lib.prof_enable(2)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        sums = one_pass()
+        scores, sums = one_pass()
     fence()
     dt = time.perf_counter() - t0
     prof = {}
@@ -511,9 +552,10 @@ def run_eval(a, args, device, rank, world, dist_on, steps=None, warmup=None, cpu
         dt = float(t.item())
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(a.dump_outputs, {"scores": scores, "metric_sums": sums})
+    del scores
     sums = sums.cpu().tolist()
-    struct = {"live_token_rows": float((comb != 0).mean()), "live_titles": 1.0, "needed_titles": 1.0, "needed_tiles": 1.0, "live_gradient_slabs": 1.0,
-              "attention_bwd_sequences": 1.0}
     out = {"metric": "eval impressions/sec (full-corpus encode + scoring + ranking metrics), NRMS", "value": round(n * world * a.steps / dt, 1),
            "unit": "impressions/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
@@ -522,10 +564,13 @@ def run_eval(a, args, device, rank, world, dist_on, steps=None, warmup=None, cpu
                       "news": a.eval_news, "impressions_per_gpu": n, "candidates": int(off[-1]), "eval_batch": a.eval_batch, "parallelism": f"dp{world}",
                       "feed": getattr(a, "eval_feed", "resident"),
                       "scored_impressions": int(sums[0]), "mean_auc": round(sums[1] / max(sums[0], 1), 4)}}
-    out["roofline"] = roofline_of(prof, a.dtype, struct)
+    if a.full:
+        struct = {"live_token_rows": float((comb != 0).mean()), "live_titles": 1.0, "needed_titles": 1.0, "needed_tiles": 1.0,
+                  "live_gradient_slabs": 1.0, "attention_bwd_sequences": 1.0}
+        out["roofline"] = roofline_of(prof, a.dtype, struct)
     if prof:
         out["kernel_ms_per_step"] = {k: round(ms / a.steps, 4) for k, (c, ms) in sorted(prof.items(), key=lambda kv: -kv[1][1])[:10]}
-    if world == 1 and not a.no_cpu_baseline and cpu:
+    if a.full and world == 1 and not a.no_cpu_baseline and cpu:
         out["cpu_baseline"] = cpu_eval_baseline(make_args("fp32"), a.vocab, a.eval_news, n, 7)
     del model, nv_keep
     from newsrecommendation_amd import ops as _ops
@@ -584,7 +629,8 @@ def build_naml_from_disk(a, args, device):
     return model, stats, tmp
 
 
-def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, steps=None, warmup=None, plain_headline=True):
+def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, steps=None, warmup=None, plain_headline=True,
+              dump=False):
     """One train workload: W untimed warm-up steps, exactly K timed steps between barrier + synchronize fences, MAX over
     ranks.  Returns the JSON dict on rank 0 (None elsewhere)."""
     import shutil
@@ -649,7 +695,7 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
             bucket.step()
         else:
             opt.step()
-        return loss
+        return loss, score
 
     def fence():
         if dist_on:
@@ -661,13 +707,14 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
     # and allocates) are bracketed broadly -- that is where kernel_ms_per_step and the choice of the dominant kernel come
     # from -- and the TIMED region brackets only that dominant kernel, which `roofline` is computed from.
     # --all-kernels: every launch, in the timed region (a diagnostic run, not a headline number).
-    prof_on = (not a.no_prof) and rank == 0
+    # Only with --full: a plain run brackets nothing.
+    prof_on = a.full and (not a.no_prof) and rank == 0
     warm_prof, dominant = {}, None
     for i in range(warmup):
         if prof_on and not a.all_kernels and i == 1:
             torch.cuda.synchronize()
             _lib.prof_enable(2)
-        loss = step(i)
+        loss, score = step(i)
     if prof_on and not a.all_kernels and warmup >= 2:
         _lib.prof_enable(False)
         warm_prof = _lib.prof_collect()
@@ -690,7 +737,7 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
     t0 = time.perf_counter()
     trace = [] if os.environ.get("NR_BENCH_STEP_TIMES") else None
     for i in range(steps):
-        loss = step(warmup + i)
+        loss, score = step(warmup + i)
         if trace is not None:
             trace.append(time.perf_counter())
     fence()
@@ -709,12 +756,17 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
     final_loss = float(loss.item())
 
     out = None
+    if rank == 0 and dump:
+        # What the caller of the last timed step receives: the (loss, score) the model returned.  The updated parameters are
+        # state, not a result, and not reproducible: the default backward adds gradients with fp32 atomics (last-bit order
+        # effects), and over many Adam steps those differences grow, most in parameters whose gradient is near zero.
+        dump_outputs(a.dump_outputs, {"loss": loss, "score": score})
     if rank == 0:
         total = a.batch * world * steps
         ms_step = dt / steps * 1e3
         if feed is not None:
             batches = [feed.batch(i) for i in range(warmup, warmup + 4)]
-        struct = batch_structure(batches, args, model_name)
+        struct = batch_structure(batches, args, model_name) if a.full else None
         plain = plain_headline and not (dense or a.deterministic or a.compact_history)
         out = {"metric": f"train impressions/sec @ batch {a.batch}, " + model_name, "value": round(total / dt, 1), "unit": "impressions/s",
                "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(ms_step, 3),
@@ -728,12 +780,15 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
                           "compact_history": bool(a.compact_history), "dense_batch": bool(dense), "feed": a.feed,
                           "deterministic": bool(a.deterministic),
                           "optimizer": "flat bucket + HIP fused Adam" if bucket is not None else "DDP + torch.optim.Adam(fused)",
-                          "parallelism": f"dp{world}", "final_loss": round(final_loss, 4), "batch_structure": struct}}
+                          "parallelism": f"dp{world}", "final_loss": round(final_loss, 4)}}
+        if a.full:
+            out["config"]["batch_structure"] = struct
         if dist_on and a.dist_backend != "nccl":
             out["config"]["rehearsal"] = f"{a.dist_backend} backend, ranks share GPUs: NOT a measurement"
         # the committed PMC passes profile the default (sparse, resident, non-deterministic) workload only
-        out["roofline"] = roofline_of(prof, dtype, struct, workload=(model_name, dtype, a.batch) if plain else None)
-        if out["roofline"] is not None:
+        if a.full:
+            out["roofline"] = roofline_of(prof, dtype, struct, workload=(model_name, dtype, a.batch) if plain else None)
+        if out.get("roofline") is not None:
             out["roofline"]["step"] = step_roofline(model_name, dtype, a.batch, ms_step, plain=plain)
         # the per-kernel table: from the timed region when it was bracketed broadly, else from the warm-up steps (the
         # dominant kernel's entry is then replaced by its timed-region measurement)
@@ -756,7 +811,7 @@ def run_train(a, device, rank, world, dist_on, model_name, dtype, dense=False, s
     # leave the device as found: the next workload of this process builds its own model
     if a.deterministic:
         _ops.set_deterministic(False)
-    del model, net, bucket, opt, batches, feed
+    del model, net, bucket, opt, batches, feed, loss, score
     _ops.pack_cache.clear()
     _ops.table_cache.invalidate()
     torch.cuda.empty_cache()
@@ -786,8 +841,8 @@ def brief(out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --eval: 3 passes)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default 5; --eval: 1 pass)")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--vocab", type=int, default=30000)
@@ -805,12 +860,18 @@ def main():
                     help="ops.set_deterministic(True): fixed-point integer-atomic gradient accumulation (bit-reproducible gradients)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one rank per GPU: the measured configuration); gloo: rehearsal of the N > 1 path only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events in the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel timings and roofline, the other "
+                         "BASELINE configs under `also` (default 1-GPU train line) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-prof", action="store_true", help="--full without bracketing kernels with HIP events")
     ap.add_argument("--compact-history", action="store_true",
                     help="opt-in: encode only history slots with mask != 0 (their vectors reach the loss through a factor 0); "
                          "NOT the headline configuration -- the reference encodes all 55 titles per impression")
-    ap.add_argument("--all-kernels", action="store_true", help="list every kernel label in kernel_ms_per_step (default: top 12)")
+    ap.add_argument("--all-kernels", action="store_true",
+                    help="with --full: list every kernel label in kernel_ms_per_step (default: top 12)")
     ap.add_argument("--eval", action="store_true", help="eval workload (BASELINE configs[4]) instead of the train step")
     ap.add_argument("--eval-news", type=int, default=100000)
     ap.add_argument("--eval-impressions", type=int, default=125000, help="impressions per GPU (1M over 8 GPUs)")
@@ -818,9 +879,13 @@ def main():
     ap.add_argument("--eval-feed", default="resident", choices=["resident", "host"],
                     help="eval: index arrays resident on the device before the clock starts (default), or uploaded from host arrays in every pass")
     ap.add_argument("--no-also", action="store_true",
-                    help="headline only: skip the other BASELINE configs (NAML, eval, dense batch, fp32) that the default 1-GPU "
-                         "run measures in the same process and attaches under `also`")
+                    help="--full without the other BASELINE configs (NAML, eval, dense batch, fp32) that the default 1-GPU "
+                         "run then measures in the same process and attaches under `also`")
     a = ap.parse_args()
+    if a.all_kernels and not a.full:
+        ap.error("--all-kernels is a per-kernel measurement: it needs --full")
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be >= 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -841,23 +906,25 @@ def main():
             dist.init_process_group(a.dist_backend)
 
     if a.eval:
-        if a.steps == 20 and a.warmup == 5:
-            a.steps, a.warmup = 3, 1
-        out = run_eval(a, make_args(a.dtype), device, rank, world, dist_on)
+        a.steps = 3 if a.steps is None else a.steps
+        a.warmup = 1 if a.warmup is None else a.warmup
+        out = run_eval(a, make_args(a.dtype), device, rank, world, dist_on, dump=a.dump_outputs is not None)
         if out is not None:
             print(json.dumps(out))
         if dist_on:
             dist.destroy_process_group()
         return
 
-    out = run_train(a, device, rank, world, dist_on, a.model, a.dtype, dense=a.dense_batch)
-    # The default 1-GPU run (the driver's BENCH line) also puts the other BASELINE configs on the same clock, in this
+    a.steps = 20 if a.steps is None else a.steps
+    a.warmup = 5 if a.warmup is None else a.warmup
+    out = run_train(a, device, rank, world, dist_on, a.model, a.dtype, dense=a.dense_batch, dump=a.dump_outputs is not None)
+    # With --full, the default 1-GPU run also puts the other BASELINE configs on the same clock, in this
     # process, after the headline's timed region: configs[2] NAML, configs[4] eval (one GPU's share), the dense batch (what
     # the step costs when the sparsity shortcuts find nothing) and the fp32 mode (the one held to 1e-4).  Headline keys are
     # untouched; each entry is a full measurement with its own warm-up, fences and dominant kernel.
     headline_default = (a.model == "NRMS" and a.dtype == "bf16" and not a.dense_batch and not a.deterministic and a.feed == "resident"
                         and not a.compact_history and a.dp_mode == "flat" and not a.freeze_embedding)
-    if out is not None and world == 1 and headline_default and not a.no_also:
+    if out is not None and world == 1 and headline_default and a.full and not a.no_also:
         also = {}
         t_also = time.perf_counter()
         for key, fn in (("naml", lambda: run_train(a, device, rank, world, False, "NAML", "bf16", steps=10, warmup=3)),
@@ -870,7 +937,7 @@ def main():
                 also[key] = {"error": f"{type(e).__name__}: {e}"[:300]}
         also["_seconds"] = round(time.perf_counter() - t_also, 1)
         out["also"] = also
-    if out is not None and world == 1 and not a.no_cpu_baseline and a.model == "NRMS":
+    if out is not None and world == 1 and a.full and not a.no_cpu_baseline and a.model == "NRMS":
         out["cpu_baseline"] = cpu_baseline(make_args(a.dtype), a.vocab, 7)
     if out is not None:
         print(json.dumps(out))

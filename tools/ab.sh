@@ -4,7 +4,7 @@
 A=$1; B=$2; shift 2
 for i in 1 2; do
   for L in "$A" "$B"; do
-    NRHIP_LIB=$(realpath "$L") python3 bench.py --no-also --no-cpu-baseline --steps 30 --warmup 6 "$@" 2>/dev/null | python3 -c "
+    NRHIP_LIB=$(realpath "$L") python3 bench.py --full --no-also --no-cpu-baseline --steps 30 --warmup 6 "$@" 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=j.get('kernel_ms_per_step',{})

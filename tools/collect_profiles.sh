@@ -8,10 +8,10 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p profiles gpurun_out
 CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-prof --no-also"
 echo "[1/5] bench lines"
-python3 bench.py > profiles/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || echo bench failed          # headline + also {naml, eval, dense, fp32} + cpu_baseline
-python3 bench.py --feed device --no-cpu-baseline --no-also > profiles/${TAG}_bench_feed_device.json 2>> gpurun_out/${TAG}_bench.err || echo feed failed
-python3 bench.py --deterministic --no-cpu-baseline --no-also > profiles/${TAG}_bench_deterministic.json 2>> gpurun_out/${TAG}_bench.err || echo det failed
-NR_NO_COMPACT_ROWS=1 NR_NO_POOL_FUSED=1 python3 bench.py --no-cpu-baseline --no-also > profiles/${TAG}_bench_round2_paths.json 2>> gpurun_out/${TAG}_bench.err || echo old-path failed
+python3 bench.py --full > profiles/${TAG}_bench.json || echo bench failed                                   # headline + also {naml, eval, dense, fp32} + cpu_baseline
+python3 bench.py --full --feed device --no-cpu-baseline --no-also > profiles/${TAG}_bench_feed_device.json || echo feed failed
+python3 bench.py --full --deterministic --no-cpu-baseline --no-also > profiles/${TAG}_bench_deterministic.json || echo det failed
+NR_NO_COMPACT_ROWS=1 NR_NO_POOL_FUSED=1 python3 bench.py --full --no-cpu-baseline --no-also > profiles/${TAG}_bench_round2_paths.json || echo old-path failed
 if [ "${2:-all}" = "bench" ]; then mkdir -p gpurun_out/profiles_${TAG}; cp profiles/${TAG}_bench*.json gpurun_out/profiles_${TAG}/; exit 0; fi   # bench lines only
 echo "[2/5] kernel trace + stats"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o kt -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also > /tmp/kt.log 2>&1 || echo kernel-trace failed
