@@ -151,7 +151,10 @@ typedef struct {
   int table_rows;     /* gather source: rows V of the table (needed in deterministic mode only, to size dtable's shadow; else 0) */
   const void* proj_table; /* nr_mhsa_fwd only, optional [V, 3N] dtype = table . W_qkv^T + b_qkv (one nr_gemm_nt over the table):
                          eval mode (p_in == 0, bf16 gather source, qkv == NULL, no backward) gathers the projections of a token
-                         from here instead of projecting every occurrence -- same values, ~V/(n*L) of the GEMM work */
+                         from here instead of projecting every occurrence -- same values, ~V/(n*L) of the GEMM work.
+                         With a mask, the y rows at MASKED query positions are unspecified (currently zero where the
+                         unmasked keys form one run at 32 < L <= 64, a context vector otherwise): the consumer must apply
+                         the same mask.  An all-masked sequence gives zero rows. */
   const int32_t* seq_needed; /* optional [n]: 0 = the caller will not use this sequence's output (it reaches the
                          loss through a factor 0, e.g. a masked history slot, src/model/NRMS.py:59-60, model_utils.py:28,51): its y rows
                          are written as exact zeros without being computed.  NULL: every sequence is computed.  With row_ws the
@@ -192,7 +195,8 @@ int nr_mhsa_fwd(const nr_mhsa_desc* d, void* qkv, void* y, nr_stream_t stream);
 /* dy [n*L, N] dtype.  dqkv: workspace [n*L, 3N] dtype.  w_qkv_t: [Kp, ldwt] dtype = w_qkv^T
  * (nr_cast_pad transpose=1; Kp = d_model rounded up to a chunk; needed only if dx/dtable).
  * dw_qkv [3N, d_model], db_qkv [3N]: fp32, accumulated.  dx: dense source -> [n*L, ldx] dtype
- * or NULL; dtable: gather source -> [V, d_model] fp32 accumulated (skips id 0) or NULL.      */
+ * or NULL; dtable: gather source -> [V, d_model] fp32 accumulated (skips id 0) or NULL.
+ * dtable may be NULL on every gather path, compact row storage included (a frozen table: dw_qkv / db_qkv only). */
 int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dqkv, const void* w_qkv_t,
                 int ldwt, float* dw_qkv, float* db_qkv, void* dx, float* dtable, nr_stream_t stream);
 

@@ -712,7 +712,10 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
     // dqkv_c through the id-sorted positions
     NR_CHECK_ARG(tmask != nullptr, "mhsa_bwd: the forward stored x_rows compactly; qkv / dy / dqkv must be 8-byte aligned");
     NR_CHECK_ARG(!d->dy_far_unwritten || d->seq_nz != nullptr, "mhsa_bwd: dy_far_unwritten needs the seq_nz flags");
-    NR_CHECK_ARG(dtable != nullptr && dx == nullptr && w_qkv_t != nullptr && ldwt >= 3 * N, "mhsa_bwd: gather source takes dtable (and w_qkv_t [d_model, >=3N])");
+    // dtable == NULL: a frozen table -- no table gradient, so no id sort and no scatter GEMM; the attention backward, db and dW
+    // still run
+    NR_CHECK_ARG(dx == nullptr && (dtable == nullptr || (w_qkv_t != nullptr && ldwt >= 3 * N)),
+                 "mhsa_bwd: gather source takes dtable or nothing, not dx (and with dtable, w_qkv_t [d_model, >=3N])");
     int32_t* ws = d->row_ws;
     if (ph_main) {
       // n sequence flags: which sequences got a non-zero upstream gradient (the caller's, read in place, or made here)
@@ -732,14 +735,16 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
                                            d->b_qkv, seq_ws + 4, seq_ws, ws + W.pos, ws + W.dump, db_qkv, d->dy_far_unwritten ? slab_ws : nullptr)))
         return rc;
       // table gradient: rows in token-id order, A rows through their live-list positions
-      if ((rc = nr_launch_sort_rows_by_id(ws, ws + W.live_idx, ws + W.live_ids, M, d->table_rows, ws + W.hist, ws + W.sort_idx, ws + W.sort_ids, s,
+      if (dtable != nullptr && (rc = nr_launch_sort_rows_by_id(ws, ws + W.live_idx, ws + W.live_ids, M, d->table_rows, ws + W.hist, ws + W.sort_idx, ws + W.sort_ids, s,
                                           ws + W.sort_k, /*histogram counted by the forward:*/ws + W.cursor)))
         return rc;
-      EpiArgs ep = store_epi(dtable, d->d_model, NR_F32, nullptr, 0);
-      ep.ids = d->ids; ep.ids_stride = 1; ep.Dtrue = d->d_model; ep.drop = nr_make_drop(d->p_in, d->seed_in);
-      ep.row_count = ws; ep.row_idx = ws + W.sort_idx; ep.row_ids = ws + W.sort_ids; ep.a_idx = ws + W.sort_k;
-      RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
-      if ((rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_SCATTER, ep, s))) return rc;
+      if (dtable != nullptr) {
+        EpiArgs ep = store_epi(dtable, d->d_model, NR_F32, nullptr, 0);
+        ep.ids = d->ids; ep.ids_stride = 1; ep.Dtrue = d->d_model; ep.drop = nr_make_drop(d->p_in, d->seed_in);
+        ep.row_count = ws; ep.row_idx = ws + W.sort_idx; ep.row_ids = ws + W.sort_ids; ep.a_idx = ws + W.sort_k;
+        RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
+        if ((rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_SCATTER, ep, s))) return rc;
+      }
     }
     if (ph_dw && (rc = nr_launch_gemm_tn_counted(dqkv, 3 * N, d->x_rows, d->ld_rows, dw_qkv, d->d_model, M, 3 * N, Kp, 3 * N, d->d_model, ws, s,
                                                  W.tn_floats ? reinterpret_cast<float*>(ws + W.tn_scratch) : nullptr, W.tn_floats)))

@@ -478,7 +478,9 @@ USE_PROJECTED_TABLE = True      # eval-mode shortcut of the gather MHSA (see _Pr
 
 
 def _mhsa_projected(table, params, flat, ids, mask, heads, code, p_out):
-    """No-grad, no input dropout, bf16, L <= 32: attention over projections gathered from the once-projected table."""
+    """No-grad, no input dropout, bf16, L <= 64: attention over projections gathered from the once-projected table.
+    With a mask, the y rows at MASKED query positions are unspecified (currently zeros where the unmasked keys form one run
+    at 32 < L <= 64, a context vector otherwise): the consumer must apply the same mask.  An all-masked sequence gives zeros."""
     wq, bq, wk, bk, wv, bv = params
     if flat is not None:
         wcat, bcat = flat["w"], flat["b"]

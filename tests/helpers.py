@@ -70,3 +70,21 @@ def assert_close(a, b, atol, rtol=0.0, name=""):
     tol = atol + rtol * float(b.abs().max())
     err = float((a - b).abs().max())
     assert err <= tol, f"{name}: max|diff|={err:.3e} > {tol:.3e} (ref max {float(b.abs().max()):.3e})"
+
+
+def metric_row_as_device(labels, s):
+    """[AUC, MRR, nDCG@5, nDCG@10] of one impression, ranked as the device kernel (ops.eval_metrics) ranks it, on the scores `s`
+    it produced.  Rank metrics are discontinuous in the scores (near-ties), so both implementations are compared on the SAME
+    scores.  Duplicate candidates of an impression have EQUAL scores; numpy's default argsort (src/metrics.py:6,20) leaves their
+    order unspecified, the device kernel uses the stable order reversed -- restated here.  Without ties the row must be exactly
+    the reference's functions (checked).  Returns (row, tie_free)."""
+    order = np.argsort(s, kind="stable")[::-1]
+    yt = labels[order]
+    dcg = lambda k: np.sum((2 ** yt[:k] - 1) / np.log2(np.arange(len(yt[:k])) + 2))
+    row = [O.auc_score(labels, s), np.sum(yt / (np.arange(len(yt)) + 1)) / yt.sum(), dcg(5) / O.dcg_score(labels, labels, 5),
+           dcg(10) / O.dcg_score(labels, labels, 10)]
+    tie_free = len(np.unique(s)) == len(s)
+    if tie_free:
+        assert np.allclose(row, [O.auc_score(labels, s), O.mrr_score(labels, s), O.ndcg_score(labels, s, 5),
+                                 O.ndcg_score(labels, s, 10)], atol=1e-12)
+    return row, tie_free

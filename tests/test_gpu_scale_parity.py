@@ -49,8 +49,8 @@ def _grad_report(model, oracle_grads, atol, rtol):
     return worst
 
 
-def _nrms_case(dt, seed, B=B, V=5000):
-    cfg = O.default_cfg()
+def _nrms_case(dt, seed, B=B, V=5000, freeze_embedding=False, user_log_mask=False):
+    cfg = O.default_cfg(freeze_embedding=freeze_embedding, user_log_mask=user_log_mask)
     g = torch.Generator().manual_seed(seed)
     table = torch.randn(V, cfg.word_embedding_dim, generator=g) * 0.4
     table[0] = 0
@@ -77,8 +77,9 @@ STEP_KERNELS = ("gemm_tn3_live", "gemm_tn3_rows", "attn_mfma_bwd_rows", "gemm_nt
                 "pool_fused_bwd", "gemm_nt_wreg_live", "rows_materialize_live", "sort_rows_by_id")
 
 
-def _nrms_against_the_oracle(dt, train, B, V, seed):
-    cfg, sd, m, (hist, mask, cand, label) = _nrms_case(dt, seed, B, V)
+def _nrms_against_the_oracle(dt, train, B, V, seed, freeze_embedding=False, user_log_mask=False):
+    cfg, sd, m, (hist, mask, cand, label) = _nrms_case(dt, seed, B, V, freeze_embedding, user_log_mask)
+    tkey = "news_encoder.embedding_matrix.weight"
     t = TOL[dt]
     m.train(train)
     keep = None
@@ -100,24 +101,33 @@ def _nrms_against_the_oracle(dt, train, B, V, seed):
     if dt == "bf16":
         # the kernels of the benchmarked step, not their small-shape stand-ins
         for want in STEP_KERNELS:
+            if freeze_embedding and want in ("sort_rows_by_id", "gemm_nt_dma_live"):
+                continue
             assert _has(labels, want), (want, sorted(labels))
+        if freeze_embedding:
+            # a frozen table: compact row storage still runs (attention backward, dW over the live rows), the table-gradient
+            # half of it -- the id sort and the scatter-epilogue GEMM -- does not
+            assert not _has(labels, "sort_rows_by_id") and not _has(labels, "gemm_nt_dma_live[bf16,epi=2,"), sorted(labels)
     if train:
         n, T, D, N, p = B * 55, cfg.num_words_title, cfg.word_embedding_dim, cfg.news_dim, cfg.drop_rate
         word = ops.dropout_mask(n * T * D, p, seed_in, "cuda").cpu().reshape(n, T, D)
         ctx = ops.dropout_mask(n * T * N, p, seed_out, "cuda").cpu().reshape(n, T, N)
         nc = B * 5
         keep = {"cand_word": word[:nc], "hist_word": word[nc:], "cand_ctx": ctx[:nc], "hist_ctx": ctx[nc:]}
-    sdo = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    sdo = {k: v.clone().requires_grad_(not (freeze_embedding and k == tkey)) for k, v in sd.items()}
     lo, so = O.nrms_forward(hist, mask, cand, label, sdo, cfg, keep=keep)
     lo.backward()
     assert torch.isfinite(score).all() and torch.isfinite(loss)
     assert_close(loss, lo.detach(), t["tol"], name="loss")
     assert_close(score, so.detach(), t["tol"], name="score")
     worst = _grad_report(m, {k: v.grad for k, v in sdo.items() if v.grad is not None}, t["gatol"], t["grtol"])
-    print(f"nrms B={B} {dt} train={train}: loss {float(loss):.6f} vs {float(lo):.6f}; worst grad err / max|g|: "
+    print(f"nrms B={B} {dt} train={train} freeze={freeze_embedding} ulm={user_log_mask}: loss {float(loss):.6f} vs {float(lo):.6f}; worst grad err / max|g|: "
           + ", ".join(f"{k.split('.', 1)[1]}={v:.2e}" for k, v in sorted(worst.items(), key=lambda kv: -kv[1])[:5]))
-    tab = dict(m.named_parameters())["news_encoder.embedding_matrix.weight"]
-    assert float(tab.grad[0].abs().max()) == 0.0                          # padding_idx row
+    tab = dict(m.named_parameters())[tkey]
+    if freeze_embedding:
+        assert not tab.requires_grad and tab.grad is None
+    else:                                                                 # table trainable
+        assert float(tab.grad[0].abs().max()) == 0.0                      # padding_idx row
     return labels
 
 
