@@ -49,8 +49,8 @@ typedef void* nr_stream_t; /* hipStream_t */
 int nr_version(void);
 /* Copies the calling thread's last error message (NUL terminated) into buf; returns its length. */
 int nr_last_error(char* buf, size_t n);
-/* Integer switches of the library (kernel-family selection, debugging): name without the NR_ prefix, e.g.
- * "NO_SLABS", "SIDE_STREAM", "TN3_ROUNDS" (full list: csrc/nr_common.h, enum NrOpt).  Defaults are the production
+/* Integer switches of the library (a production path and the variant it replaced, which tests compare): name without the
+ * NR_ prefix, e.g. "NO_SLABS", "NT_WREG" (full list: csrc/nr_common.h, enum NrOpt).  Defaults are the production
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
@@ -422,9 +422,6 @@ int nr_adam_step_packed(float* param, float* grad, float* exp_avg, float* exp_av
 int nr_prof_enable(int on);
 int nr_prof_filter(const char* label_prefix);
 int nr_prof_collect(char* buf, size_t n);
-/* Phase stamps of the tiled LDS-DMA NT GEMM (measurement only; option NT_ABLATE bit 64, tools/nt_trace.py): copies up to
- * n (<= 8 * 4096) 64-bit words -- per workgroup 7 s_memrealtime stamps and the HW_ID register -- after a device sync. */
-int nr_debug_nt_trace(unsigned long long* out, int n);
 
 /* ---------------------------------------------------------------------------------------
  * The two MFMA GEMM building blocks on dense operands (used by every op above; exported for unit tests

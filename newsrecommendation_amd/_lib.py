@@ -123,7 +123,6 @@ SIGNATURES = {
     "nr_prof_enable": [_i],
     "nr_prof_collect": [C.c_char_p, C.c_size_t],
     "nr_prof_filter": [C.c_char_p],
-    "nr_debug_nt_trace": [_vp, _i],
 }
 
 _lib = None

@@ -45,9 +45,7 @@ static thread_local char g_err[512] = "";
 namespace {
 struct OptDef { const char* name; int def; };
 const OptDef g_opt_defs[NR_OPT_COUNT] = {
-    {"NO_SLABS", 0},   {"NO_ATTN_SKIP", 0}, {"SIDE_STREAM", 0}, {"ATTN_OLD", 0},  {"ATTN_VALU", 0},   {"NO_PAD_SUB", 0},
-    {"NO_FUSED_FWD", 0}, {"NO_TN3", 0},     {"TN_V1", 0},       {"TN3_ROUNDS", 0}, {"TN3_WK", 0},      {"TN3_NI", 0},
-    {"NT_NOWIDE", 0},  {"NT_NODMA", 0},     {"DMA_MIN_K", 192}, {"DMA_WM2_ALL", 0}, {"ATTN_PRED", 0}, {"ATTN_GENERIC", 0}, {"NO_ROW_SUB", 0}, {"ATTN_BWD_OCC4", 0}, {"NT_ABLATE", 0}, {"NT_WREG", 1}, {"NO_SCATTER_SORT", 0}, {"TN3_MIN_M", 16384}, {"NO_COMPACT_ROWS", 0}, {"NO_POOL_FUSED", 0}, {"ATTN_BWD_GRID", 0}, {"TN3_ATOMIC", 0}, {"TN3_ABLATE", 0}, {"POOL_ABLATE", 0}};
+    {"NO_SLABS", 0}, {"NT_WREG", 1}, {"NO_SCATTER_SORT", 0}, {"NO_COMPACT_ROWS", 0}, {"NO_POOL_FUSED", 0}};
 std::atomic<int> g_opt[NR_OPT_COUNT];
 std::once_flag g_opt_once;
 void opt_init() {
@@ -216,40 +214,6 @@ int nr_det_close(int handle) {
   return rc;
 }
 
-// ---- side stream: two independent GEMMs of one backward composite run concurrently -----------------------------
-// The weight-gradient GEMM (LDS/MFMA bound) and the input-gradient GEMM (bound by L2 atomics or output stores)
-// consume the same upstream gradient and do not depend on each other.  fork: the side stream waits for everything
-// enqueued so far on the caller's stream; join: the caller's stream waits for the side stream.  Both are event
-// waits on the device -- nothing blocks on the host, and memory the caller frees after the call is only reused
-// by work ordered behind the join.
-namespace {
-struct SideStream { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; int dev = -1; };
-thread_local SideStream g_side;
-// Opt-in (NR_SIDE_STREAM=1): measured 9.66 -> 9.43 ms/step at the bench shape; off by default because overlapped
-// launches no longer have a per-kernel duration of their own, which the roofline accounting of bench.py relies on.
-bool side_enabled() {
-  return nr_opt(NR_OPT_SIDE_STREAM) != 0;
-}
-int side_fork(hipStream_t main, hipStream_t* out) {
-  int dev = 0;
-  NR_CHECK_HIP(hipGetDevice(&dev));
-  if (g_side.s == nullptr || g_side.dev != dev) {
-    NR_CHECK_HIP(hipStreamCreateWithFlags(&g_side.s, hipStreamNonBlocking));
-    NR_CHECK_HIP(hipEventCreateWithFlags(&g_side.fork, hipEventDisableTiming));
-    NR_CHECK_HIP(hipEventCreateWithFlags(&g_side.join, hipEventDisableTiming));
-    g_side.dev = dev;
-  }
-  NR_CHECK_HIP(hipEventRecord(g_side.fork, main));
-  NR_CHECK_HIP(hipStreamWaitEvent(g_side.s, g_side.fork, 0));
-  *out = g_side.s;
-  return NR_OK;
-}
-int side_join(hipStream_t main) {
-  NR_CHECK_HIP(hipEventRecord(g_side.join, g_side.s));
-  NR_CHECK_HIP(hipStreamWaitEvent(main, g_side.join, 0));
-  return NR_OK;
-}
-}  // namespace
 static inline bool dtype_ok(int dt) { return dt == NR_F32 || dt == NR_BF16; }
 
 static RowSrc dense_rows(const void* base, int ld, int cols) {
@@ -350,7 +314,7 @@ static bool conv_slab_shape(const nr_conv_desc* d) {
 // 0.57 of the rows of a MIND-shaped batch.  The forward and the backward call evaluate this same predicate.
 static bool mhsa_compact_rows(const nr_mhsa_desc* d) {
   const int N = d->heads * d->d_head, M = d->n * d->L, Kp = round_up(d->d_model, nr_chunk(d->dtype));
-  return !nr_opt(NR_OPT_NO_COMPACT_ROWS) && !nr_opt(NR_OPT_NO_SLABS) && !nr_opt(NR_OPT_NO_ATTN_SKIP) && !nr_opt(NR_OPT_NO_SCATTER_SORT) &&
+  return !nr_opt(NR_OPT_NO_COMPACT_ROWS) && !nr_opt(NR_OPT_NO_SLABS) && !nr_opt(NR_OPT_NO_SCATTER_SORT) &&
          g_det_elems.load() == 0 && d->dtype == NR_BF16 && d->src_kind == NR_SRC_GATHER && d->x_rows != nullptr && d->row_ws != nullptr &&
          d->b_qkv != nullptr && d->table_rows > 0 && M >= 4096 && M % 32 == 0 && (3 * N) % 8 == 0 && 3 * N <= 2048 && d->d_model % 4 == 0 &&
          d->ld_rows >= Kp && nr_attn_compact_ok(d->dtype, d->L, d->d_head, d->heads) && nr_gemm_tn_slabs_ok(3 * N, d->ld_rows, M, 3 * N, Kp);
@@ -770,8 +734,7 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
       }
       if ((rc = nr_launch_live_slabs(slab_ws, d->n, d->L, s))) return rc;
     }
-    const bool no_skip = nr_opt(NR_OPT_NO_ATTN_SKIP) != 0;
-    if (tmask != nullptr && !no_skip) {
+    if (tmask != nullptr) {
       // the attention backward walks a list that leaves out the all-padding sequences no live slab comes near
       seq_ws = d->row_ws + W.seq;
       if (ph_main && (rc = nr_launch_seq_list(slab_ws, tmask, d->n, d->L, seq_ws, s))) return rc;
@@ -803,11 +766,7 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
     if (dtable != nullptr) det.add(dtable, (size_t)d->table_rows * d->d_model);
     if ((rc = det.begin(true, false))) return rc;
   }
-  const bool fork = want_dx && side_enabled() && M >= 65536 && !det.on() && d->bwd_phase == 0;
-  hipStream_t s2 = s;
-  if (fork && (rc = side_fork(s, &s2))) return rc;
   if (want_dx && ph_main) {
-    hipStream_t s = s2;   // the input-gradient GEMM goes to the side stream
     NR_CHECK_ARG(w_qkv_t != nullptr && ldwt >= 3 * N, "mhsa_bwd: w_qkv_t [d_model, >=3N] needed for dx / dtable");
     RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
     if (d->src_kind == NR_SRC_GATHER) {
@@ -849,10 +808,6 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
     } else if ((rc = nr_launch_gemm_tn(d->dtype, dqkv, 3 * N, Xs, dw_qkv, d->d_model, db_qkv, M, 3 * N, Kp, 3 * N, d->d_model, s))) {
       return rc;
     }
-  }
-  if (fork) {
-    const int rj = side_join(s);
-    if (rc == NR_OK) rc = rj;
   }
   const int rd = det.end();
   return rc ? rc : rd;
@@ -1028,9 +983,6 @@ int nr_additive_pool_bwd(const nr_pool_desc* d, const void* e, const float* alph
   if ((rc = nr_launch_pool_core_bwd(d->dtype, d->x, e, d->w2, alpha, g, ld_g, dpre, partial, dw2, db2, d->n, d->L, d->N, d->q, s, zero_flags)))
     return rc;
   RowSrc X = dense_rows(d->x, d->N, d->N);
-  const bool fork = dx != nullptr && side_enabled() && M >= 65536 && !det.on();
-  hipStream_t s2 = s;
-  if (fork && (rc = side_fork(s, &s2))) return rc;
   if (ws != nullptr) {
     if ((rc = nr_launch_live_slabs(ws, d->n, d->L, s))) return rc;
     if ((rc = nr_launch_gemm_tn_slabs(dpre, d->q, d->x, d->N, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, ws + d->n + 4, ws + d->n, s, 0,
@@ -1045,11 +997,7 @@ int nr_additive_pool_bwd(const nr_pool_desc* d, const void* e, const float* alph
     EpiArgs ep = store_epi(dx, d->N, d->dtype, nullptr, 0);
     ep.rowscale = alpha; ep.G = g; ep.ldg = ld_g; ep.L = d->L;
     ep.seq_nz = zero_flags;                          // tiles made of zero-gradient sequences only just write zeros
-    rc = nr_launch_gemm_nt(d->dtype, P, w1_t, ldw1t, M, d->N, d->q, EPI_POOLBWD, ep, s2);
-  }
-  if (fork) {
-    const int rj = side_join(s);
-    if (rc == NR_OK) rc = rj;
+    rc = nr_launch_gemm_nt(d->dtype, P, w1_t, ldw1t, M, d->N, d->q, EPI_POOLBWD, ep, s);
   }
   return rc;
 }

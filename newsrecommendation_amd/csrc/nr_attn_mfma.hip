@@ -958,7 +958,7 @@ template <bool HAS_MASK, int PT, bool SUB, bool FULL = false, int LC = 0, int DC
 // CPT (needs FULL && SUB, L <= 31): compact row storage + bias gradient, see AttnMArgs::pos / dump / db
 // OCC = waves per SIMD the register allocation aims at.  The generic instantiations need ~160 VGPRs and spill heavily under a
 // 128 cap (1.6 - 2.3 ms instead of 0.75); the shape-specialised one fitted 128 before the per-row padding substitution and
-// spills a little with it -- 3 waves without spills win (NR_ATTN_BWD_OCC4 keeps the other build selectable)
+// spills a little with it -- 3 waves without spills win
 __global__ __launch_bounds__(AW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void bwd_kernel(AttnMArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform -> SGPR address math
@@ -1761,7 +1761,7 @@ int launch(bool bwd, const AttnMArgs& a, hipStream_t stream) {
   if (a.L > 32) {
     const size_t smem64 = bwd ? AW * (9 * IMG * sizeof(bf16_t) + 256 * sizeof(float)) : AW * (7 * IMG * sizeof(bf16_t) + 64 * sizeof(float));
     if (bwd) {
-      if (a.L == 50 && a.d == 20 && a.heads == 20 && !nr_opt(NR_OPT_ATTN_GENERIC)) {
+      if (a.L == 50 && a.d == 20 && a.heads == 20) {
         NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bwd64_kernel<50, 20, 20>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem64));
         hipLaunchKernelGGL((bwd64_kernel<50, 20, 20>), dim3((unsigned)blocks), dim3(AW * 64), smem64, stream, a);
       } else {
@@ -1769,7 +1769,7 @@ int launch(bool bwd, const AttnMArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(bwd64_kernel<>, dim3((unsigned)blocks), dim3(AW * 64), smem64, stream, a);
       }
     } else {
-      const bool user50 = a.L == 50 && a.d == 20 && a.heads == 20 && !nr_opt(NR_OPT_ATTN_GENERIC);     // the reference's defaults
+      const bool user50 = a.L == 50 && a.d == 20 && a.heads == 20;     // the reference's defaults
       if (a.ids != nullptr) {
         if (user50) hipLaunchKernelGGL((fwd64_kernel<true, 50, 20, 20>), dim3((unsigned)blocks), dim3(AW * 64), smem64, stream, a);
         else hipLaunchKernelGGL(fwd64_kernel<true>, dim3((unsigned)blocks), dim3(AW * 64), smem64, stream, a);
@@ -1791,37 +1791,34 @@ int launch(bool bwd, const AttnMArgs& a, hipStream_t stream) {
   size_t smem_s = smem + (sub ? (size_t)((3 * a.N + 7) / 8) * 8 * sizeof(bf16_t) : 0) +
                   (cpt ? (size_t)(32 + AW * 96 + hgroups * AW * 96) * sizeof(float) : 0);
   // the compact-storage kernel of the reference's title shape runs 4 workgroups per CU on a slimmer layout (bwd_kernel, SLIM)
-  const bool slim = bwd && cpt && a.heads % AW == 0 && a.L == 30 && a.d == 20 && a.heads == 20 && p3 && !nr_opt(NR_OPT_ATTN_GENERIC) &&
-                    !nr_opt(NR_OPT_ATTN_PRED) && !nr_opt(NR_OPT_ATTN_BWD_OCC4);
+  const bool slim = bwd && cpt && a.heads % AW == 0 && a.L == 30 && a.d == 20 && a.heads == 20 && p3;
   if (slim)
     smem_s = (size_t)AW * (4 * IMG * sizeof(bf16_t) + (a.mask ? 32 : 0) * sizeof(float)) + (size_t)((3 * a.N + 7) / 8) * 8 * sizeof(bf16_t) +
              (size_t)(32 + AW * 32 + hgroups * AW * 3 * 20) * sizeof(float);
-  if (cpt && nr_opt(NR_OPT_ATTN_BWD_GRID) > 0) blocks = std::min<long>(blocks, nr_opt(NR_OPT_ATTN_BWD_GRID));
   auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(AW * 64), smem_s, stream, a); };
   // FULL: all head slots real and the store panels alias the images (d <= 21 in the backward): unpredicated memory
   // instructions, counted waits (see fwd_kernel)
   // (the forward takes the backward's shape condition too: both directions must agree on who supplies padding rows)
-  const bool full = a.heads % AW == 0 && a.L * a.d >= 64 && 3 * 32 * AW * a.d <= 2 * AW * IMG && !nr_opt(NR_OPT_ATTN_PRED);
-  const bool title30 = full && p3 && a.L == 30 && a.d == 20 && a.heads == 20 && !nr_opt(NR_OPT_ATTN_GENERIC);   // the reference's defaults
+  const bool full = a.heads % AW == 0 && a.L * a.d >= 64 && 3 * 32 * AW * a.d <= 2 * AW * IMG;
+  const bool title30 = full && p3 && a.L == 30 && a.d == 20 && a.heads == 20;   // the reference's defaults
   auto pick = [&](auto tag_mask, auto tag_sub) {
     constexpr bool HM = decltype(tag_mask)::value, SB = decltype(tag_sub)::value;
     if (bwd && cpt) {
       // (launcher contract: FULL shape with per-row substitution, L <= 31)
       if constexpr (SB) {
-        if (title30 && slim) go(bwd_kernel<HM, 3, true, true, 30, 20, 20, 4, true>);          // (NR_ATTN_BWD_OCC4=1: the 3-wave build)
-        else if (title30) go(bwd_kernel<HM, 3, true, true, 30, 20, 20, 3, true>);
+        if (title30 && slim) go(bwd_kernel<HM, 3, true, true, 30, 20, 20, 4, true>);
         else p3 ? go(bwd_kernel<HM, 3, true, true, 0, 0, 0, 3, true>) : go(bwd_kernel<HM, 4, true, true, 0, 0, 0, 3, true>);
       }
     } else if (bwd) {
       // 3 waves per SIMD without spills beat 4 with the 11 scratch accesses per item the row substitution pushes the
       // 128-VGPR build into (same box: 0.74 vs 0.91 ms)
-      if (title30) nr_opt(NR_OPT_ATTN_BWD_OCC4) ? go(bwd_kernel<HM, 3, SB, true, 30, 20, 20, 4>) : go(bwd_kernel<HM, 3, SB, true, 30, 20, 20, 3>);
+      if (title30) go(bwd_kernel<HM, 3, SB, true, 30, 20, 20, 3>);
       else if (full) p3 ? go(bwd_kernel<HM, 3, SB, true>) : go(bwd_kernel<HM, 4, SB, true>);
       else p3 ? go(bwd_kernel<HM, 3, SB>) : go(bwd_kernel<HM, 4, SB>);
     } else if (!SB && a.ids != nullptr) {
       // eval's title-level gather: the specialised, unpredicated instantiation for the reference's default shape too
       // (32 x 20 x 20: eval's short histories -- the last 32 clicks of a front-padded history, train.score_shard)
-      const bool user32 = full && p3 && a.L == 32 && a.d == 20 && a.heads == 20 && !nr_opt(NR_OPT_ATTN_GENERIC);
+      const bool user32 = full && p3 && a.L == 32 && a.d == 20 && a.heads == 20;
       if (title30) go(fwd_kernel<HM, 3, false, true, true, 30, 20, 20>);
       else if (user32) go(fwd_kernel<HM, 3, false, true, true, 32, 20, 20>);
       else p3 ? go(fwd_kernel<HM, 3, false, true>) : go(fwd_kernel<HM, 4, false, true>);
@@ -1869,8 +1866,7 @@ bool nr_attn_mfma_supported(int L, int d_head) { return L >= 1 && L <= 64 && d_h
 // Padding-token substitution (tmask / bias) exists on the bf16 panel kernels only: L <= 32, d_head % 4 == 0, 8-byte
 // aligned tensors.  nr_attn_pad_ok tells the caller beforehand; a launch that asks for it elsewhere is an error.
 bool nr_attn_pad_ok(int dtype, int L, int d_head, const void* p0, const void* p1) {
-  const bool old_path = nr_opt(NR_OPT_ATTN_OLD) || nr_opt(NR_OPT_ATTN_VALU) || nr_opt(NR_OPT_NO_PAD_SUB);
-  return !old_path && dtype == NR_BF16 && L >= 1 && L <= 32 && d_head >= 4 && d_head <= 32 && d_head % 4 == 0 &&
+  return dtype == NR_BF16 && L >= 1 && L <= 32 && d_head >= 4 && d_head <= 32 && d_head % 4 == 0 &&
          (((uintptr_t)p0 | (uintptr_t)p1) & 7) == 0;
 }
 
@@ -1887,8 +1883,7 @@ int nr_launch_attn_mfma(bool bwd, int dtype, const void* qkv, const float* mask,
   a.drop = drop;
   const uintptr_t al = dtype == NR_BF16 ? 7 : 15;
   a.vec = (d_head % 4 == 0) && (((uintptr_t)qkv | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dqkv) & al) == 0;
-  const bool old_path = nr_opt(NR_OPT_ATTN_OLD) != 0;
-  const bool fast = dtype == NR_BF16 && a.vec && !old_path;
+  const bool fast = dtype == NR_BF16 && a.vec;
   if (L > 32 && !fast) return -1;   // caller falls back to the LDS/VALU kernels
   // "_live": the backward walks a device-side list of sequences (n is then an upper bound)
   NrProfScope ps(stream, "attn_mfma_%s[%s,n=%d,L=%d,h=%d,d=%d]", bwd ? (seq_list ? "bwd_live" : "bwd") : (seq_list ? "fwd_live" : "fwd"),
@@ -1934,7 +1929,7 @@ int nr_launch_attn_bwd_compact(const void* qkv, const float* mask, const void* d
 // then need not write the bias into the padding rows of partly live sequences (nr_launch_bias_rows), nobody reads them.
 bool nr_attn_rowsub_ok(int dtype, int L, int d_head, int heads) {
   return dtype == NR_BF16 && nr_attn_pad_ok(dtype, L, d_head, nullptr, nullptr) && heads % AW == 0 && L * d_head >= 64 &&
-         3 * 32 * AW * d_head <= 2 * AW * b16::IMG && !nr_opt(NR_OPT_ATTN_PRED) && !nr_opt(NR_OPT_NO_ROW_SUB);
+         3 * 32 * AW * d_head <= 2 * AW * b16::IMG;
 }
 
 // Forward attention whose Q|K|V rows are gathered from a per-token-id table of projections [V, 3N] (bf16 panel kernel:
@@ -1959,8 +1954,6 @@ int nr_launch_attn_gather_fwd(const void* proj_table, const int32_t* ids, const 
 // Fused title-level forward (gather + dropout + Q|K|V projection + attention + dropout), bf16 only.
 // Returns -1 when the shape is outside what the fused kernel covers (the caller then runs the unfused path).
 bool nr_mhsa_fused_shape_ok(int L, int heads, int d_head, int d_model, int ldt, int ldw) {
-  const bool off = nr_opt(NR_OPT_NO_FUSED_FWD) != 0;
-  if (off) return false;
   return L >= 1 && L <= 32 && d_head % 4 == 0 && 3 * d_head <= 64 && d_model <= 320 && d_model > 288 && ldt >= 320 && ldw >= 320 &&
          (heads * d_head) % 4 == 0;
 }

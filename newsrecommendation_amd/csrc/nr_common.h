@@ -67,41 +67,16 @@ struct DeviceGuard {
   if (nr_guard__.rc) return nr_guard__.rc
 
 // ---- library options (host) -----------------------------------------------------------------
-// One table of integer switches instead of getenv() calls scattered over the launchers.  Defaults are the
-// production configuration; each entry can be preset from the environment variable NR_<NAME> (read ONCE, when the
-// first option is looked up) or changed at run time through nr_set_option() (include/nrhip.h) -- the tests use the
-// latter to compare a path with its own switched-off variant inside one process.
+// Switches that turn a production path off in favour of the variant it replaced, kept because tests compare the two: a
+// test runs the same work with a switch set and cleared (nr_set_option, include/nrhip.h) and checks that both give the
+// same results.  Defaults are the production configuration; each entry can also be preset from the environment variable
+// NR_<NAME> (read ONCE, when the first option is looked up).
 enum NrOpt {
-  NR_OPT_NO_SLABS = 0,   // 1: weight-gradient GEMMs contract every row (no live-slab lists)
-  NR_OPT_NO_ATTN_SKIP,   // 1: the attention backward walks every sequence (no device-side sequence list)
-  NR_OPT_SIDE_STREAM,    // 1: weight- and input-gradient GEMMs of one backward run on two streams
-  NR_OPT_ATTN_OLD,       // 1: per-wave staging attention kernels instead of the bf16 panel kernels
-  NR_OPT_ATTN_VALU,      // 1: LDS/VALU attention kernels
-  NR_OPT_NO_PAD_SUB,     // 1: no bias substitution for all-padding sequences
-  NR_OPT_NO_FUSED_FWD,   // 1: never use the fused title-level forward kernels
-  NR_OPT_NO_TN3,         // 1: weight gradients through tn2 / v1 kernels
-  NR_OPT_TN_V1,          // 1: first-generation TN kernel
-  NR_OPT_TN3_ROUNDS,     // >0: force the number of row-split rounds of tn3
-  NR_OPT_TN3_WK,         // 2 / 4: force the tn3 tile family
-  NR_OPT_TN3_NI,         // 4 / 8: force the tn3 n-tile
-  NR_OPT_NT_NOWIDE,      // 1: no "wide" NT kernel
-  NR_OPT_NT_NODMA,       // 1: no LDS-DMA NT kernel
-  NR_OPT_DMA_MIN_K,      // smallest K that takes the LDS-DMA NT kernel (default 192)
-  NR_OPT_DMA_WM2_ALL,    // 1: 128-row DMA tiles for every N
-  NR_OPT_ATTN_PRED,      // 1: predicated (pre-"FULL") memory instructions in the bf16 panel attention kernels
-  NR_OPT_ATTN_GENERIC,   // 1: no shape-specialised (L=30, 20 heads of 20) instantiation of the panel attention kernels
-  NR_OPT_NO_ROW_SUB,     // 1: the projection writes the bias into padding rows (bias_rows) instead of per-row substitution
-  NR_OPT_ATTN_BWD_OCC4,  // 1: the specialised attention backward built for 4 waves per SIMD (128 VGPRs, a few spills) instead of 3
-  NR_OPT_NT_ABLATE,      // measurement only (results are WRONG): tiled LDS-DMA NT kernel without 1: output stores, 2: MFMAs, 4: operand DMA, 8: epilogue; 64: phase stamps (nr_debug_nt_trace)
-  NR_OPT_NT_WREG,        // 1 (default): skinny-K bf16 NT GEMMs with the weights held in registers (persistent, LDS ring of activation rows); 3: the same with 16-row instead of 32-row stages for the QKV shape; 0: tile kernels
+  NR_OPT_NO_SLABS = 0,    // 1: weight-gradient GEMMs contract every row (no live-slab lists)
+  NR_OPT_NT_WREG,         // 1 (default): skinny-K bf16 NT GEMMs with the weights held in registers (persistent, LDS ring of activation rows); 0: tile kernels
   NR_OPT_NO_SCATTER_SORT, // 1: the table-gradient GEMM walks the live rows in batch order instead of token-id order
-  NR_OPT_TN3_MIN_M,      // smallest row count that takes the LDS-DMA weight-gradient kernel (default 16384)
   NR_OPT_NO_COMPACT_ROWS, // 1: x_rows / dqkv of the news-level training path keep one row per token (no compact row storage)
-  NR_OPT_NO_POOL_FUSED,  // 1: additive pooling forward as fc1 GEMM + pool_core_fwd instead of the fused kernel
-  NR_OPT_ATTN_BWD_GRID,  // >0: workgroups of the compact-row attention backward (default 4096 = 16 per CU, grid-stride over the walk)
-  NR_OPT_TN3_ATOMIC,     // 1: the LDS-DMA weight-gradient kernel adds its tiles into dW with fp32 atomics even when the caller brought scratch
-  NR_OPT_TN3_ABLATE,     // measurement only (results are WRONG): 1 = the LDS-DMA weight-gradient kernel skips its fp32 atomic epilogue
-  NR_OPT_POOL_ABLATE,    // measurement only (results are WRONG): fused pooling forward without 1: weighted sum, 2: softmax, 4: out reduction, 8: MFMAs, 16: tanh / logit epilogue
+  NR_OPT_NO_POOL_FUSED,   // 1: additive pooling forward as fc1 GEMM + pool_core_fwd instead of the fused kernel
   NR_OPT_COUNT
 };
 int nr_opt(int which);

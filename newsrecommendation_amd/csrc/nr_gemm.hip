@@ -950,22 +950,9 @@ __device__ __forceinline__ int swzP(int row) { return (0x78 >> (2 * ((row >> 2) 
 // ring depth of the DMA kernel: 4 stages when they fit (150 KB for the one-per-CU tile, 78 KB when two workgroups share a CU)
 constexpr int dma_ring_stages(int stage_bytes, int wm) { return 4 * stage_bytes <= (wm == 4 ? 150 : 78) * 1024 ? 4 : 3; }
 
-// phase stamps of the LDS-DMA NT kernel (NR_NT_ABLATE bit 64; measurement only): 8 x s_memrealtime (100 MHz) per workgroup
-__device__ unsigned long long g_nt_trace[8 * 4096];
-__device__ __forceinline__ void nt_stamp(int abl, int slot) {
-  if ((abl & 64) && threadIdx.x == 0 && blockIdx.x < 4096) g_nt_trace[blockIdx.x * 8 + slot] = wall_clock64();
-}
-
 template <int EPI, int NT16, bool PK, int WM>
 __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B,
-                                                           int ldb, int M, int Ntot, int K, EpiArgs ep, int nchunks_abl) {
-  const int nchunks = nchunks_abl & 0xffff, abl = nchunks_abl >> 16;   // abl: NR_NT_ABLATE phase ablation (measurement only)
-  nt_stamp(abl, 0);
-  if ((abl & 64) && threadIdx.x == 0 && blockIdx.x < 4096) {
-    unsigned hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    g_nt_trace[blockIdx.x * 8 + 7] = hwid;
-  }
+                                                           int ldb, int M, int Ntot, int K, EpiArgs ep, int nchunks) {
   // WM row groups of 64 rows x 2 column halves = 2*WM waves.  WM = 4: 256-row tile, one workgroup per CU.
   // WM = 2: 128-row tile whose ring fits twice into the CU's LDS, so one workgroup's pipeline fill and epilogue
   // overlap the other's MFMA loop.
@@ -1050,7 +1037,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
     for (int t = 0; t < PB + 1; ++t) {
       if (t < PB || extra) {
         const int kk = isA[t] ? min(k0, K - 8 - c8) : k0;   // K tail of A: re-read a valid chunk (B is zero there)
-        if (!(abl & 4)) dma16(src[t] + kk, lds0 + stage * STAGE + (pfirst + t) * 1024);
+        dma16(src[t] + kk, lds0 + stage * STAGE + (pfirst + t) * 1024);
       }
     }
   };
@@ -1136,7 +1123,6 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
         if (wn * HN + j < NT16) fb[buf][j] = *reinterpret_cast<const bf16x8*>(st + offB + j * 1024);
     };
     auto mfmas = [&](int buf) {
-      if (abl & 2) return;
 #pragma unroll
       for (int j = 0; j < HN; ++j) {
         if (wn * HN + j < NT16) {
@@ -1162,10 +1148,8 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
       }
       mfmas(cur);
     };
-    nt_stamp(abl, 1);
     wait_stages(min(NS - 2, nk - 1));
     __builtin_amdgcn_s_barrier();
-    nt_stamp(abl, 2);
     load_frags(0, 0);
     int kt = 0;
     for (; kt + 1 < nk; kt += 2) {
@@ -1199,11 +1183,6 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  nt_stamp(abl, 3);
-  if (abl & 8) {
-    if (acc[0][0][0] == 12345.678f) ((float*)ep.C)[0] = acc[1][0][1];   // keeps the loop alive
-    return;
-  }
   if (PK) {
     // packed bf16 epilogue: 128 rows at a time through a bf16 LDS image (8-byte writes), 16-byte row stores
     bf16_t* sCb = reinterpret_cast<bf16_t*>(smem);
@@ -1269,17 +1248,13 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
         }
       }
       __syncthreads();
-      nt_stamp(abl, 4 + pass);
       for (int u = tid; u < 128 * (WBN / 8); u += WTHR) {
         const int row = u / (WBN / 8), c0 = (u % (WBN / 8)) * 8;
         const int m = m0 + pass * 128 + row;
         if (m < M && c0 < N) {
           const int mout = !compact ? m : (r_lds ? reinterpret_cast<const int*>(smem + NS * STAGE + 1024)[pass * 128 + row] : ep.row_idx[m]);
           bf16_t* dst = (bf16_t*)ep.C + (size_t)mout * ep.ldc + nbase + c0;
-          if (abl & 1) {
-            const uint4 q = *reinterpret_cast<const uint4*>(sCb + row * SCB + c0);
-            if (q.x == 0x12345678u && q.y == 0x9abcdef0u) *reinterpret_cast<uint4*>(dst) = q;
-          } else if (c0 + 8 <= N && (ep.ldc % 8) == 0 && (nbase % 8) == 0) {
+          if (c0 + 8 <= N && (ep.ldc % 8) == 0 && (nbase % 8) == 0) {
             *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(sCb + row * SCB + c0);
           } else {
             for (int e = 0; e < 8 && c0 + e < N; ++e) dst[e] = sCb[row * SCB + c0 + e];
@@ -1288,7 +1263,6 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    nt_stamp(abl, 6);
     return;
   }
   if constexpr (EPI == EPI_SCATTER) {
@@ -1320,7 +1294,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
             const int c = 128 * u + 2 * lane + e;
             if (c < WC && cw0 + c < N && nbase + cw0 + c < ep.Dtrue) {
               if (DET) { if (runq[u][e] != 0) nr_accum_fix(dst + c, runq[u][e]); }
-              else if (run[u][e] != 0.f && !((abl & 1) && run[u][e] != 1234.5f)) atomicAdd(dst + c, run[u][e]);
+              else if (run[u][e] != 0.f) atomicAdd(dst + c, run[u][e]);
             }
           }
       }
@@ -1329,7 +1303,7 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
     };
     const bool from_lds = i_lds && m0 + DBM - 1 < M;
     const bool pair_ok = ((ep.Dtrue | nbase | cw0) & 1) == 0;     // every (row, even column) of this wave is an even element index
-    const bool dropping = ep.drop.thresh != 0 && !(abl & 16);
+    const bool dropping = ep.drop.thresh != 0;
     constexpr int RB = DET ? 2 : 4;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -1452,19 +1426,11 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
   }
 }
 
-}  // namespace
-extern "C" int nr_debug_nt_trace(unsigned long long* out, int n) {
-  if (out == nullptr || n <= 0) return NR_ERR_ARG;
-  NR_CHECK_HIP(hipDeviceSynchronize());
-  NR_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nt_trace), sizeof(unsigned long long) * (size_t)(n < 8 * 4096 ? n : 8 * 4096)));
-  return NR_OK;
-}
-namespace {
 // =========================================================================================
 // NT with the WEIGHTS IN REGISTERS (bf16 in, bf16 out; K <= 32 * KS; EPI_STORE / EPI_STORE_TANH).
 // For the skinny-K projections (QKV: N = 1200, K = 304) the tile kernels above spend their time
 // on everything but MFMAs: per 256 x 208 tile 10 k-steps of barrier + DMA issue + 11 fragment
-// reads in front of 28 MFMAs, then a fill and a drain that overlap nothing (tools/nt_trace.py:
+// reads in front of 28 MFMAs, then a fill and a drain that overlap nothing (phase stamps:
 // 20 us per tile, 4.5 us of it MFMA).  Here a wave keeps its slice of the weight matrix --
 // TPW column tiles x the whole K -- in VGPRs for the life of the (persistent) workgroup and only
 // the activation rows move: 16-row stages through an LDS ring filled by LDS-DMA, ONE barrier per
@@ -1837,7 +1803,6 @@ struct PoolFusedArgs {
   float* out; int ld_out;            // [n, ld_out] out
   const int32_t* needed;             // [n] or null
   int n, L, N, q;
-  int ablate;                        // NR_OPT_POOL_ABLATE (measurement only)
 };
 
 template <int KS>
@@ -1972,7 +1937,7 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
   auto phase_out = [&](int k) {
     const int kf = k - 2;
     float* dst = reinterpret_cast<float*>(dump_g);
-    if (kf >= 0 && kf < nsteps && tid < N && !(a.ablate & 4)) {
+    if (kf >= 0 && kf < nsteps && tid < N) {
       const float* red = sRed + (kf & 1) * NW * NCOL + tid;
       float v = 0.f;
 #pragma unroll
@@ -1988,19 +1953,16 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
     const bool real = kp >= 0 && kp < nsteps;
     const int sq = real ? sList[kp] : 0;
     const float* part = sPart + (kp & 1) * NW * 32 + (lane & 31);
-    float al = 1.f;
-    if (!(a.ablate & 2)) {
-      // a_l = exp(s_l) / (sum + 1e-8), exactly as src/model/model_utils.py:23-30 writes it (no maximum is subtracted there
-      // either; |s| <= |w2|_1 + |b2| because |e| <= 1)
-      float sl = b2;
+    // a_l = exp(s_l) / (sum + 1e-8), exactly as src/model/model_utils.py:23-30 writes it (no maximum is subtracted there
+    // either; |s| <= |w2|_1 + |b2| because |e| <= 1)
+    float sl = b2;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) sl += part[w * 32];
-      const float ex = (lane & 31) < L ? __expf(sl) : 0.f;
-      al = ex / (sum32(ex) + 1e-8f);
-    }
+    for (int w = 0; w < NW; ++w) sl += part[w * 32];
+    const float ex = (lane & 31) < L ? __expf(sl) : 0.f;
+    const float al = ex / (sum32(ex) + 1e-8f);
     float* adst = (real && wid == 0 && lane < L) ? a.alpha + (size_t)sq * L + lane : reinterpret_cast<float*>(dump_g);
     *adst = al;
-    if (real && !(a.ablate & 1)) {
+    if (real) {
       const char* st = smem + (kp % NS) * STAGE;
       // lane = 16-byte column chunk (clamped: the surplus lanes read chunk 0 and drop it), wave = rows wid, wid + 8, ...
       const int ccr = cc_ok ? cc : 0;
@@ -2039,7 +2001,7 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
 #pragma unroll
       for (int i = 0; i < RT; ++i) acc[i][t] = bv;
     }
-    if (real && wcol0 < q && !(a.ablate & 8)) {                              // wave-uniform
+    if (real && wcol0 < q) {                              // wave-uniform
 #pragma unroll
       for (int s2 = 0; s2 < KS; ++s2) {
 #pragma unroll
@@ -2062,7 +2024,7 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
         bf16x4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float th = (a.ablate & 16) ? acc[i][t][r] : 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * acc[i][t][r]) + 1.f);
+          const float th = 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * acc[i][t][r]) + 1.f);
           o[r] = (bf16_t)th;
           pd = fmaf((float)o[r], w2r[t][r], pd);                              // the logit sees e as the backward will (bf16)
         }
@@ -2476,8 +2438,7 @@ int launch_nt_dma_w(const RowSrc& A, const void* B, int ldb, int M, int N, int K
   NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   const int tilesM = (M + DBM - 1) / DBM, nchunks = (N + NT16 * 16 - 1) / (NT16 * 16);
   const int grid = ((tilesM + 7) / 8) * 8 * nchunks;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * WM), smem, stream, (const bf16_t*)A.base, A.ld, (const bf16_t*)B, ldb, M, N, K, ep,
-                     nchunks | (nr_opt(NR_OPT_NT_ABLATE) << 16));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * WM), smem, stream, (const bf16_t*)A.base, A.ld, (const bf16_t*)B, ldb, M, N, K, ep, nchunks);
   NR_CHECK_LAUNCH();
   return NR_OK;
 }
@@ -2488,12 +2449,11 @@ int launch_nt_dma_p(const RowSrc& A, const void* B, int ldb, int M, int N, int K
   // column chunk (att_fc1: 0.47 -> 0.41 ms); with several chunks the smaller tile re-reads A more often and loses
   // (QKV projection: 1.45 -> 1.57 ms)
   constexpr bool fits2 = 3 * (8 + NT16) * 1024 <= 78 * 1024;
-  const bool wm2_all = nr_opt(NR_OPT_DMA_WM2_ALL) != 0;
   // short contractions (K <= 224: at most 7 k-steps) are all pipeline fill and epilogue: two workgroups per CU overlap
   // them even with two column chunks (pooling dX, N = 400, K = 200: 0.445 -> 0.372 ms)
   // ... and up to two column chunks the second read of A is cheaper than the idle fill / epilogue phases of a lone
   // workgroup (NAML conv, N = 400, K = 960: 0.738 -> 0.694 ms); six chunks (QKV projection) still lose (0.51 -> 0.57)
-  if (fits2 && (N <= 2 * NT16 * 16 || K <= 224 || wm2_all)) return launch_nt_dma_w<EPI, NT16, PK, 2>(A, B, ldb, M, N, K, ep, stream);
+  if (fits2 && (N <= 2 * NT16 * 16 || K <= 224)) return launch_nt_dma_w<EPI, NT16, PK, 2>(A, B, ldb, M, N, K, ep, stream);
   return launch_nt_dma_w<EPI, NT16, PK, 4>(A, B, ldb, M, N, K, ep, stream);
 }
 
@@ -2549,8 +2509,7 @@ __global__ __launch_bounds__(128 * WK) void gemm_tn3_kernel(const bf16_t* __rest
                                                             int ldx, float* __restrict__ dW, int ldw, float* __restrict__ db,
                                                             int M, int N, int K, int Nstore, int Kstore, int tilesK, int ntile,
                                                             int nsplit, int rps, const int32_t* __restrict__ slab_list,
-                                                            const int32_t* __restrict__ slab_count, int xgap, int ablate,
-                                                            float* __restrict__ scratch) {
+                                                            const int32_t* __restrict__ slab_count, int xgap, float* __restrict__ scratch) {
   using G = Geo<WK, NI>;
   constexpr int TBN = G::TBN, TBK = G::TBK, NT = G::NT, NW = G::NW, CHA = G::CHA, CH = G::CH, SCW = G::SCW, PA = G::PA, NP = G::NP,
                 STAGE = G::STAGE;
@@ -2724,7 +2683,6 @@ __global__ __launch_bounds__(128 * WK) void gemm_tn3_kernel(const bf16_t* __rest
       continue;
     }
     // lanes on consecutive floats: one atomic instruction covers whole 128-byte lines of a dW row
-    if (!ablate)
     for (int u = tid; u < 64 * TBK; u += NT) {
       const int row = u / TBK, c = u - row * TBK;
       const int n = n0 + pass * 64 + row, k = k0 + c;
@@ -2800,9 +2758,8 @@ int launch_t(const void* dC, int ldc, const void* X, int ldx, float* dW, int ldw
   // ONE round of resident workgroups (256 CUs x 1 or 2), splits a multiple of the 8 XCDs, >= 16 slabs per split.
   // Measured at N=1200, K=304: 1 / 2 / 3 / 4 rounds = 1.03 / 1.14 / 1.25 / 1.34 ms -- every split pays a ring fill and
   // an fp32 atomic epilogue over the whole [N, K] tile, so fewer, longer splits win.
-  const int force_rounds = nr_opt(NR_OPT_TN3_ROUNDS);
-  const int resident = 256 * (WK == 4 ? 1 : 2), rounds = force_rounds ? force_rounds : 1;
-  int nsplit = (resident * rounds / ntile / 8) * 8;     // rounded down: never a few workgroups left for an extra round
+  const int resident = 256 * (WK == 4 ? 1 : 2);
+  int nsplit = (resident / ntile / 8) * 8;              // rounded down: never a few workgroups left for an extra round
   if (nsplit < 8) nsplit = 8;
   int rps = (M + nsplit - 1) / nsplit;
   rps = ((rps + TBM - 1) / TBM) * TBM;
@@ -2813,13 +2770,12 @@ int launch_t(const void* dC, int ldc, const void* X, int ldx, float* dW, int ldw
   NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM));
   const bool counted = slab_list == nullptr && slab_count != nullptr;           // dense rows, device-side row count
   if (slab_list != nullptr && (M / TBM + nsplit - 1) / nsplit > 1024) slab_list = nullptr;   // a split's list must fit its LDS stage
-  // store + reduce epilogue when the caller brought enough scratch (not with forced extra rounds).  Deterministic mode takes it
-  // too: the splits are added in a fixed order by one owner per element, the fixed-point table then only carries db.
-  const bool use_scratch = scratch != nullptr && scratch_floats >= (size_t)nsplit * ntile * G::TBN * G::TBK && !force_rounds &&
-                           !nr_opt(NR_OPT_TN3_ATOMIC) && (((uintptr_t)scratch) & 15) == 0;
+  // store + reduce epilogue when the caller brought enough scratch.  Deterministic mode takes it too: the splits are added in
+  // a fixed order by one owner per element, the fixed-point table then only carries db.
+  const bool use_scratch = scratch != nullptr && scratch_floats >= (size_t)nsplit * ntile * G::TBN * G::TBK && (((uintptr_t)scratch) & 15) == 0;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), G::SMEM, stream, (const bf16_t*)dC, ldc, (const bf16_t*)X, ldx, dW, ldw, db, M, N,
                      K, Nstore, Kstore, tilesK, ntile, nsplit, rps, slab_list, (slab_list || counted) ? slab_count : nullptr, xgap,
-                     nr_opt(NR_OPT_TN3_ABLATE), use_scratch ? scratch : nullptr);
+                     use_scratch ? scratch : nullptr);
   if (use_scratch) {
     const int mode = slab_list != nullptr ? 1 : (counted ? 2 : 0);
     int rg = (Nstore * ((Kstore + 3) / 4) + 63) / 64;
@@ -2832,31 +2788,26 @@ int launch_t(const void* dC, int ldc, const void* X, int ldx, float* dW, int ldw
 }
 
 // rows a multiple of the 32-row slab, at least 8 columns on both sides (tail clamping), 16-byte aligned rows
+constexpr int MIN_M = 16384;   // smallest row count that takes this kernel
 bool eligible(int ldc, int ldx, int M, int N, int K) {
-  const bool off = nr_opt(NR_OPT_NO_TN3) != 0;
   // (round 1 kept the user level, M = 25 600, on tn2: 0.31 vs 0.18 ms then; with one round of splits and >= 16 slabs per
   //  split tn3 now wins there too: 0.067 vs 0.089 ms for [25 600, 1200] x [25 600, 400])
-  return !off && M % TBM == 0 && M >= nr_opt(NR_OPT_TN3_MIN_M) && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0 && ldc % 8 == 0 && ldx % 8 == 0;
+  return M % TBM == 0 && M >= MIN_M && N >= 8 && K >= 8 && N % 8 == 0 && K % 8 == 0 && ldc % 8 == 0 && ldx % 8 == 0;
 }
+// the 320-wide K tile (WK = 4) when K > 160 and rounding K up to whole such tiles adds at most 15 %
+bool wide_k(int K) { return K > 160 && ((K + 319) / 320) * 320 * 100 <= K * 115; }
 int launch(const void* dC, int ldc, const void* X, int ldx, float* dW, int ldw, float* db, int M, int N, int K, int Nstore,
            int Kstore, hipStream_t stream, const int32_t* slab_list = nullptr, const int32_t* slab_count = nullptr, int xgap = 0,
            float* scratch = nullptr, size_t sf = 0) {
-  const int force = nr_opt(NR_OPT_TN3_WK);
-  const int force_ni = nr_opt(NR_OPT_TN3_NI);
-  const bool wide = force ? force == 4 : (K > 160 && ((K + 319) / 320) * 320 * 100 <= K * 115);
-  if (wide) {
-    const bool big = force_ni ? force_ni == 8 : N > 256;
-    if (big) return launch_t<4, 8>(dC, ldc, X, ldx, dW, ldw, db, M, N, K, Nstore, Kstore, stream, slab_list, slab_count, xgap, scratch, sf);
+  if (wide_k(K)) {
+    if (N > 256) return launch_t<4, 8>(dC, ldc, X, ldx, dW, ldw, db, M, N, K, Nstore, Kstore, stream, slab_list, slab_count, xgap, scratch, sf);
     return launch_t<4, 4>(dC, ldc, X, ldx, dW, ldw, db, M, N, K, Nstore, Kstore, stream, slab_list, slab_count, xgap, scratch, sf);
   }
   return launch_t<2, 4>(dC, ldc, X, ldx, dW, ldw, db, M, N, K, Nstore, Kstore, stream, slab_list, slab_count, xgap, scratch, sf);
 }
 size_t scratch_floats(int M, int N, int K) {
   if (N < 8 || K < 8) return 0;
-  const int force = nr_opt(NR_OPT_TN3_WK);
-  const int force_ni = nr_opt(NR_OPT_TN3_NI);
-  const bool wide = force ? force == 4 : (K > 160 && ((K + 319) / 320) * 320 * 100 <= K * 115);
-  if (wide) return ((force_ni ? force_ni == 8 : N > 256)) ? scratch_floats_t<4, 8>(M, N, K) : scratch_floats_t<4, 4>(M, N, K);
+  if (wide_k(K)) return N > 256 ? scratch_floats_t<4, 8>(M, N, K) : scratch_floats_t<4, 4>(M, N, K);
   return scratch_floats_t<2, 4>(M, N, K);
 }
 }  // namespace tn3
@@ -3480,7 +3431,6 @@ int nr_launch_pool_fused_fwd(const void* x, int ldx, const void* w1, int ldw1, c
   PoolFusedArgs a;
   a.x = (const bf16_t*)x; a.ldx = ldx; a.w1 = (const bf16_t*)w1; a.ldw1 = ldw1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
   a.e = (bf16_t*)e; a.lde = lde; a.alpha = alpha; a.out = out; a.ld_out = ld_out; a.needed = needed; a.n = n; a.L = L; a.N = N; a.q = q;
-  a.ablate = nr_opt(NR_OPT_POOL_ABLATE);
   auto kern = pool_fused_fwd_kernel<KS>;
   NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   NrProfScope ps(stream, needed ? "pool_fused_fwd_needed[bf16,n=%d,L=%d,N=%d,q=%d]" : "pool_fused_fwd[bf16,n=%d,L=%d,N=%d,q=%d]", n, L, N, q);
@@ -3556,16 +3506,14 @@ int nr_launch_gemm_nt(int dtype, const RowSrc& A, const void* B, int ldb, int M,
   if (epi != EPI_SCATTER) NR_CHECK_ARG(ep.ldc % 4 == 0 && ((uintptr_t)ep.C & 15) == 0, "gemm_nt: output ld %d / alignment", ep.ldc);
   if (epi == EPI_STORE && ep.act_tanh) epi = EPI_STORE_TANH;
   // Kernel choice (bf16, dense A), from per-shape measurements on MI355X (tools/gemm_probe.py):
-  //   K >= 256            : LDS-DMA ring kernel, 256-row tiles x column chunks of 208 / 320 (QKV projection K=304:
+  //   K >= DMA_MIN_K (192): LDS-DMA ring kernel, 256-row tiles x column chunks of 208 / 320 (QKV projection K=304:
   //                         1.42 ms vs 1.92 ms tiled; att_fc1 K=400; dX K=1200), packed bf16 epilogue
   //   N <= 208, small K   : "wide" kernel, all N columns per workgroup (A read once)
   //   otherwise           : 128 x 128 tiled kernel with the packed bf16 epilogue (pooling dX, K=200: 0.77 vs 1.02 ms)
-  const bool no_wide = nr_opt(NR_OPT_NT_NOWIDE) != 0;
-  const bool no_dma = nr_opt(NR_OPT_NT_NODMA) != 0;
+  constexpr int DMA_MIN_K = 192;
   const int kr32 = (K + 31) / 32 * 32;
   const bool dense_bf16 = dtype == NR_BF16 && A.kind == ROWS_DENSE && A.drop.thresh == 0 && ep.rows_out == nullptr;
-  const int dma_min_k = nr_opt(NR_OPT_DMA_MIN_K);
-  if (dense_bf16 && !no_dma && K >= dma_min_k && ldb >= kr32 && (A.ld >= K || A.gap > 0)) {
+  if (dense_bf16 && K >= DMA_MIN_K && ldb >= kr32 && (A.ld >= K || A.gap > 0)) {
     EpiArgs epg = ep;
     epg.a_gap = A.gap;
     const EpiArgs& ep = epg;                       // (shadows the parameter: the kernels below see the operand's row gap)
@@ -3587,9 +3535,6 @@ int nr_launch_gemm_nt(int dtype, const RowSrc& A, const void* B, int ldb, int M,
       if (epi == EPI_STORE && !tile_skip && K > 288 && K <= 320 && N >= 320) {
         NrProfScope ps(stream, lbl, epi, M, N, K);
         if (ep.row_count && ep.a_dense) return launch_nt_wreg_m<EPI_STORE, 5, 10, 2, WREG_COMPACT_DENSE, true>(A, B, ldb, M, N, K, ep, stream);
-        if (nr_opt(NR_OPT_NT_WREG) == 3)           // 16-row stages (one row tile per barrier)
-          return ep.row_count ? launch_nt_wreg_m<EPI_STORE, 5, 10, 1, WREG_COMPACT>(A, B, ldb, M, N, K, ep, stream)
-                              : launch_nt_wreg_m<EPI_STORE, 5, 10, 1, WREG_DENSE>(A, B, ldb, M, N, K, ep, stream);
         return ep.row_count ? launch_nt_wreg_m<EPI_STORE, 5, 10, 2, WREG_COMPACT, true>(A, B, ldb, M, N, K, ep, stream)
                             : launch_nt_wreg_m<EPI_STORE, 5, 10, 2, WREG_DENSE, true>(A, B, ldb, M, N, K, ep, stream);
       }
@@ -3617,7 +3562,7 @@ int nr_launch_gemm_nt(int dtype, const RowSrc& A, const void* B, int ldb, int M,
     if (c13 < c20) return launch_nt_dma_e<13>(A, B, ldb, M, N, K, epi, ep, stream);
     return launch_nt_dma_e<20>(A, B, ldb, M, N, K, epi, ep, stream);
   }
-  if (dense_bf16 && !no_wide && N <= 208 && A.gap == 0) {
+  if (dense_bf16 && N <= 208 && A.gap == 0) {
     NrProfScope ps(stream, "gemm_nt_wide[bf16,epi=%d,M=%d,N=%d,K=%d]", epi, M, N, K);
     return launch_nt_wide_e<13>(A, B, ldb, M, N, K, epi, ep, stream);
   }
@@ -3975,8 +3920,7 @@ int nr_launch_gemm_tn(int dtype, const void* dC, int ldc, const RowSrc& A, float
   NR_CHECK_ARG(N % ch == 0 && K % ch == 0 && ldc % ch == 0 && A.ld % ch == 0, "gemm_tn: N=%d K=%d ldc=%d lda=%d must be multiples of %d",
                N, K, ldc, A.ld, ch);
   NR_CHECK_ARG(((uintptr_t)A.base & 15) == 0 && ((uintptr_t)dC & 15) == 0, "gemm_tn: operands must be 16-byte aligned");
-  const bool tn_v1 = nr_opt(NR_OPT_TN_V1) != 0;
-  if (!tn_v1 && dtype == NR_BF16 && A.kind == ROWS_DENSE && A.drop.thresh == 0) {
+  if (dtype == NR_BF16 && A.kind == ROWS_DENSE && A.drop.thresh == 0) {
     if (tn3::eligible(ldc, A.ld, M, N, K)) {
       NrProfScope ps(stream, "gemm_tn3[bf16,M=%d,N=%d,K=%d,gap=%d]", M, N, K, A.gap);
       return tn3::launch(dC, ldc, A.base, A.ld, dW, ldw, db, M, N, K, Nstore, Kstore, stream, nullptr, nullptr, A.gap);

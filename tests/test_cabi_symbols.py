@@ -53,10 +53,31 @@ def test_descriptor_layout_and_workspace_sizes_are_host_arithmetic():
     p = _lib.PoolDesc(n=28160, L=30, q=200)
     assert lib.nr_pool_workspace_bytes(C.byref(p)) >= 4 * (28160 + M // 32)
     assert lib.nr_linear_workspace_bytes(C.byref(_lib.LinearDesc(M=100, N=400, dtype=_lib.NR_BF16))) == 100 * 400 * 2
-    assert _lib.get_option("DMA_MIN_K") == 192 and _lib.get_option("NO_SUCH_OPTION") == -1
+
+
+def test_option_table_holds_the_reference_switches():
+    """The switches the GPU tests use to run a reference path: production defaults, readable and settable by name;
+    an unknown name reads -1."""
+    defaults = {"NO_SLABS": 0, "NT_WREG": 1, "NO_SCATTER_SORT": 0, "NO_COMPACT_ROWS": 0, "NO_POOL_FUSED": 0}
+    assert {k: _lib.get_option(k) for k in defaults} == defaults
+    assert _lib.get_option("NR_NT_WREG") == 1 and _lib.get_option("NO_SUCH_OPTION") == -1
     _lib.set_option("NO_SLABS", 1)
     assert _lib.get_option("NO_SLABS") == 1
     _lib.set_option("NO_SLABS", 0)
+
+
+RETIRED_OPTIONS = ["NO_ATTN_SKIP", "SIDE_STREAM", "ATTN_OLD", "ATTN_VALU", "NO_PAD_SUB", "NO_FUSED_FWD", "NO_TN3", "TN_V1",
+                   "TN3_ROUNDS", "TN3_WK", "TN3_NI", "NT_NOWIDE", "NT_NODMA", "DMA_MIN_K", "DMA_WM2_ALL", "ATTN_PRED",
+                   "ATTN_GENERIC", "NO_ROW_SUB", "ATTN_BWD_OCC4", "NT_ABLATE", "TN3_MIN_M", "ATTN_BWD_GRID", "TN3_ATOMIC",
+                   "TN3_ABLATE", "POOL_ABLATE"]
+
+
+@pytest.mark.parametrize("name", RETIRED_OPTIONS)
+def test_retired_option_is_unknown(name):
+    """Switches for superseded or measurement-only paths are gone from the option table: unknown to get and set."""
+    assert _lib.get_option(name) == -1
+    with pytest.raises(RuntimeError, match="unknown option"):
+        _lib.set_option(name, 1)
 
 
 def test_undersized_workspace_is_refused_before_any_launch():

@@ -146,7 +146,8 @@ def test_empty_inputs_are_noops():
     assert out.shape == (0, 8)
 
 
-_SIDE_SCRIPT = r"""
+# one bf16 NRMS training step at title / history scale: loss and the sum / absolute sum of every parameter gradient
+_NRMS_GRAD_SCRIPT = r"""
 import json, sys, torch
 from types import SimpleNamespace
 from newsrecommendation_amd.model import NRMS
@@ -156,7 +157,7 @@ args = SimpleNamespace(num_words_title=30, user_log_length=50, npratio=4, word_e
                        user_log_mask=False, freeze_embedding=False, compute_dtype="bf16")
 g = torch.Generator().manual_seed(3)
 import os
-V, B = 5000, int(os.environ.get("NR_TEST_B", "64"))   # 64 * 55 * 30 = 105 600 token rows: above the fork threshold
+V, B = 5000, int(os.environ.get("NR_TEST_B", "64"))   # B * 55 titles of 30 tokens
 table = (torch.randn(V, 300, generator=g) * 0.4).numpy(); table[0] = 0
 m = NRMS.Model(args, table).cuda().train()
 hist = torch.randint(0, V, (B, 50, 30), generator=g, dtype=torch.int32).cuda()
@@ -173,33 +174,6 @@ for n, p in m.named_parameters():
         out[n] = [float(p.grad.double().sum()), float(p.grad.double().abs().sum())]
 print("RESULT " + json.dumps(out))
 """
-
-
-def test_side_stream_option_gives_the_same_gradients():
-    """NR_SIDE_STREAM=1 forks the input-gradient GEMMs of the MHSA / pooling backward onto a second stream
-    (fork/join by events).  Same seeds -> same dropout draws -> loss identical, gradient sums equal up to the
-    order of the fp32 atomics."""
-    import json, os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-    def run(side):
-        env = dict(os.environ, PYTHONPATH=root)
-        env.pop("NR_SIDE_STREAM", None)
-        if side:
-            env["NR_SIDE_STREAM"] = "1"
-        r = subprocess.run([sys.executable, "-c", _SIDE_SCRIPT], env=env, cwd=root, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
-        return json.loads(line[7:])
-
-    a, b = run(False), run(True)
-    assert a["loss"] == b["loss"]
-    for k in a:
-        if k == "loss":
-            continue
-        (s0, a0), (s1, a1) = a[k], b[k]
-        assert abs(a0 - a1) <= 1e-4 * a0 + 1e-6, (k, a0, a1)
-        assert abs(s0 - s1) <= 1e-4 * a0 + 1e-6, (k, s0, s1)
 
 
 def test_attention_backward_is_independent_of_what_the_workgroup_computed_before():
@@ -248,7 +222,7 @@ def test_live_slab_weight_gradients_equal_the_full_contraction():
         env.pop("NR_NO_SLABS", None)
         if no_slabs:
             env["NR_NO_SLABS"] = "1"
-        r = subprocess.run([sys.executable, "-c", _SIDE_SCRIPT], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        r = subprocess.run([sys.executable, "-c", _NRMS_GRAD_SCRIPT], env=env, cwd=root, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
         return json.loads(line[7:])
