@@ -165,7 +165,8 @@ typedef struct {
   int row_ws_ready;   /* nr_mhsa_bwd only: nonzero = row_ws still holds what nr_mhsa_fwd wrote for these ids (reused as is).
                          REQUIRED when nr_mhsa_fwd was given row_ws: on the bf16 title-level path the forward then leaves
                          the qkv rows of all-padding sequences unwritten (the attention kernels substitute the bias), and the
-                         backward attention has to do the same.                                                   */
+                         backward attention has to do the same ("The MHSA training plan": what each decision of
+                         the forward obliges the backward to do).                                                  */
   int bwd_phase;      /* nr_mhsa_bwd only.  0: the whole backward.  1: everything but the weight / bias gradients (flags, attention
                          backward, dx / table gradient) ; 2: only dw_qkv / db_qkv, after a phase-1 call with the same
                          descriptor and row_ws.  The split lets a data-parallel host start the all-reduce of the (large)
@@ -187,7 +188,8 @@ typedef struct {
  * projections are never written to HBM).  On every other path qkv is required.                              */
 int nr_mhsa_fwd_fused(const nr_mhsa_desc* d);
 /* 1 when nr_mhsa_fwd / nr_mhsa_bwd keep x_rows and dqkv in compact row storage for this descriptor (bf16 gather source with
- * x_rows and row_ws, title-level shapes): only then may dy_far_unwritten be used.                                  */
+ * x_rows and row_ws, title-level shapes): only then may dy_far_unwritten be used.  The exported field of the plan both
+ * calls share ("The MHSA training plan").                                                              */
 int nr_mhsa_compact_rows(const nr_mhsa_desc* d);
 /* Bytes of row_ws that nr_mhsa_fwd / nr_mhsa_bwd use for this descriptor (depends on n and L only). */
 size_t nr_mhsa_workspace_bytes(const nr_mhsa_desc* d);

@@ -232,6 +232,10 @@ static EpiArgs store_epi(void* C, int ldc, int out_dtype, const float* bias, int
   return e;
 }
 
+static inline bool aligned(int bytes, const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & (uintptr_t)(bytes - 1)) == 0;
+}
+
 static int mhsa_rows(const nr_mhsa_desc* d, RowSrc* out) {
   RowSrc s = dense_rows(d->x, d->ldx, d->d_model);
   if (d->src_kind == NR_SRC_GATHER) {
@@ -298,6 +302,27 @@ static bool pool_has_flags(const nr_pool_desc* d) {
   return !nr_opt(NR_OPT_NO_SLABS) && d->dtype == NR_BF16 && M % 32 == 0 && d->L <= 32 && nr_gemm_tn_slabs_ok(d->q, d->N, M, d->q, d->N);
 }
 
+// ---- the live-slab weight gradient, shared by the MHSA, convolution and pooling backward -------------------------
+// `ws` is the flag workspace laid out as nr_launch_live_slabs describes it.  First half: the n sequence flags -- a copy of the
+// caller's seq_nz, else one pass over dy [n * L, N] -- then the list of live slabs.  (The pooling backward has its flags from
+// nr_launch_row_flags_f32 already and calls nr_launch_live_slabs itself.)
+static int live_slab_list(int32_t* ws, const int32_t* seq_nz, const void* dy, int n, int L, int N, hipStream_t s) {
+  int rc = NR_OK;
+  if (seq_nz != nullptr) {                         // the consumer of the output already knows which sequences got a gradient
+    NR_CHECK_HIP(hipMemcpyAsync(ws, seq_nz, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  } else if ((rc = nr_launch_title_flags(dy, n, L, N, ws, s))) {      // one pass over dy (bf16)
+    return rc;
+  }
+  return nr_launch_live_slabs(ws, n, L, s);
+}
+// Second half (the MHSA backward runs its attention in between, and in a phased call finds the list of its phase-1 call):
+// dW += dC^T . X, db += colsum(dC) over the listed slabs.
+static int gemm_tn_live_slabs(const int32_t* ws, int n, const void* dC, int ldc, const void* X, int ldx, float* dW, int ldw, float* db, int M,
+                              int N, int K, int Nstore, int Kstore, hipStream_t s, int xgap = 0, float* scratch = nullptr, size_t scratch_floats = 0) {
+  return nr_launch_gemm_tn_slabs(dC, ldc, X, ldx, dW, ldw, db, M, N, K, Nstore, Kstore, ws + n + 4, ws + n, s, xgap,
+                                 scratch_floats ? scratch : nullptr, scratch_floats);
+}
+
 // Shapes whose conv backward contracts live 32-row slabs only (bf16, rows a multiple of 32, tn3-eligible): only then may the
 // forward leave the im2col rows of far-from-needed titles unwritten
 static bool conv_slab_shape(const nr_conv_desc* d) {
@@ -306,21 +331,54 @@ static bool conv_slab_shape(const nr_conv_desc* d) {
          nr_gemm_tn_slabs_ok(d->N, d->ld_rows, M, d->N, 3 * d->Dp);
 }
 
-// Compact row storage of the news-level training path (bf16, gather source, x_rows + row_ws given): x_rows and dqkv hold ONLY
-// the live rows (non-padding tokens), in live-list order -- the padding rows of both are never needed: a padding token
-// gathers the zero row (the projection substitutes the bias, the weight gradient would contract a zero row, padding_idx
-// gets no table gradient), and the one thing its dQ|dK|dV row feeds, the bias gradient, comes out of the attention backward
-// itself.  Halves the gradient stores of the attention backward and lets the weight-gradient GEMM contract 0.33 instead of
-// 0.57 of the rows of a MIND-shaped batch.  The forward and the backward call evaluate this same predicate.
-static bool mhsa_compact_rows(const nr_mhsa_desc* d) {
-  const int N = d->heads * d->d_head, M = d->n * d->L, Kp = round_up(d->d_model, nr_chunk(d->dtype));
-  return !nr_opt(NR_OPT_NO_COMPACT_ROWS) && !nr_opt(NR_OPT_NO_SLABS) && !nr_opt(NR_OPT_NO_SCATTER_SORT) &&
-         g_det_elems.load() == 0 && d->dtype == NR_BF16 && d->src_kind == NR_SRC_GATHER && d->x_rows != nullptr && d->row_ws != nullptr &&
-         d->b_qkv != nullptr && d->table_rows > 0 && M >= 4096 && M % 32 == 0 && (3 * N) % 8 == 0 && 3 * N <= 2048 && d->d_model % 4 == 0 &&
-         d->ld_rows >= Kp && nr_attn_compact_ok(d->dtype, d->L, d->d_head, d->heads) && nr_gemm_tn_slabs_ok(3 * N, d->ld_rows, M, 3 * N, Kp);
+// ---- the news-level training path: ONE plan, read by the forward and the backward ("MHSA training plan") ----------
+// The forward leaves rows of qkv, x_rows and y unwritten and only the matching backward knows not to read them, so both
+// take every shape-level decision from this struct, filled from the descriptor alone by mhsa_check.  What hangs on the
+// buffers of one call (alignment of qkv / y / dy / dqkv, dtable / dx / w_qkv_t, row_ws_ready, bwd_phase) is tested at the
+// use site, on top of a field.  mhsa_check has made two things true that no field repeats: b_qkv != NULL (for n > 0, and
+// no plan is made for n == 0) and, for bf16, (3N) % 8 == 0.
+struct MhsaPlan {
+  int M, Kp;            // rows; d_model rounded up to the dtype's chunk
+  bool keeps_rows;      // gather source with x_rows: the forward materialises the gathered rows there for the backward
+  bool compacts;        // the live (non-padding) rows are listed in row_ws: the projection, and the table gradient, run over them
+  bool pad_shape;       // the attention kernels can take Q|K|V of padding tokens from the bias (nr_attn_pad_ok, pointers aside)
+  bool pad_sub;         // ... and do (given 8-byte aligned buffers): qkv rows of all-padding sequences stay unwritten
+  bool row_sub;         // ... per row: no padding row of qkv is written or read
+  bool dw_slabs;        // the weight gradient contracts live 32-row slabs of dqkv / x_rows
+  bool skip_far;        // seq_needed given and dw_slabs: x_rows no live slab can reach stay unwritten
+  bool compact_rows;    // compact row storage: x_rows and dqkv hold the live rows only (below)
+  bool sorts_scatter;   // the table gradient walks the live rows in token-id order
+  bool needed_list;     // seq_needed given and a sequence of y is whole 16-byte units: the attention forward can walk a list
+};
+// Compact row storage (bf16, gather source, x_rows + row_ws given): x_rows and dqkv hold ONLY the live rows (non-padding
+// tokens), in live-list order -- the padding rows of both are never needed: a padding token gathers the zero row (the
+// projection substitutes the bias, the weight gradient would contract a zero row, padding_idx gets no table gradient), and
+// the one thing its dQ|dK|dV row feeds, the bias gradient, comes out of the attention backward itself.  Halves the gradient
+// stores of the attention backward and lets the weight-gradient GEMM contract 0.33 instead of 0.57 of the rows of a
+// MIND-shaped batch.
+static MhsaPlan mhsa_plan(const nr_mhsa_desc* d) {
+  MhsaPlan p;
+  const int N3 = 3 * d->heads * d->d_head;
+  p.M = d->n * d->L; p.Kp = round_up(d->d_model, nr_chunk(d->dtype));
+  const bool gather = d->src_kind == NR_SRC_GATHER;
+  p.keeps_rows = gather && d->x_rows != nullptr;
+  p.compacts = gather && d->row_ws != nullptr && d->dtype == NR_BF16 && p.M >= 4096;
+  p.pad_shape = nr_attn_pad_ok(d->dtype, d->L, d->d_head, nullptr, nullptr);
+  p.pad_sub = p.keeps_rows && p.compacts && p.pad_shape;
+  p.row_sub = p.pad_sub && nr_attn_rowsub_ok(d->dtype, d->L, d->d_head, d->heads);
+  p.dw_slabs = p.keeps_rows && p.compacts && !nr_opt(NR_OPT_NO_SLABS) && p.M % 32 == 0 &&
+               nr_gemm_tn_slabs_ok(N3, d->ld_rows, p.M, N3, p.Kp);
+  p.skip_far = p.dw_slabs && d->seq_needed != nullptr;
+  p.sorts_scatter = p.compacts && d->table_rows > 0 && !nr_opt(NR_OPT_NO_SCATTER_SORT);
+  // (nr_attn_compact_ok: row_sub's shape test and L <= 31; one dump row of row_ws holds 3N <= 2048 elements; not in deterministic mode)
+  p.compact_rows = p.row_sub && p.dw_slabs && p.sorts_scatter && !nr_opt(NR_OPT_NO_COMPACT_ROWS) && g_det_elems.load() == 0 && N3 <= 2048 &&
+                   d->d_model % 4 == 0 && d->ld_rows >= p.Kp && nr_attn_compact_ok(d->dtype, d->L, d->d_head, d->heads);
+  p.needed_list = d->seq_needed != nullptr && ((size_t)d->L * (N3 / 3) * nr_elt_size(d->dtype)) % 16 == 0;
+  return p;
 }
 
-static int mhsa_check(const nr_mhsa_desc* d) {
+// Argument check of the three MHSA entry points; on success *plan is the plan of this descriptor (all false for n == 0).
+static int mhsa_check(const nr_mhsa_desc* d, MhsaPlan* plan) {
   NR_CHECK_ARG(d != nullptr, "mhsa: null descriptor");
   NR_CHECK_ARG(dtype_ok(d->dtype), "mhsa: bad dtype %d", d->dtype);
   NR_CHECK_ARG(d->n >= 0 && d->L >= 1 && d->L <= 64 && d->d_model >= 1 && d->heads >= 1 && d->d_head >= 1,
@@ -336,6 +394,8 @@ static int mhsa_check(const nr_mhsa_desc* d) {
   NR_CHECK_ARG(d->row_ws == nullptr || d->row_ws_bytes >= mhsa_ws_of(d).total * sizeof(int32_t),
                "mhsa: row_ws holds %zu bytes, nr_mhsa_workspace_bytes() asks for %zu", d->row_ws_bytes,
                mhsa_ws_of(d).total * sizeof(int32_t));
+  if (d->n > 0) *plan = mhsa_plan(d);
+  else memset(plan, 0, sizeof(*plan));
   return NR_OK;
 }
 
@@ -549,16 +609,20 @@ int nr_mhsa_fwd_fused(const nr_mhsa_desc* d) {
              : 0;
 }
 
-int nr_mhsa_compact_rows(const nr_mhsa_desc* d) { return (d != nullptr && mhsa_check(d) == NR_OK && d->n > 0 && mhsa_compact_rows(d)) ? 1 : 0; }
+int nr_mhsa_compact_rows(const nr_mhsa_desc* d) {
+  MhsaPlan P;
+  return (d != nullptr && mhsa_check(d, &P) == NR_OK && P.compact_rows) ? 1 : 0;
+}
 
 int nr_mhsa_fwd(const nr_mhsa_desc* d, void* qkv, void* y, nr_stream_t stream) {
-  int rc = mhsa_check(d);
+  MhsaPlan P;
+  int rc = mhsa_check(d, &P);
   if (rc) return rc;
   if (d->n == 0) return NR_OK;
   NR_CHECK_ARG(y != nullptr, "mhsa_fwd: null output");
   hipStream_t s = (hipStream_t)stream;
   NR_DEVICE_GUARD(stream, y);
-  const int N = d->heads * d->d_head, M = d->n * d->L, Kp = round_up(d->d_model, nr_chunk(d->dtype));
+  const int N = d->heads * d->d_head, M = P.M, Kp = P.Kp;
   const MhsaWs W = mhsa_ws_of(d);
   RowSrc A;
   if ((rc = mhsa_rows(d, &A))) return rc;
@@ -583,60 +647,52 @@ int nr_mhsa_fwd(const nr_mhsa_desc* d, void* qkv, void* y, nr_stream_t stream) {
   NR_CHECK_ARG(qkv != nullptr, "mhsa_fwd: the unfused path needs the qkv buffer (see nr_mhsa_fwd_fused)");
   EpiArgs ep = store_epi(qkv, 3 * N, d->dtype, d->b_qkv, 0);
   const uint32_t* tmask = nullptr;
-  bool seq_hdr_zeroed = false;
-  if (d->x_rows != nullptr && d->src_kind == NR_SRC_GATHER) {
-    // gather + dropout once into x_rows (kept for the backward), then a plain dense projection GEMM
+  int32_t* ws = d->row_ws;
+  // ---- rows: gather + dropout once into x_rows (kept for the backward), then a plain dense projection GEMM over them
+  if (P.keeps_rows) {
     NR_CHECK_ARG(d->ld_rows >= Kp && d->ld_rows % nr_chunk(d->dtype) == 0, "mhsa_fwd: ld_rows=%d must cover %d", d->ld_rows, Kp);
-    const bool compacting = d->row_ws != nullptr && d->dtype == NR_BF16 && M >= 4096 && (3 * N) % 8 == 0;
-    const bool cstore = compacting && mhsa_compact_rows(d);     // x_rows holds the live rows only, in live-list order
     // Padding tokens (id 0) gather the zero row of the table: their projection is the bias.  Project the live rows
     // only (compacted on the device) and write the bias into the others.  If table row 0 is not zero, the
     // compaction keeps every row and nothing changes.
     // (the compaction kernel also clears the counters of the "needed" list built further down: one memset less in the chain)
-    if (compacting && (rc = nr_launch_compact_rows_fwd(d->ids, M, d->n, d->L, d->x, d->d_model, d->row_ws, s, cstore ? d->row_ws + W.pos : nullptr,
-                                                       d->row_ws + W.seq, cstore ? d->row_ws + W.hist : nullptr, d->table_rows)))
+    if (P.compacts && (rc = nr_launch_compact_rows_fwd(d->ids, M, d->n, d->L, d->x, d->d_model, ws, s, P.compact_rows ? ws + W.pos : nullptr,
+                                                       ws + W.seq, P.compact_rows ? ws + W.hist : nullptr, d->table_rows)))
       return rc;
-    seq_hdr_zeroed = compacting;
-    if (cstore) {
-      NR_CHECK_ARG(nr_attn_pad_ok(d->dtype, d->L, d->d_head, qkv, y), "mhsa_fwd: qkv / y must be 8-byte aligned");
-      if ((rc = nr_launch_gather_live_rows(d->dtype, A, d->x_rows, d->ld_rows, M, Kp, d->row_ws, d->row_ws + W.live_idx, d->row_ws + W.live_ids, s,
-                                           d->row_ws + W.hist, d->table_rows)))       // (+ the id histogram for the backward's sort)
-        return rc;
-      A = dense_rows(d->x_rows, d->ld_rows, d->d_model);
-      ep.row_count = d->row_ws; ep.row_idx = d->row_ws + W.live_idx; ep.row_ids = d->row_ws + W.live_ids;
-      ep.a_dense = 1;                                  // A row k = live row k; row_idx scatters the output rows
-      tmask = reinterpret_cast<const uint32_t*>(d->row_ws + W.tmask);      // per-row substitution: no bias rows are written
-    } else {
-    // under "needed" flags the rows of all-padding sequences no weight-gradient slab can reach are not even written
-    // (only where the backward contracts live slabs: a dense contraction would read every row)
-    const bool skip_far = compacting && d->seq_needed != nullptr && M % 32 == 0 && nr_gemm_tn_slabs_ok(3 * N, d->ld_rows, M, 3 * N, Kp) &&
-                          !nr_opt(NR_OPT_NO_SLABS);
-    if ((rc = nr_launch_rows_materialize(d->dtype, A, d->x_rows, d->ld_rows, M, Kp, s, skip_far ? d->seq_needed : nullptr, 32 / d->L + 2,
-                                         d->L, skip_far ? d->row_ws + 2 : nullptr)))
+    if (P.compacts) { ep.row_count = ws; ep.row_idx = ws + W.live_idx; ep.row_ids = ws + W.live_ids; }
+  }
+  if (P.compact_rows) {
+    // ---- compact row storage: x_rows holds the live rows only, in live-list order; the attention kernels substitute per row
+    NR_CHECK_ARG(aligned(8, qkv, y), "mhsa_fwd: qkv / y must be 8-byte aligned");
+    if ((rc = nr_launch_gather_live_rows(d->dtype, A, d->x_rows, d->ld_rows, M, Kp, ws, ws + W.live_idx, ws + W.live_ids, s,
+                                         ws + W.hist, d->table_rows)))       // (+ the id histogram for the backward's sort)
       return rc;
     A = dense_rows(d->x_rows, d->ld_rows, d->d_model);
-    if (compacting) {
-      ep.row_count = d->row_ws; ep.row_idx = d->row_ws + W.live_idx; ep.row_ids = d->row_ws + W.live_ids;
-      // Sequences made of padding tokens only (empty history slots, ~45 % of the titles of a MIND-shaped batch): the
-      // attention kernels take their Q|K|V from the bias themselves (per-sequence live mask == 0), so those qkv rows are
-      // neither written here nor read there.  The bias goes into the padding rows of the other sequences.
-      if (d->b_qkv != nullptr && nr_attn_pad_ok(d->dtype, d->L, d->d_head, qkv, y))
-        tmask = reinterpret_cast<const uint32_t*>(d->row_ws + W.tmask);
-      // ... unless the attention kernels substitute per row (then no padding row of qkv is ever written or read)
-      if (!(tmask != nullptr && nr_attn_rowsub_ok(d->dtype, d->L, d->d_head, d->heads)) &&
-          (rc = nr_launch_bias_rows(qkv, 3 * N, 3 * N, d->b_qkv, d->row_ws + W.dead_idx, d->row_ws + 1, M, tmask, d->L, s)))
-        return rc;
-    }
-    }
+    ep.a_dense = 1;                                  // A row k = live row k; row_idx scatters the output rows
+    tmask = reinterpret_cast<const uint32_t*>(ws + W.tmask);
+  } else if (P.keeps_rows) {
+    // ---- one x_rows row per token.  Under "needed" flags the rows of all-padding sequences no weight-gradient slab can
+    // reach are not even written (only where the backward contracts live slabs: a dense contraction would read every row)
+    if ((rc = nr_launch_rows_materialize(d->dtype, A, d->x_rows, d->ld_rows, M, Kp, s, P.skip_far ? d->seq_needed : nullptr, 32 / d->L + 2,
+                                         d->L, P.skip_far ? ws + 2 : nullptr)))
+      return rc;
+    A = dense_rows(d->x_rows, d->ld_rows, d->d_model);
+    // Sequences made of padding tokens only (empty history slots, ~45 % of the titles of a MIND-shaped batch): the
+    // attention kernels take their Q|K|V from the bias themselves (per-sequence live mask == 0), so those qkv rows are
+    // neither written here nor read there.  The bias goes into the padding rows of the other sequences.
+    if (P.pad_sub && aligned(8, qkv, y)) tmask = reinterpret_cast<const uint32_t*>(ws + W.tmask);
+    // ... unless the attention kernels substitute per row (then no padding row of qkv is ever written or read)
+    if (P.compacts && !(tmask != nullptr && P.row_sub) &&
+        (rc = nr_launch_bias_rows(qkv, 3 * N, 3 * N, d->b_qkv, ws + W.dead_idx, ws + 1, M, tmask, d->L, s)))
+      return rc;
   }
   if ((rc = nr_launch_gemm_nt(d->dtype, A, d->w_qkv, d->ldw, M, 3 * N, Kp, EPI_STORE, ep, s))) return rc;
   // "output not needed" flags: with the compaction scratch at hand the attention kernel walks a device-side list of the
   // needed sequences and a store-only kernel zero-fills the y rows of the others; without it the kernel skips in place
   const int32_t* fwd_list = nullptr;
-  if (d->seq_needed != nullptr && tmask != nullptr && ((size_t)d->L * N * nr_elt_size(d->dtype)) % 16 == 0 && (((uintptr_t)y) & 15) == 0) {
-    int32_t* lw = d->row_ws + W.seq;
+  if (P.needed_list && tmask != nullptr && aligned(16, y)) {
+    int32_t* lw = ws + W.seq;
     if ((rc = nr_launch_needed_list(d->seq_needed, d->n, lw, y, (size_t)d->L * N * nr_elt_size(d->dtype), s,
-                                    d->y_far_unwritten ? 32 / d->L + 2 : -1, seq_hdr_zeroed)))
+                                    d->y_far_unwritten ? 32 / d->L + 2 : -1, /*tmask: the compaction ran and cleared the list's counters*/true)))
       return rc;
     fwd_list = lw;
   }
@@ -645,106 +701,85 @@ int nr_mhsa_fwd(const nr_mhsa_desc* d, void* qkv, void* y, nr_stream_t stream) {
                         fwd_list ? nullptr : d->seq_needed);
 }
 
-int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dqkv, const void* w_qkv_t, int ldwt,
-                float* dw_qkv, float* db_qkv, void* dx, float* dtable, nr_stream_t stream) {
-  int rc = mhsa_check(d);
-  if (rc) return rc;
-  if (d->n == 0) return NR_OK;
-  NR_CHECK_ARG(qkv && dy && dqkv && dw_qkv && db_qkv, "mhsa_bwd: null operand");
-  hipStream_t s = (hipStream_t)stream;
-  NR_DEVICE_GUARD(stream, dqkv);
-  const int N = d->heads * d->d_head, M = d->n * d->L, ch = nr_chunk(d->dtype), Kp = round_up(d->d_model, ch);
+// Backward with compact row storage: x_rows holds the live rows in live-list order (forward), dqkv gets them in the same
+// order; dW = dqkv_c^T . x_c over `count` dense rows, db from the attention kernel, the table gradient reads dqkv_c through
+// the id-sorted positions
+static int mhsa_bwd_compact(const nr_mhsa_desc* d, const MhsaPlan& P, const uint32_t* tmask, const void* qkv, const void* dy, void* dqkv,
+                            const void* w_qkv_t, int ldwt, float* dw_qkv, float* db_qkv, void* dx, float* dtable, hipStream_t s) {
+  int rc = NR_OK;
+  const int N = d->heads * d->d_head, M = P.M;
   const MhsaWs W = mhsa_ws_of(d);
-  RowSrc A;
-  if ((rc = mhsa_rows(d, &A))) return rc;
-  NR_CHECK_ARG(d->bwd_phase >= 0 && d->bwd_phase <= 2, "mhsa_bwd: bwd_phase=%d", d->bwd_phase);
-  const bool ph_main = d->bwd_phase != 2;          // flags, attention backward, dx / table gradient
-  const bool ph_dw = d->bwd_phase != 1;            // weight / bias gradients
-  // row_ws_ready: the forward compacted the rows and (when the attention kernels support it) left the qkv rows of
-  // padding tokens unwritten -- the backward attention must substitute the bias exactly as the forward one did
-  const uint32_t* tmask = nullptr;
-  if (d->row_ws != nullptr && d->row_ws_ready && d->src_kind == NR_SRC_GATHER && d->dtype == NR_BF16 && M >= 4096 &&
-      (3 * N) % 8 == 0 && d->b_qkv != nullptr && d->x_rows != nullptr && nr_attn_pad_ok(d->dtype, d->L, d->d_head, nullptr, nullptr)) {
-    // shape-wise the forward substituted; whether it really did also hung on the alignment of its qkv / y
-    NR_CHECK_ARG(nr_attn_pad_ok(d->dtype, d->L, d->d_head, qkv, dqkv) && (((uintptr_t)dy) & 7) == 0,
-                 "mhsa_bwd: the forward left padding rows of qkv unwritten; qkv / dy / dqkv must be 8-byte aligned");
-    tmask = reinterpret_cast<const uint32_t*>(d->row_ws + W.tmask);
-  }
-  if (d->row_ws_ready && mhsa_compact_rows(d)) {
-    // ---- compact row storage (see mhsa_compact_rows): x_rows holds the live rows in live-list order (forward), dqkv gets them
-    // in the same order; dW = dqkv_c^T . x_c over `count` dense rows, db from the attention kernel, the table gradient reads
-    // dqkv_c through the id-sorted positions
-    NR_CHECK_ARG(tmask != nullptr, "mhsa_bwd: the forward stored x_rows compactly; qkv / dy / dqkv must be 8-byte aligned");
-    NR_CHECK_ARG(!d->dy_far_unwritten || d->seq_nz != nullptr, "mhsa_bwd: dy_far_unwritten needs the seq_nz flags");
-    // dtable == NULL: a frozen table -- no table gradient, so no id sort and no scatter GEMM; the attention backward, db and dW
-    // still run
-    NR_CHECK_ARG(dx == nullptr && (dtable == nullptr || (w_qkv_t != nullptr && ldwt >= 3 * N)),
-                 "mhsa_bwd: gather source takes dtable or nothing, not dx (and with dtable, w_qkv_t [d_model, >=3N])");
-    int32_t* ws = d->row_ws;
-    if (ph_main) {
-      // n sequence flags: which sequences got a non-zero upstream gradient (the caller's, read in place, or made here)
-      const int32_t* slab_ws = d->seq_nz;
-      if (slab_ws == nullptr) {
-        if ((rc = nr_launch_title_flags(dy, d->n, d->L, N, ws + W.slab, s))) return rc;
-        slab_ws = ws + W.slab;
-      }
-      // rows count .. roundup32(count) of dqkv: the weight-gradient GEMM contracts whole 32-row slabs (x_c is zero there);
-      // the same launch clears the counters of the sequence list that follows
-      int32_t* seq_ws = ws + W.seq;
-      if ((rc = nr_launch_zero_tail_rows(dqkv, 3 * N, ws, M, s, seq_ws, 4))) return rc;
-      // the walk leaves out the all-padding sequences with a zero gradient (nothing to store, nothing to add to db); slab
-      // distances do not matter any more -- no slab is contracted -- so the list kernel runs with a zero reach
-      if ((rc = nr_launch_seq_list(slab_ws, tmask, d->n, d->L, seq_ws, s, /*reach=*/0, /*zeroed=*/true))) return rc;
-      if ((rc = nr_launch_attn_bwd_compact(qkv, d->mask, dy, dqkv, d->n, d->L, d->heads, d->d_head, nr_make_drop(d->p_out, d->seed_out), s, tmask,
-                                           d->b_qkv, seq_ws + 4, seq_ws, ws + W.pos, ws + W.dump, db_qkv, d->dy_far_unwritten ? slab_ws : nullptr)))
-        return rc;
+  NR_CHECK_ARG(tmask != nullptr, "mhsa_bwd: the forward stored x_rows compactly; qkv / dy / dqkv must be 8-byte aligned");
+  NR_CHECK_ARG(!d->dy_far_unwritten || d->seq_nz != nullptr, "mhsa_bwd: dy_far_unwritten needs the seq_nz flags");
+  // dtable == NULL: a frozen table -- no table gradient, so no id sort and no scatter GEMM; the attention backward, db and dW
+  // still run
+  NR_CHECK_ARG(dx == nullptr && (dtable == nullptr || (w_qkv_t != nullptr && ldwt >= 3 * N)),
+               "mhsa_bwd: gather source takes dtable or nothing, not dx (and with dtable, w_qkv_t [d_model, >=3N])");
+  int32_t* ws = d->row_ws;
+  if (d->bwd_phase != 2) {
+    // n sequence flags: which sequences got a non-zero upstream gradient (the caller's, read in place, or made here)
+    const int32_t* flags = d->seq_nz;
+    if (flags == nullptr) {
+      if ((rc = nr_launch_title_flags(dy, d->n, d->L, N, ws + W.slab, s))) return rc;
+      flags = ws + W.slab;
+    }
+    // rows count .. roundup32(count) of dqkv: the weight-gradient GEMM contracts whole 32-row slabs (x_c is zero there);
+    // the same launch clears the counters of the sequence list that follows
+    int32_t* seq_ws = ws + W.seq;
+    if ((rc = nr_launch_zero_tail_rows(dqkv, 3 * N, ws, M, s, seq_ws, 4))) return rc;
+    // the walk leaves out the all-padding sequences with a zero gradient (nothing to store, nothing to add to db); slab
+    // distances do not matter any more -- no slab is contracted -- so the list kernel runs with a zero reach
+    if ((rc = nr_launch_seq_list(flags, tmask, d->n, d->L, seq_ws, s, /*reach=*/0, /*zeroed=*/true))) return rc;
+    if ((rc = nr_launch_attn_bwd_compact(qkv, d->mask, dy, dqkv, d->n, d->L, d->heads, d->d_head, nr_make_drop(d->p_out, d->seed_out), s, tmask,
+                                         d->b_qkv, seq_ws + 4, seq_ws, ws + W.pos, ws + W.dump, db_qkv, d->dy_far_unwritten ? flags : nullptr)))
+      return rc;
+    if (dtable != nullptr) {
       // table gradient: rows in token-id order, A rows through their live-list positions
-      if (dtable != nullptr && (rc = nr_launch_sort_rows_by_id(ws, ws + W.live_idx, ws + W.live_ids, M, d->table_rows, ws + W.hist, ws + W.sort_idx, ws + W.sort_ids, s,
+      if ((rc = nr_launch_sort_rows_by_id(ws, ws + W.live_idx, ws + W.live_ids, M, d->table_rows, ws + W.hist, ws + W.sort_idx, ws + W.sort_ids, s,
                                           ws + W.sort_k, /*histogram counted by the forward:*/ws + W.cursor)))
         return rc;
-      if (dtable != nullptr) {
-        EpiArgs ep = store_epi(dtable, d->d_model, NR_F32, nullptr, 0);
-        ep.ids = d->ids; ep.ids_stride = 1; ep.Dtrue = d->d_model; ep.drop = nr_make_drop(d->p_in, d->seed_in);
-        ep.row_count = ws; ep.row_idx = ws + W.sort_idx; ep.row_ids = ws + W.sort_ids; ep.a_idx = ws + W.sort_k;
-        RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
-        if ((rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_SCATTER, ep, s))) return rc;
-      }
+      EpiArgs ep = store_epi(dtable, d->d_model, NR_F32, nullptr, 0);
+      ep.ids = d->ids; ep.ids_stride = 1; ep.Dtrue = d->d_model; ep.drop = nr_make_drop(d->p_in, d->seed_in);
+      ep.row_count = ws; ep.row_idx = ws + W.sort_idx; ep.row_ids = ws + W.sort_ids; ep.a_idx = ws + W.sort_k;
+      RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
+      if ((rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_SCATTER, ep, s))) return rc;
     }
-    if (ph_dw && (rc = nr_launch_gemm_tn_counted(dqkv, 3 * N, d->x_rows, d->ld_rows, dw_qkv, d->d_model, M, 3 * N, Kp, 3 * N, d->d_model, ws, s,
-                                                 W.tn_floats ? reinterpret_cast<float*>(ws + W.tn_scratch) : nullptr, W.tn_floats)))
-      return rc;
-    return NR_OK;
   }
+  if (d->bwd_phase != 1)
+    rc = nr_launch_gemm_tn_counted(dqkv, 3 * N, d->x_rows, d->ld_rows, dw_qkv, d->d_model, M, 3 * N, P.Kp, 3 * N, d->d_model, ws, s,
+                                   W.tn_floats ? reinterpret_cast<float*>(ws + W.tn_scratch) : nullptr, W.tn_floats);
+  return rc;
+}
+
+// Backward with one dqkv row per token (and one x_rows row per token when the forward kept rows).
+static int mhsa_bwd_rows(const nr_mhsa_desc* d, const MhsaPlan& P, const uint32_t* tmask, const RowSrc& A, const void* qkv, const void* dy,
+                         void* dqkv, const void* w_qkv_t, int ldwt, float* dw_qkv, float* db_qkv, void* dx, float* dtable, hipStream_t s) {
+  int rc = NR_OK;
+  const int N = d->heads * d->d_head, M = P.M, Kp = P.Kp;
+  const MhsaWs W = mhsa_ws_of(d);
+  const bool ph_main = d->bwd_phase != 2;          // flags, attention backward, dx / table gradient
+  const bool ph_dw = d->bwd_phase != 1;            // weight / bias gradients
   NR_CHECK_ARG(!d->dy_far_unwritten, "mhsa_bwd: dy_far_unwritten is only honoured with compact row storage (nr_mhsa_compact_rows)");
   // Sequences whose upstream gradient dy is exactly zero (history slots the user encoder masks out) get exact zeros in
   // dQ|dK|dV (dP = dy.V^T = 0, so dS = 0): a pass over dy flags the others, and the weight-gradient GEMM contracts only
   // the 32-row slabs that touch a flagged sequence.  Scratch: the tail of row_ws (n flags, count, M/32 slab ids).
-  const bool no_slabs = nr_opt(NR_OPT_NO_SLABS) != 0;
   int32_t* slab_ws = nullptr;
   int32_t* seq_ws = nullptr;
-  if (!no_slabs && d->row_ws != nullptr && d->dtype == NR_BF16 && d->src_kind == NR_SRC_GATHER && d->x_rows != nullptr && M % 32 == 0 &&
-      M >= 4096 && nr_attn_pad_ok(d->dtype, d->L, d->d_head, qkv, dqkv) && (((uintptr_t)dy) & 7) == 0 &&
-      nr_gemm_tn_slabs_ok(3 * N, d->ld_rows, M, 3 * N, Kp)) {
+  // (pad_shape: an extra term of this site alone -- the forward's skip_far does not ask for it, so L > 32 under seq_needed
+  //  ends in the check below; kept as found)
+  if (P.dw_slabs && P.pad_shape && aligned(8, qkv, dqkv, dy)) {
     slab_ws = d->row_ws + W.slab;
-    if (ph_main) {                                 // (phase 2 finds the lists of its phase-1 call in row_ws)
-      if (d->seq_nz != nullptr) {                  // the consumer of y already knows which sequences got a gradient
-        NR_CHECK_HIP(hipMemcpyAsync(slab_ws, d->seq_nz, (size_t)d->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-      } else if ((rc = nr_launch_title_flags(dy, d->n, d->L, N, slab_ws, s))) {      // one pass over dy (bf16 [M, N])
-        return rc;
-      }
-      if ((rc = nr_launch_live_slabs(slab_ws, d->n, d->L, s))) return rc;
-    }
+    // (phase 2 finds the lists of its phase-1 call in row_ws)
+    if (ph_main && (rc = live_slab_list(slab_ws, d->seq_nz, dy, d->n, d->L, N, s))) return rc;
     if (tmask != nullptr) {
       // the attention backward walks a list that leaves out the all-padding sequences no live slab comes near
       seq_ws = d->row_ws + W.seq;
       if (ph_main && (rc = nr_launch_seq_list(slab_ws, tmask, d->n, d->L, seq_ws, s))) return rc;
     }
   }
-  // x_rows written under "needed" flags (nr_mhsa_fwd: skip_far) are complete only where a live slab can reach: the slab
-  // path is then mandatory (a dense contraction would multiply unwritten rows by their zero gradient)
-  NR_CHECK_ARG(!(d->row_ws_ready && d->seq_needed != nullptr && d->row_ws != nullptr && d->dtype == NR_BF16 && d->src_kind == NR_SRC_GATHER &&
-                 d->x_rows != nullptr && M >= 4096 && (3 * N) % 8 == 0 && M % 32 == 0 && nr_gemm_tn_slabs_ok(3 * N, d->ld_rows, M, 3 * N, Kp) &&
-                 !no_slabs) || slab_ws != nullptr,
+  // x_rows written under "needed" flags are complete only where a live slab can reach: the slab path is then mandatory (a
+  // dense contraction would multiply unwritten rows by their zero gradient)
+  NR_CHECK_ARG(!(d->row_ws_ready && P.skip_far) || slab_ws != nullptr,
                "mhsa_bwd: x_rows were materialised under seq_needed: qkv / dqkv / dy must be 8-byte aligned so that the live-slab path runs");
   if (ph_main && (rc = nr_launch_attn(true, d->dtype, qkv, d->mask, nullptr, dy, dqkv, d->n, d->L, d->heads, d->d_head,
                                       nr_make_drop(d->p_out, d->seed_out), s, tmask, tmask ? d->b_qkv : nullptr,
@@ -752,11 +787,10 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
     return rc;
   // dW_qkv[3N, d_model] += dQKV^T . X ; db += colsum(dQKV).  X: the rows saved by the forward when present.
   RowSrc Xs = A;
-  if (d->x_rows != nullptr && d->src_kind == NR_SRC_GATHER) {
+  if (P.keeps_rows) {
     NR_CHECK_ARG(d->ld_rows >= Kp, "mhsa_bwd: ld_rows=%d must cover %d", d->ld_rows, Kp);
     Xs = dense_rows(d->x_rows, d->ld_rows, d->d_model);
   }
-  const bool want_dx = dx != nullptr || dtable != nullptr;
   DetScope det(s);
   NR_CHECK_ARG(!det.on() || d->bwd_phase == 0, "mhsa_bwd: deterministic mode runs the backward in one call (bwd_phase = 0)");
   if (det.on()) {
@@ -766,7 +800,7 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
     if (dtable != nullptr) det.add(dtable, (size_t)d->table_rows * d->d_model);
     if ((rc = det.begin(true, false))) return rc;
   }
-  if (want_dx && ph_main) {
+  if ((dx != nullptr || dtable != nullptr) && ph_main) {
     NR_CHECK_ARG(w_qkv_t != nullptr && ldwt >= 3 * N, "mhsa_bwd: w_qkv_t [d_model, >=3N] needed for dx / dtable");
     RowSrc G = dense_rows(dqkv, 3 * N, 3 * N);
     if (d->src_kind == NR_SRC_GATHER) {
@@ -774,18 +808,18 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
       NR_CHECK_ARG(d->d_model % 4 == 0, "mhsa_bwd: d_model=%d must be a multiple of 4", d->d_model);
       EpiArgs ep = store_epi(dtable, d->d_model, NR_F32, nullptr, 0);
       ep.ids = d->ids; ep.ids_stride = 1; ep.Dtrue = d->d_model; ep.drop = nr_make_drop(d->p_in, d->seed_in);
-      if (d->row_ws != nullptr && d->dtype == NR_BF16 && M >= 4096) {
+      if (P.compacts) {
         // only rows with a non-padding token id reach the table gradient: compact them, GEMM over those alone
-        if (!d->row_ws_ready && (rc = nr_launch_compact_rows(d->ids, 1, M, d->row_ws, s))) return rc;
-        ep.row_count = d->row_ws; ep.row_idx = d->row_ws + W.live_idx; ep.row_ids = d->row_ws + W.live_ids;
-        if (d->table_rows > 0 && !nr_opt(NR_OPT_NO_SCATTER_SORT)) {
+        int32_t* ws = d->row_ws;
+        if (!d->row_ws_ready && (rc = nr_launch_compact_rows(d->ids, 1, M, ws, s))) return rc;
+        ep.row_count = ws; ep.row_idx = ws + W.live_idx; ep.row_ids = ws + W.live_ids;
+        if (P.sorts_scatter) {
           // ... in token-id order: occurrences of one word become neighbours, the scatter epilogue adds them up in
           // registers and issues one atomic row per run instead of one per occurrence (memory-side fp32 atomics run at
           // ~1.3 TB/s chip-wide; a MIND-shaped batch repeats each word ~9 times)
-          if ((rc = nr_launch_sort_rows_by_id(d->row_ws, ep.row_idx, ep.row_ids, M, d->table_rows, d->row_ws + W.hist,
-                                              d->row_ws + W.sort_idx, d->row_ws + W.sort_ids, s)))
+          if ((rc = nr_launch_sort_rows_by_id(ws, ep.row_idx, ep.row_ids, M, d->table_rows, ws + W.hist, ws + W.sort_idx, ws + W.sort_ids, s)))
             return rc;
-          ep.row_idx = d->row_ws + W.sort_idx; ep.row_ids = d->row_ws + W.sort_ids;
+          ep.row_idx = ws + W.sort_idx; ep.row_ids = ws + W.sort_ids;
         }
       }
       rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_SCATTER, ep, s);
@@ -796,21 +830,42 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
       EpiArgs ep = store_epi(dx, d->ldx, d->dtype, nullptr, 0);
       rc = nr_launch_gemm_nt(d->dtype, G, w_qkv_t, ldwt, M, d->d_model, 3 * N, EPI_STORE, ep, s);
     }
+    if (rc) return rc;
   }
-  if (rc) return rc;
   // (after the table gradient: in a phased call the host's all-reduce of that gradient overlaps this GEMM)
   if (ph_dw) {
-    if (slab_ws != nullptr) {
-      if ((rc = nr_launch_gemm_tn_slabs(dqkv, 3 * N, d->x_rows, d->ld_rows, dw_qkv, d->d_model, db_qkv, M, 3 * N, Kp, 3 * N, d->d_model,
-                                        slab_ws + d->n + 4, slab_ws + d->n, s, 0,
-                                        W.tn_floats ? reinterpret_cast<float*>(d->row_ws + W.tn_scratch) : nullptr, W.tn_floats)))
-        return rc;
-    } else if ((rc = nr_launch_gemm_tn(d->dtype, dqkv, 3 * N, Xs, dw_qkv, d->d_model, db_qkv, M, 3 * N, Kp, 3 * N, d->d_model, s))) {
-      return rc;
-    }
+    if (slab_ws != nullptr)
+      rc = gemm_tn_live_slabs(slab_ws, d->n, dqkv, 3 * N, d->x_rows, d->ld_rows, dw_qkv, d->d_model, db_qkv, M, 3 * N, Kp, 3 * N, d->d_model, s, 0,
+                              reinterpret_cast<float*>(d->row_ws + W.tn_scratch), W.tn_floats);
+    else
+      rc = nr_launch_gemm_tn(d->dtype, dqkv, 3 * N, Xs, dw_qkv, d->d_model, db_qkv, M, 3 * N, Kp, 3 * N, d->d_model, s);
+    if (rc) return rc;
   }
-  const int rd = det.end();
-  return rc ? rc : rd;
+  return det.end();
+}
+
+int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dqkv, const void* w_qkv_t, int ldwt,
+                float* dw_qkv, float* db_qkv, void* dx, float* dtable, nr_stream_t stream) {
+  MhsaPlan P;
+  int rc = mhsa_check(d, &P);
+  if (rc) return rc;
+  if (d->n == 0) return NR_OK;
+  NR_CHECK_ARG(qkv && dy && dqkv && dw_qkv && db_qkv, "mhsa_bwd: null operand");
+  NR_DEVICE_GUARD(stream, dqkv);
+  RowSrc A;
+  if ((rc = mhsa_rows(d, &A))) return rc;
+  NR_CHECK_ARG(d->bwd_phase >= 0 && d->bwd_phase <= 2, "mhsa_bwd: bwd_phase=%d", d->bwd_phase);
+  // row_ws_ready: the forward compacted the rows and, shape-wise, left the qkv rows of padding tokens unwritten (whether it
+  // really did also hung on the alignment of its qkv / y) -- the backward attention must substitute the bias exactly as
+  // the forward one did
+  const uint32_t* tmask = nullptr;
+  if (d->row_ws_ready && P.pad_sub) {
+    NR_CHECK_ARG(aligned(8, qkv, dqkv, dy), "mhsa_bwd: the forward left padding rows of qkv unwritten; qkv / dy / dqkv must be 8-byte aligned");
+    tmask = reinterpret_cast<const uint32_t*>(d->row_ws + mhsa_ws_of(d).tmask);
+  }
+  if (d->row_ws_ready && P.compact_rows)
+    return mhsa_bwd_compact(d, P, tmask, qkv, dy, dqkv, w_qkv_t, ldwt, dw_qkv, db_qkv, dx, dtable, (hipStream_t)stream);
+  return mhsa_bwd_rows(d, P, tmask, A, qkv, dy, dqkv, w_qkv_t, ldwt, dw_qkv, db_qkv, dx, dtable, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------- Conv1d k=3
@@ -879,22 +934,15 @@ int nr_conv1d_k3_bwd(const nr_conv_desc* d, const void* dy, float* dw_pack, floa
     A = dense_rows(d->x_rows, d->Dp, 3 * d->Dp);
     A.gap = d->T;
     // titles with an exactly zero upstream gradient (masked history slots) add nothing to dW / db: live slabs only
-    const bool no_slabs = nr_opt(NR_OPT_NO_SLABS) != 0;
-    const int M = d->n * d->T;
+    const bool slab_shape = conv_slab_shape(d), slabs = slab_shape && d->bwd_ws != nullptr && aligned(16, dy);
     // x_rows written under "needed" flags are complete only where a live slab can reach: the slab path is then mandatory
-    NR_CHECK_ARG(!(d->seq_needed != nullptr && conv_slab_shape(d)) || (d->bwd_ws != nullptr && (((uintptr_t)dy) & 15) == 0),
+    NR_CHECK_ARG(!(d->seq_needed != nullptr && slab_shape) || slabs,
                  "conv1d_bwd: x_rows were materialised under seq_needed: bwd_ws (and a 16-byte aligned dy) are required");
-    if (!no_slabs && d->bwd_ws != nullptr && d->dtype == NR_BF16 && M % 32 == 0 && d->T <= 32 && d->N % 8 == 0 &&
-        (((uintptr_t)dy) & 15) == 0 && nr_gemm_tn_slabs_ok(d->N, d->ld_rows, M, d->N, 3 * d->Dp)) {
+    if (slabs) {
       hipStream_t s = (hipStream_t)stream;
-      if (d->seq_nz != nullptr) {
-        NR_CHECK_HIP(hipMemcpyAsync(d->bwd_ws, d->seq_nz, (size_t)d->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-      } else if ((rc = nr_launch_title_flags(dy, d->n, d->T, d->N, d->bwd_ws, s))) {
-        return rc;
-      }
-      if ((rc = nr_launch_live_slabs(d->bwd_ws, d->n, d->T, s))) return rc;
-      return nr_launch_gemm_tn_slabs(dy, d->N, d->x_rows, d->Dp, dw_pack, 3 * d->Dp, db, M, d->N, 3 * d->Dp, d->N, 3 * d->Dp,
-                                     d->bwd_ws + d->n + 4, d->bwd_ws + d->n, s, d->T);
+      if ((rc = live_slab_list(d->bwd_ws, d->seq_nz, dy, d->n, d->T, d->N, s))) return rc;
+      return gemm_tn_live_slabs(d->bwd_ws, d->n, dy, d->N, d->x_rows, d->Dp, dw_pack, 3 * d->Dp, db, d->n * d->T, d->N, 3 * d->Dp, d->N, 3 * d->Dp,
+                                s, d->T);
     }
   }
   return nr_launch_gemm_tn(d->dtype, dy, d->N, A, dw_pack, 3 * d->Dp, db, d->n * d->T, d->N, 3 * d->Dp, d->N, 3 * d->Dp,
@@ -977,17 +1025,14 @@ int nr_additive_pool_bwd(const nr_pool_desc* d, const void* e, const float* alph
       return rc;
     if ((rc = nr_launch_colsum_split(partial, rows, d->q + 1, d->q + 1, dw2, d->q, db2, s))) return rc;
     if ((rc = nr_launch_live_slabs(ws, d->n, d->L, s))) return rc;
-    return nr_launch_gemm_tn_slabs(dpre, d->q, d->x, d->N, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, ws + d->n + 4, ws + d->n, s, 0,
-                                   tn_floats ? tn_scratch : nullptr, tn_floats);
+    return gemm_tn_live_slabs(ws, d->n, dpre, d->q, d->x, d->N, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, s, 0, tn_scratch, tn_floats);
   }
   if ((rc = nr_launch_pool_core_bwd(d->dtype, d->x, e, d->w2, alpha, g, ld_g, dpre, partial, dw2, db2, d->n, d->L, d->N, d->q, s, zero_flags)))
     return rc;
   RowSrc X = dense_rows(d->x, d->N, d->N);
   if (ws != nullptr) {
     if ((rc = nr_launch_live_slabs(ws, d->n, d->L, s))) return rc;
-    if ((rc = nr_launch_gemm_tn_slabs(dpre, d->q, d->x, d->N, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, ws + d->n + 4, ws + d->n, s, 0,
-                                      tn_floats ? tn_scratch : nullptr, tn_floats)))
-      return rc;
+    if ((rc = gemm_tn_live_slabs(ws, d->n, dpre, d->q, d->x, d->N, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, s, 0, tn_scratch, tn_floats))) return rc;
   } else if ((rc = nr_launch_gemm_tn(d->dtype, dpre, d->q, X, dw1, d->N, db1, M, d->q, d->N, d->q, d->N, s))) {
     return rc;
   }

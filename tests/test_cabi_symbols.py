@@ -91,3 +91,46 @@ def test_undersized_workspace_is_refused_before_any_launch():
     p = _lib.PoolDesc(n=64, L=30, N=400, q=200, dtype=_lib.NR_BF16, x=16, w1=16, ldw1=400, b1=16, w2=16, b2=16, partial_bytes=8)
     rc = lib.nr_additive_pool_bwd(C.byref(p), 16, 16, 16, 400, 16, 200, 16, 16, 16, 16, 16, 16, None, None)
     assert rc == 1 and "nr_pool_workspace_bytes" in _lib.last_error()
+
+
+def _mind_title_desc(**changes):
+    """The MIND title-level training descriptor (bf16, gather source, rows kept, scratch given) with fake non-null pointers;
+    row_ws_bytes is what the library asks for after the changes."""
+    import ctypes as C
+    f = dict(n=28160, L=30, d_model=300, heads=20, d_head=20, dtype=_lib.NR_BF16, src_kind=_lib.NR_SRC_GATHER, x=4096, ldx=304,
+             ids=4096, w_qkv=4096, ldw=304, b_qkv=4096, x_rows=4096, ld_rows=304, row_ws=4096, table_rows=30000)
+    f.update(changes)
+    d = _lib.MhsaDesc(**f)
+    need = _lib.lib().nr_mhsa_workspace_bytes(C.byref(d))
+    assert need > 0
+    d.row_ws_bytes = need
+    return d
+
+
+COMPACT_ROWS_OFF = {"fp32": dict(dtype=_lib.NR_F32), "dense_source": dict(src_kind=_lib.NR_SRC_DENSE, ids=None),
+                    "no_x_rows": dict(x_rows=None), "no_row_ws": dict(row_ws=None), "no_table_rows": dict(table_rows=0),
+                    "M_below_4096": dict(n=128), "M_not_multiple_of_32": dict(n=28161), "L_32": dict(L=32),
+                    "ld_rows_below_Kp": dict(ld_rows=296)}
+
+
+def test_compact_rows_plan_over_a_descriptor_grid():
+    """nr_mhsa_compact_rows is the exported face of the MHSA training plan: 1 for the MIND title shape in bf16, and 0 when any
+    single term of the plan is taken away -- each descriptor still passes the argument check (a workspace size > 0 and a
+    row_ws_bytes of that size), so every zero comes from its own term.  Host arithmetic only."""
+    import ctypes as C
+    lib = _lib.lib()
+    assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc())) == 1
+    assert lib.nr_mhsa_compact_rows(None) == 0
+    for name, change in COMPACT_ROWS_OFF.items():
+        assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc(**change))) == 0, name
+    # the neighbours on the permitted side of each bound still store compactly; an empty batch stores nothing
+    assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc(n=0))) == 0
+    assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc(L=31))) == 1
+    assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc(ld_rows=312))) == 1
+    for opt in ("NO_COMPACT_ROWS", "NO_SLABS", "NO_SCATTER_SORT"):
+        _lib.set_option(opt, 1)
+        try:
+            assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc())) == 0, opt
+        finally:
+            _lib.set_option(opt, 0)
+        assert lib.nr_mhsa_compact_rows(C.byref(_mind_title_desc())) == 1, opt
