@@ -94,6 +94,9 @@ int nr_cast_pad_batch(const nr_cast_job* jobs, int n, int dtype, nr_stream_t str
  * (accumulate != 0: dw += ..., else dw = ...).                                               */
 int nr_pack_conv_w(const float* w, int N, int D, void* dst, int Dp, int dtype, nr_stream_t stream);
 int nr_unpack_conv_dw(const float* dw_pack, int N, int D, int Dp, float* dw, int accumulate, nr_stream_t stream);
+/* The same weight as the [D, ld] operand of the table-gradient GEMM (nr_conv1d_k3_bwd_table): dst[d, j*N + n] = w[n, d, 2 - j],
+ * zero from column 3N to ld (ld >= 3N; bf16: a multiple of 32 so that the LDS-DMA GEMM runs whole k-steps).             */
+int nr_pack_conv_w_t(const float* w, int N, int D, void* dst, int ld, int dtype, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * K1  embedding row gather — nn.Embedding(padding_idx=0) lookup,
@@ -249,12 +252,26 @@ typedef struct {
                          (nr_additive_pool_fwd / _bwd with the same flags) never reads them -- and, on shapes whose backward
                          contracts live slabs only, does not store the x_rows of titles far from every needed one;
                          nr_conv1d_k3_bwd must then be given the same flags and bwd_ws                                         */
+  int table_rows;     /* nr_conv1d_k3_bwd_table / nr_conv_table_workspace_bytes only: rows V of the table; else 0               */
 } nr_conv_desc;
 size_t nr_conv_workspace_bytes(const nr_conv_desc* d);
 int nr_conv1d_k3_fwd(const nr_conv_desc* d, void* y, nr_stream_t stream);
 /* dw_pack [N, 3*Dp] fp32 accumulated (nr_unpack_conv_dw -> [N, D, 3]); db [N] accumulated.
- * The title-embedding table is frozen on this path (src/demo.sh:12): no dtable.             */
+ * The gradient of a trainable title-embedding table is a call of its own: nr_conv1d_k3_bwd_table.   */
 int nr_conv1d_k3_bwd(const nr_conv_desc* d, const void* dy, float* dw_pack, float* db, nr_stream_t stream);
+/* Gradient of a trainable title-embedding table (freeze_embedding=False, the default of src/parameters.py:47; src/model/NAML.py:104-107):
+ *   dx[s,t,:] = sum_j W_j^T dy[s,t-j+1,:] ;  dtable[id_s, t*D + c] += keep(s,t,c) * scale * dx[s,t,c]   for id_s != 0.
+ * dtable: fp32 [table_rows, T*D] contiguous, ACCUMULATED.  dy [n*T, N] dtype; w_t_pack [D, ldwt] dtype (nr_pack_conv_w_t).
+ * Reads of the descriptor: n, T, D, N, dtype, ids, ids_stride, p_in, seed_in (the forward's), seq_nz (optional), table_rows.
+ * Titles with id 0 or outside [0, table_rows), and titles whose seq_nz flag is 0, are not computed.  All occurrences of one news id
+ * are summed by one workgroup in batch order and added with plain stores: no atomics, the result is bit-identical from run to
+ * run in every mode (nr_set_deterministic needs no scratch for dtable here).
+ * Size: dtable is addressed with 64-bit offsets, so tables of 2^31 elements and more (V*T*D*4 bytes > 4 GiB from V ~ 120 000 at
+ * T*D = 9 000) are handled; refused on the host before any launch are table_rows * T >= 2^31 and n*T*max(D, N) >= 2^32.
+ * ws: nr_conv_table_workspace_bytes(d) bytes of scratch, 16-byte aligned (checked before any launch).             */
+size_t nr_conv_table_workspace_bytes(const nr_conv_desc* d);
+int nr_conv1d_k3_bwd_table(const nr_conv_desc* d, const void* dy, const void* w_t_pack, int ldwt, float* dtable, void* ws, size_t ws_bytes,
+                           nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * K5  additive attention pooling — AttentionPooling.forward, src/model/model_utils.py:13-31

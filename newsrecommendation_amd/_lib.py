@@ -38,7 +38,7 @@ class ConvDesc(C.Structure):
                 ("table", C.c_void_p), ("ids", C.c_void_p), ("ids_stride", C.c_int), ("p_in", C.c_float),
                 ("seed_in", C.c_uint32), ("w_pack", C.c_void_p), ("bias", C.c_void_p), ("x_rows", C.c_void_p),
                 ("ld_rows", C.c_int), ("bwd_ws", C.c_void_p), ("bwd_ws_bytes", C.c_size_t), ("seq_nz", C.c_void_p),
-                ("seq_needed", C.c_void_p)]
+                ("seq_needed", C.c_void_p), ("table_rows", C.c_int)]
 
 
 CAST_BATCH_MAX = 16          # NR_CAST_BATCH_MAX of include/nrhip.h
@@ -70,7 +70,7 @@ class LinearDesc(C.Structure):
 
 _vp, _i, _f, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint32
 # name -> argtypes ; every entry returns int unless listed in RESTYPES.  Must list exactly the symbols of include/nrhip.h.
-RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": C.c_size_t, "nr_mhsa_workspace_bytes": C.c_size_t, "nr_conv_workspace_bytes": C.c_size_t, "nr_pool_workspace_bytes": C.c_size_t,
+RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": C.c_size_t, "nr_mhsa_workspace_bytes": C.c_size_t, "nr_conv_workspace_bytes": C.c_size_t, "nr_conv_table_workspace_bytes": C.c_size_t, "nr_pool_workspace_bytes": C.c_size_t,
             "nr_linear_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
@@ -81,6 +81,7 @@ SIGNATURES = {
     "nr_get_option": [C.c_char_p],
     "nr_mhsa_workspace_bytes": [C.POINTER(MhsaDesc)],
     "nr_conv_workspace_bytes": [C.POINTER(ConvDesc)],
+    "nr_conv_table_workspace_bytes": [C.POINTER(ConvDesc)],
     "nr_pool_workspace_bytes": [C.POINTER(PoolDesc)],
     "nr_pool_contracts_slabs": [C.POINTER(PoolDesc)],
     "nr_pool_seq_flags": [C.POINTER(PoolDesc), _vp],
@@ -99,6 +100,7 @@ SIGNATURES = {
     "nr_cast_pad_batch": [_vp, _i, _i, _vp],
     "nr_pack_conv_w": [_vp, _i, _i, _vp, _i, _i, _vp],
     "nr_unpack_conv_dw": [_vp, _i, _i, _i, _vp, _i, _vp],
+    "nr_pack_conv_w_t": [_vp, _i, _i, _vp, _i, _i, _vp],
     "nr_embed_gather_fwd": [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp],
     "nr_embed_gather_bwd": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
     "nr_gather_cast_fwd": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp],
@@ -108,6 +110,7 @@ SIGNATURES = {
     "nr_mhsa_bwd": [C.POINTER(MhsaDesc), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "nr_conv1d_k3_fwd": [C.POINTER(ConvDesc), _vp, _vp],
     "nr_conv1d_k3_bwd": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp],
+    "nr_conv1d_k3_bwd_table": [C.POINTER(ConvDesc), _vp, _vp, _i, _vp, _vp, C.c_size_t, _vp],
     "nr_additive_pool_fwd": [C.POINTER(PoolDesc), _vp, _vp, _vp, _i, _vp],
     "nr_additive_pool_bwd": [C.POINTER(PoolDesc), _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "nr_pad_blend_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

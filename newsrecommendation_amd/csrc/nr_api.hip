@@ -286,6 +286,29 @@ static MhsaWs mhsa_ws_of(const nr_mhsa_desc* d) {
 }
 // bwd_ws of the convolution (int32): n title flags | 4 counters | M/32 slab ids | pad
 static size_t conv_ws_elems(int n, int T) { return (size_t)n + 4 + ((size_t)n * T) / 32 + 12; }
+// ws of nr_conv1d_k3_bwd_table.  int32: 8 header | live_s, live_id, sort_s, sort_id, sort_k, ord_s, ord_slot [n] each | hist [V + 8] |
+// ident [n*T] ; then, 16-byte aligned: dy staged with a zero row between titles [n*(T+1)+1, N] dtype | dx [n*T, Dc] dtype
+struct ConvTabWs {
+  size_t live_s, live_id, sort_s, sort_id, sort_k, ord_s, ord_slot, hist, ident;   // int32 offsets
+  size_t dyg, dx, total;                                                           // byte offsets / size
+  int Dc;
+};
+static ConvTabWs conv_tab_layout(int n, int T, int D, int N, int V, int dtype) {
+  ConvTabWs w;
+  const size_t n_ = (size_t)(n > 0 ? n : 0), T_ = (size_t)(T > 0 ? T : 0), es = (size_t)nr_elt_size(dtype);
+  size_t o = 8;
+  w.live_s = o; o += n_; w.live_id = o; o += n_; w.sort_s = o; o += n_; w.sort_id = o; o += n_; w.sort_k = o; o += n_;
+  w.ord_s = o; o += n_; w.ord_slot = o; o += n_;
+  w.hist = o; o += (size_t)(V > 0 ? V : 0) + 8;
+  o = (o + 3) / 4 * 4;
+  w.ident = o; o += n_ * T_;
+  o = (o + 3) / 4 * 4;
+  w.Dc = round_up(D > 0 ? D : 1, nr_chunk(dtype));
+  w.dyg = o * sizeof(int32_t);
+  w.dx = w.dyg + (((n_ * (T_ + 1) + 1) * (size_t)(N > 0 ? N : 0) * es + 15) / 16) * 16;
+  w.total = w.dx + ((n_ * T_ * (size_t)w.Dc * es + 15) / 16) * 16;
+  return w;
+}
 int nr_pool_partial_rows(int n);
 // `partial` of the pooling backward (fp32): nr_pool_partial_rows(n) rows of (q+1) | int32 scratch: n flags, 4 counters, M/32 slabs
 static size_t pool_ws_used(int n, int q) { return ((size_t)nr_pool_partial_rows(n) * (q + 1) + 3) / 4 * 4; }
@@ -493,6 +516,10 @@ size_t nr_mhsa_workspace_bytes(const nr_mhsa_desc* d) {
 }
 size_t nr_conv_workspace_bytes(const nr_conv_desc* d) {
   return (d == nullptr || d->n < 0 || d->T < 1) ? 0 : conv_ws_elems(d->n, d->T) * sizeof(int32_t);
+}
+size_t nr_conv_table_workspace_bytes(const nr_conv_desc* d) {
+  if (d == nullptr || d->n < 0 || d->T < 1 || d->D < 1 || d->N < 1 || d->table_rows < 1 || !dtype_ok(d->dtype)) return 0;
+  return conv_tab_layout(d->n, d->T, d->D, d->N, d->table_rows, d->dtype).total;
 }
 int nr_pool_contracts_slabs(const nr_pool_desc* d) {
   return (d != nullptr && d->n > 0 && d->L >= 1 && d->q >= 1 && dtype_ok(d->dtype) && pool_has_flags(d)) ? 1 : 0;
@@ -947,6 +974,55 @@ int nr_conv1d_k3_bwd(const nr_conv_desc* d, const void* dy, float* dw_pack, floa
   }
   return nr_launch_gemm_tn(d->dtype, dy, d->N, A, dw_pack, 3 * d->Dp, db, d->n * d->T, d->N, 3 * d->Dp, d->N, 3 * d->Dp,
                            (hipStream_t)stream);
+}
+
+// Table gradient of the title convolution: dx over the live titles (one NT GEMM on dy staged with a zero row between titles),
+// then the owner-computes scatter into dtable [V, T*D] (nr_convtab.hip).  Uses of the descriptor: n, T, D, N, dtype, ids,
+// ids_stride, p_in / seed_in, seq_nz, table_rows.
+int nr_conv1d_k3_bwd_table(const nr_conv_desc* d, const void* dy, const void* w_t_pack, int ldwt, float* dtable, void* ws, size_t ws_bytes,
+                           nr_stream_t stream) {
+  NR_CHECK_ARG(d != nullptr, "conv1d_bwd_table: null descriptor");
+  NR_CHECK_ARG(dtype_ok(d->dtype), "conv1d_bwd_table: bad dtype %d", d->dtype);
+  const int ch = nr_chunk(d->dtype);
+  NR_CHECK_ARG(d->n >= 0 && d->T >= 1 && d->D >= 1 && d->N >= 1 && d->N % ch == 0, "conv1d_bwd_table: bad shape n=%d T=%d D=%d N=%d", d->n, d->T,
+               d->D, d->N);
+  NR_CHECK_ARG(d->table_rows >= 1, "conv1d_bwd_table: table_rows=%d (rows V of the table) is required", d->table_rows);
+  // dtable offsets are 64-bit (V*T*D floats pass 4 GiB from V ~ 120 000 at T*D = 9 000); the table's [V*T, D] row numbers and the
+  // dropout element index (s*T + t)*D + c are 32-bit
+  NR_CHECK_ARG((uint64_t)d->table_rows * (uint64_t)d->T < 0x7fffffffull, "conv1d_bwd_table: table_rows * T = %llu does not fit 31 bits",
+               (unsigned long long)d->table_rows * (unsigned long long)d->T);
+  NR_CHECK_ARG((uint64_t)d->n * d->T * (uint64_t)(d->D > d->N ? d->D : d->N) < 0xffffffffull,
+               "conv1d_bwd_table: problem too large for 32-bit element counters");
+  NR_CHECK_ARG(d->p_in >= 0.f && d->p_in < 1.f, "conv1d_bwd_table: dropout p out of range");
+  if (d->n == 0) return NR_OK;
+  NR_CHECK_ARG(d->ids && d->ids_stride >= 1 && dy && w_t_pack && dtable && ws, "conv1d_bwd_table: null operand");
+  NR_CHECK_ARG(ldwt >= 3 * d->N && ldwt % ch == 0, "conv1d_bwd_table: w_t_pack is [D, ldwt >= 3N] (ldwt=%d, N=%d)", ldwt, d->N);
+  const ConvTabWs W = conv_tab_layout(d->n, d->T, d->D, d->N, d->table_rows, d->dtype);
+  NR_CHECK_ARG(ws_bytes >= W.total, "conv1d_bwd_table: ws holds %zu bytes, nr_conv_table_workspace_bytes() asks for %zu", ws_bytes, W.total);
+  NR_CHECK_ARG(aligned(16, dy, ws, w_t_pack) && aligned(4, dtable), "conv1d_bwd_table: dy / w_t_pack / ws must be 16-byte aligned");
+  NR_DEVICE_GUARD(stream, dtable);
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* wi = static_cast<int32_t*>(ws);
+  void* dyg = static_cast<char*>(ws) + W.dyg;
+  void* dx = static_cast<char*>(ws) + W.dx;
+  const int n = d->n, T = d->T, N = d->N, D = d->D, V = d->table_rows, K = 3 * N;
+  // bf16 shapes that reach the LDS-DMA GEMM (nr_launch_gemm_nt) multiply the live titles only, stored back to back (their count
+  // stays on the device); every other shape stages and multiplies all n titles and the scatter picks the live ones
+  const bool compact = d->dtype == NR_BF16 && K >= 192 && ldwt >= (K + 31) / 32 * 32;
+  int rc;
+  if ((rc = nr_launch_conv_table_live(d->ids, d->ids_stride, d->seq_nz, n, T, V, wi, wi + W.live_s, wi + W.live_id, s))) return rc;
+  if ((rc = nr_launch_conv_table_stage(d->dtype, dy, n, T, N, wi, wi + W.live_s, compact, dyg, compact ? wi + W.ident : nullptr, s))) return rc;
+  RowSrc A = dense_rows(dyg, N, K);
+  A.gap = T;
+  EpiArgs ep = store_epi(dx, W.Dc, d->dtype, nullptr, 0);
+  if (compact) { ep.row_count = wi + 1; ep.row_idx = wi + W.ident; }
+  if ((rc = nr_launch_gemm_nt(d->dtype, A, w_t_pack, ldwt, n * T, D, K, EPI_STORE, ep, s))) return rc;
+  if ((rc = nr_launch_sort_rows_by_id(wi, wi + W.live_s, wi + W.live_id, n, V, wi + W.hist, wi + W.sort_s, wi + W.sort_id, s, wi + W.sort_k)))
+    return rc;
+  if ((rc = nr_launch_conv_table_rank(wi, wi + W.sort_s, wi + W.sort_id, wi + W.sort_k, wi + W.hist, compact, n, wi + W.ord_s, wi + W.ord_slot, s)))
+    return rc;
+  return nr_launch_conv_table_scatter(d->dtype, dx, W.Dc, n, T, D, V, wi, wi + W.sort_id, wi + W.hist, wi + W.ord_s, wi + W.ord_slot,
+                                      nr_make_drop(d->p_in, d->seed_in), dtable, s);
 }
 
 // ---------------------------------------------------------------------------------------- additive pooling

@@ -123,3 +123,20 @@ int nr_launch_gather_live_rows(int dtype, const RowSrc& A, void* out, int ldo, i
                                const int32_t* ids, hipStream_t stream, int32_t* hist = nullptr, int V = 0);   // hist [V]: occurrences per id, counted on the way
 int nr_launch_gemm_tn(int dtype, const void* dC, int ldc, const RowSrc& A, float* dW, int ldw, float* db,
                       int M, int N, int K, int Nstore, int Kstore, hipStream_t stream);
+// ---- table gradient of the k = 3 convolution over gathered titles (nr_convtab.hip; driven by nr_conv1d_k3_bwd_table) ----
+// hdr int32 [8]: hdr[0] = live titles (id in [1, V) and seq_nz != 0), hdr[1] = hdr[0] * T; live_s / live_id [n]: their title
+// numbers (ascending) and news ids
+int nr_launch_conv_table_live(const int32_t* ids, int ids_stride, const int32_t* seq_nz, int n, int T, int V, int32_t* hdr, int32_t* live_s,
+                              int32_t* live_id, hipStream_t stream);
+// out [slots * (T + 1) + 1, N] dtype: dy of the staged titles with a zero row between titles (the layout of nr_launch_conv_rows).
+// compact: slot k = live title k; else slot s = title s (every title).  ident (optional) [slots * T]: identity row map
+int nr_launch_conv_table_stage(int dtype, const void* dy, int n, int T, int N, const int32_t* hdr, const int32_t* live_s, bool compact, void* out,
+                               int32_t* ident, hipStream_t stream);
+// sort_* / cursor: what nr_launch_sort_rows_by_id left (cursor = its hist).  ord_s / ord_slot [n]: title number and dx slot of
+// every live title, grouped by news id, ascending batch order inside a group
+int nr_launch_conv_table_rank(const int32_t* hdr, const int32_t* sort_s, const int32_t* sort_id, const int32_t* sort_k, const int32_t* cursor,
+                              bool compact, int n, int32_t* ord_s, int32_t* ord_slot, hipStream_t stream);
+// dtable[id, t*D + c] += sum over the group of id, in that order, of keep((s*T + t)*D + c) * scale * dx[(slot*T + t)*ldx + c]
+int nr_launch_conv_table_scatter(int dx_dtype, const void* dx, int ldx, int n, int T, int D, int V, const int32_t* hdr, const int32_t* sort_id,
+                                 const int32_t* cursor, const int32_t* ord_s, const int32_t* ord_slot, DropCfg drop, float* dtable,
+                                 hipStream_t stream);

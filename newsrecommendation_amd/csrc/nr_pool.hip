@@ -551,6 +551,16 @@ __global__ void pack_conv_w_kernel(const float* __restrict__ w, int N, int D, T*
   }
 }
 
+// operand of the table-gradient GEMM: dst[d, j*N + n] = w[n, d, 2 - j] (dx[t] = sum_j W_(2-j)^T dy[t + j - 1]), zero beyond 3N
+template <typename T>
+__global__ void pack_conv_w_t_kernel(const float* __restrict__ w, int N, int D, T* __restrict__ dst, int ld) {
+  const size_t total = (size_t)D * ld;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int d = (int)(i / ld), r = (int)(i - (size_t)d * ld), j = r / N, n = r - j * N;
+    dst[i] = (T)(r < 3 * N ? w[((size_t)n * D + d) * 3 + (2 - j)] : 0.f);
+  }
+}
+
 __global__ void unpack_conv_dw_kernel(const float* __restrict__ dwp, int N, int D, int Dp, float* __restrict__ dw, int accumulate) {
   const size_t total = (size_t)N * D * 3;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -723,6 +733,19 @@ int nr_pack_conv_w(const float* w, int N, int D, void* dst, int Dp, int dtype, n
     hipLaunchKernelGGL(pack_conv_w_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, N, D, (bf16_t*)dst, Dp);
   else
     hipLaunchKernelGGL(pack_conv_w_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, N, D, (float*)dst, Dp);
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_pack_conv_w_t(const float* w, int N, int D, void* dst, int ld, int dtype, nr_stream_t stream) {
+  NR_CHECK_ARG(w && dst && N > 0 && D > 0 && ld >= 3 * N && (dtype == NR_F32 || dtype == NR_BF16), "pack_conv_w_t: bad arguments");
+  NR_DEVICE_GUARD(stream, dst);
+  const size_t total = (size_t)D * ld;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == NR_BF16)
+    hipLaunchKernelGGL(pack_conv_w_t_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, w, N, D, (bf16_t*)dst, ld);
+  else
+    hipLaunchKernelGGL(pack_conv_w_t_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, w, N, D, (float*)dst, ld);
   NR_CHECK_LAUNCH();
   return NR_OK;
 }

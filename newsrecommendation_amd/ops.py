@@ -813,7 +813,9 @@ class ConvFunction(Function):
     """K4 (+K1, K2): title-embedding row gather -> dropout -> Conv1d(k=3, pad=1), src/model/NAML.py:47-54."""
 
     @staticmethod
-    def forward(ctx, w, b, ids, cfg):
+    def forward(ctx, w, b, ids, cfg, table):
+        """table: the fp32 [V, T*D] master when it is trainable (an autograd input: its gradient is made by
+        nr_conv1d_k3_bwd_table), None for a frozen table -- the forward reads cfg["table_packed"] either way."""
         _need_gpu(w, ids)
         code, T, D = cfg["code"], cfg["T"], cfg["D"]
         table_p = cfg["table_packed"]                 # [V*T, Dp]
@@ -837,6 +839,9 @@ class ConvFunction(Function):
         ctx.ids = ids                                   # keeps the (possibly strided) id view alive
         ctx.x_rows = x_rows if any(ctx.needs_input_grad[:2]) else None
         ctx.targets = (grad_target(w), grad_target(b))
+        ctx.table_grad = table is not None and ctx.needs_input_grad[4]
+        if ctx.table_grad:
+            ctx.table_shape, ctx.table_target, ctx.w32 = tuple(table.shape), grad_target(table), wc
         ctx.save_for_backward(table_p, w_p, b_c)
         return y
 
@@ -863,24 +868,44 @@ class ConvFunction(Function):
         check(_lib.lib().nr_conv1d_k3_bwd(C.byref(d), ptr(dy), ptr(dwp), ptr(db), _stream()), "nr_conv1d_k3_bwd")
         dw = ctx.targets[0] if direct else torch.empty(N, D, 3, dtype=torch.float32, device=dev)
         check(_lib.lib().nr_unpack_conv_dw(ptr(dwp), N, D, Dp, ptr(dw), int(direct), _stream()), "nr_unpack_conv_dw")
+        dtable = None
+        if ctx.table_grad:
+            # trainable title table: dx over the live titles (one more GEMM of the forward's size) and the owner-computes
+            # scatter, added straight into the bucket's gradient view when there is one (2.3 GB at 65 000 news: no copy of it)
+            V = ctx.table_shape[0]
+            dtab = ctx.table_target if ctx.table_target is not None else torch.zeros(ctx.table_shape, dtype=torch.float32, device=dev)
+            ldwt = round_up(3 * N, 32 if code == NR_BF16 else chunk(code))
+            w_t = torch.empty(D, ldwt, dtype=torch_dtype(code), device=dev)
+            check(_lib.lib().nr_pack_conv_w_t(ptr(ctx.w32), N, D, ptr(w_t), ldwt, code, _stream()), "nr_pack_conv_w_t")
+            d.table_rows = V
+            tws = _ws(_lib.lib().nr_conv_table_workspace_bytes(C.byref(d)), dev)
+            if POISON_WORKSPACES:
+                tws.fill_(-1)                     # (int32 view: every byte 0xff, a NaN pattern in both operand types)
+            check(_lib.lib().nr_conv1d_k3_bwd_table(C.byref(d), ptr(dy), ptr(w_t), ldwt, ptr(dtab), ptr(tws), tws.numel() * 4, _stream()),
+                  "nr_conv1d_k3_bwd_table")
+            if ctx.table_target is None:
+                dtable = dtab
         if direct:
-            return None, None, None, None
-        return dw, db, None, None
+            return None, None, None, None, dtable
+        return dw, db, None, None, dtable
 
 
 def conv1d_k3_gather(table, w, b, ids, T: int, D: int, code: int, p_in=0.0, needed=None):
-    """ids: int32 view [n] (any stride) of news ids; table: fp32 [V, T*D] (frozen on this path).
+    """ids: int32 view [n] (any stride) of news ids; table: fp32 [V, T*D], frozen or trainable (a trainable one gets its
+    dense [V, T*D] gradient from nr_conv1d_k3_bwd_table; row 0, the padding_idx, gets none).
     needed: optional [n] int32 flags (needed_flags); output rows of unneeded titles may stay unwritten -- pool them with the
     same flags."""
-    if table.requires_grad:
-        raise RuntimeError("NAML title-embedding table must be frozen (freeze_embedding=True, as src/demo.sh:12): "
-                           "its [V, T*D] dense gradient is out of scope on this path")
     if CHECK_INDICES:
         check_ids(ids, table.shape[0], "news id")
     # model.NAML.TitleTable holds the packed operand itself (uploaded block by block); a plain fp32 parameter is packed once
     packed = table.packed(code) if hasattr(table, "packed") else table_cache.get(table, code, row_cols=D)
     cfg = dict(code=code, T=T, D=D, p_in=float(p_in), seed_in=draw_seed() if p_in > 0 else 0, table_packed=packed, needed=needed)
-    return ConvFunction.apply(w, b, ids, cfg)
+    if isinstance(table, torch.Tensor) and table.requires_grad and torch.is_grad_enabled():
+        if table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape[1:]) != (T * D,):
+            raise RuntimeError(f"conv1d_k3_gather: a trainable title table must be contiguous fp32 [V, {T * D}], got "
+                               f"{table.dtype} {tuple(table.shape)}")
+        return ConvFunction.apply(w, b, ids, cfg, table)
+    return ConvFunction.apply(w, b, ids, cfg, None)
 
 
 # ------------------------------------------------------------------------------------------ gather + Linear (category views)

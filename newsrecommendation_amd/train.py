@@ -131,6 +131,7 @@ def train(rank, args, news_index, news_combined, embedding_matrix, category_dict
         if world > 1:
             net = parallel.wrap_ddp(model, device)             # src/main.py:82
         optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, fused=on_gpu)      # src/main.py:76
+        trainable = [p for p in model.parameters() if p.requires_grad]
     else:
         raise ValueError(f"dp_mode must be 'flat' or 'ddp', got {mode!r}")
 
@@ -170,6 +171,12 @@ def train(rank, args, news_index, news_combined, embedding_matrix, category_dict
                 bucket.step()
             else:
                 optimizer.step()
+                if on_gpu:
+                    # torch's fused Adam rewrites the parameters without moving their version counters: the packed bf16
+                    # copy of a trainable table (ops.table_cache keys on the counter) would be served stale from step 2 on
+                    for p in trainable:
+                        ops.table_cache.invalidate(p)
+                    ops.bump_param_epoch()
             with torch.no_grad():                              # accumulated on the device: no host sync per step
                 loss_sum += bz_loss.detach()
                 acc_sum += acc(label, y_hat)
