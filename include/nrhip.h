@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, and with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -428,6 +428,43 @@ typedef struct {
 } nr_pack_job;
 int nr_adam_step_packed(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
                         int step, float grad_scale, int zero_grad, const nr_pack_job* jobs, int n_jobs, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * f4, row-deferred: the same Adam over a [rows, width] fp32 table inside the bucket (an embedding table whose gradient is
+ * zero outside the rows of the batch), touching only the rows named by `ids`.  Dense Adam also moves a row whose gradient is
+ * zero (its moments decay), but that motion depends only on the row's own p, m, v and the step number: row_step[r] counts the
+ * steps row r has had, and the missing ones are REPLAYED -- the dense kernel's arithmetic with a zero gradient and the
+ * scalars of that step, kept in `sched` -- before the row is read or stepped again.  The result is bit-identical to
+ * nr_adam_step_packed over the whole table at every step.
+ *   ids == NULL            every row (a flush: brings the whole table to `upto`, after which it is what dense Adam holds)
+ *   ids outside [1, rows)  skipped; row 0 is the padding_idx row: no gradient, zero moments, it never moves
+ *   upto                   rows are first brought to `upto` steps by zero-gradient replay
+ *   apply                  0: catch-up only (before a forward reads the rows).  1: then step upto + 1 with `grad` (scaled by
+ *                          grad_scale), and, with zero_grad != 0, the row's gradient is cleared.  The call derives that step's
+ *                          scalars from lr / beta1 / beta2 exactly as nr_adam_step_packed does and files them under
+ *                          sched[upto + 1] for later replays: sched (float2 per step, zero filled) needs upto + apply <
+ *                          sched_capacity and must see EVERY step once, also one without ids (n_ids = 0, ids non-NULL).
+ *   pack_dst               optional packed bf16 copy of the table, [rows * width / pack_cols, pack_ld], kept current for the
+ *                          rows written (as nr_pack_job)
+ *   ws                     nr_adam_rows_workspace_bytes(n_ids) bytes (a flush: n_ids = rows), 16-byte aligned
+ * eps == 0 is refused: dense Adam makes NaN of every never-touched row then.  Two launches, no host synchronisation.  */
+typedef struct {
+  float *param, *grad, *exp_avg, *exp_avg_sq;
+  int rows, width;
+  int32_t* row_step;
+  float* sched;
+  int sched_capacity;
+  const int32_t* ids;
+  int ids_stride, n_ids;
+  int upto, apply, zero_grad;
+  float lr, beta1, beta2, eps, grad_scale;
+  void* pack_dst;
+  int pack_cols, pack_ld;
+  void* ws;
+  size_t ws_bytes;
+} nr_adam_rows_desc;
+size_t nr_adam_rows_workspace_bytes(int n_ids);
+int nr_adam_rows(const nr_adam_rows_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Per-kernel timing (measurement only).  While enabled, every kernel launch inside the library is

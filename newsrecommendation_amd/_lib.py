@@ -56,6 +56,14 @@ class PackJob(C.Structure):
 ADAM_PACK_MAX = 4
 
 
+class AdamRowsDesc(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("rows", C.c_int),
+                ("width", C.c_int), ("row_step", C.c_void_p), ("sched", C.c_void_p), ("sched_capacity", C.c_int), ("ids", C.c_void_p),
+                ("ids_stride", C.c_int), ("n_ids", C.c_int), ("upto", C.c_int), ("apply", C.c_int), ("zero_grad", C.c_int),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float),
+                ("pack_dst", C.c_void_p), ("pack_cols", C.c_int), ("pack_ld", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -71,7 +79,7 @@ class LinearDesc(C.Structure):
 _vp, _i, _f, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint32
 # name -> argtypes ; every entry returns int unless listed in RESTYPES.  Must list exactly the symbols of include/nrhip.h.
 RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": C.c_size_t, "nr_mhsa_workspace_bytes": C.c_size_t, "nr_conv_workspace_bytes": C.c_size_t, "nr_conv_table_workspace_bytes": C.c_size_t, "nr_pool_workspace_bytes": C.c_size_t,
-            "nr_linear_workspace_bytes": C.c_size_t}
+            "nr_linear_workspace_bytes": C.c_size_t, "nr_adam_rows_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
     "nr_last_error": [C.c_char_p, C.c_size_t],
@@ -94,6 +102,8 @@ SIGNATURES = {
     "nr_eval_metrics": [_vp, _vp, _vp, _i, _i, _vp, C.c_size_t, _vp, _vp],
     "nr_adam_step": [_vp, _vp, _vp, _vp, C.c_size_t, _f, _f, _f, _f, _i, _f, _i, _vp],
     "nr_adam_step_packed": [_vp, _vp, _vp, _vp, C.c_size_t, _f, _f, _f, _f, _i, _f, _i, _vp, _i, _vp],
+    "nr_adam_rows_workspace_bytes": [_i],
+    "nr_adam_rows": [C.POINTER(AdamRowsDesc), _vp],
     "nr_check_ids": [_vp, _i, _i, _i, _vp, _vp],
     "nr_check_labels": [_vp, _i, _i, _vp, _vp],
     "nr_cast_pad": [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp],
@@ -167,7 +177,7 @@ def lib():
                     fn = getattr(L, name)          # AttributeError if the .so lacks a declared symbol
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
-                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob)
+                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

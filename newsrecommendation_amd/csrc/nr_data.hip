@@ -7,6 +7,7 @@
 //                        all-reduce averaging factor and the next step's zero_grad folded in
 // All of it is HBM-bound integer / elementwise work: coalesced 16-byte accesses, no MFMA.
 #include "nr_common.h"
+#include "nr_adam.h"
 
 namespace {
 
@@ -147,19 +148,7 @@ __global__ __launch_bounds__(1024) void metrics_reduce_kernel(const double* __re
 }
 
 // ------------------------------------------------------------------------------------------ Adam over a flat bucket
-struct AdamCfg {
-  float beta1, beta2, eps, step_size, bc2_sqrt, grad_scale;
-  int zero_grad;
-};
-
-__device__ __forceinline__ void adam1(float& p, float& g, float& m, float& v, const AdamCfg& c) {
-  const float gr = g * c.grad_scale;
-  m = fmaf(1.f - c.beta1, gr - m, m);                             // exp_avg.lerp_(grad, 1 - beta1)
-  v = fmaf(c.beta2, v, (1.f - c.beta2) * gr * gr);                // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;              // sqrt(v) / sqrt(1 - beta2^t) + eps
-  p -= c.step_size * (m / denom);                                 // step_size = lr / (1 - beta1^t)
-  if (c.zero_grad) g = 0.f;
-}
+// AdamCfg, adam1 and the per-step scalars: nr_adam.h (shared with the row-deferred kernels of nr_adamrows.hip)
 
 // Packed (bf16, row-padded) copies of parameter matrices that live in the bucket: written in the same pass as the update
 // itself, bit-identical to what nr_cast_pad makes of the new values (the separate re-pack of a 30 000 x 300 word table was
@@ -306,9 +295,7 @@ int nr_adam_step_packed(float* param, float* grad, float* exp_avg, float* exp_av
   NR_DEVICE_GUARD(stream, param);
   AdamCfg c;
   c.beta1 = beta1; c.beta2 = beta2; c.eps = eps; c.grad_scale = grad_scale; c.zero_grad = zero_grad;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  c.step_size = (float)((double)lr / bc1);
-  c.bc2_sqrt = (float)sqrt(bc2);
+  nr_adam_bias(lr, beta1, beta2, step, &c.step_size, &c.bc2_sqrt);
   const size_t n4 = n / 4 + 1;
   const size_t blocks = (n4 + 255) / 256;
   NrProfScope ps((hipStream_t)stream, "adam_step[n=%zu]", n);

@@ -142,6 +142,9 @@ class NewsEncoder(nn.Module):
         p = self.drop_rate if self.training else 0.0
         needed = ops.needed_flags(needed)
         table = self.title_embeddings if isinstance(self.title_embeddings, TitleTable) else self.title_embeddings.weight
+        sync = getattr(table, "_nr_row_sync", None)       # parallel.FlatBucket(table_adam="deferred"): rows are stepped lazily
+        if sync is not None:
+            sync(x[:, 0])
         ctx = ops.conv1d_k3_gather(table, self.cnn.weight, self.cnn.bias, x[:, 0],
                                    self.num_words_title, self.word_embedding_dim, code, p_in=p, needed=needed)
         all_vecs = [self.attn(ctx, mask, needed=needed)]

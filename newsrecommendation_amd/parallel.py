@@ -83,11 +83,27 @@ class FlatBucket:
 
     Layout: the three projections of every MultiHeadSelfAttention are adjacent (weights [3N, d_model], then biases [3N])
     so the QKV GEMMs read / write them without a concatenation; every other parameter starts on a 256-byte boundary.
-    Frozen parameters stay where they are."""
+    Frozen parameters stay where they are.
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, group=None, broadcast=True):
+    table_adam="deferred" (one rank): the bucket's large last parameter -- NAML's trainable [V, T*D] title table, 99.9 % of the
+    bucket -- is stepped row by row instead of being streamed whole at every step (nr_adam_rows, include/nrhip.h).  A row that
+    is not in the batch is left behind; the zero-gradient steps it missed are replayed, with the dense kernel's arithmetic and
+    that step's scalars, before the row is next read -- so whoever reads rows of the table calls `table._nr_row_sync(ids)`
+    first (model.NAML.NewsEncoder.forward does), and whoever reads it as a whole calls `flush()`.  Parameters, moments and the
+    packed bf16 copy are then bit-identical to what table_adam="dense" holds."""
+
+    TABLE_ADAM = ("dense", "deferred")
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, group=None, broadcast=True, table_adam="dense"):
         from .model.model_utils import MultiHeadSelfAttention
+        if table_adam not in self.TABLE_ADAM:
+            raise ValueError(f"FlatBucket: table_adam must be one of {self.TABLE_ADAM}, got {table_adam!r}")
+        self.table_adam = table_adam
         self.group, self.world = group, world_size(group)
+        if table_adam == "deferred" and self.world > 1:
+            raise NotImplementedError("FlatBucket: table_adam='deferred' runs on one rank only: with several ranks a row must be stepped "
+                                      "on every rank that any rank touched (the union of the ranks' ids), which is not built; use "
+                                      "table_adam='dense' for data-parallel runs")
         self.lr, self.betas, self.eps, self.t = float(lr), (float(betas[0]), float(betas[1])), float(eps), 0
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
@@ -112,6 +128,13 @@ class FlatBucket:
             rest = [p for p in rest if p is not big] + [big]
         else:
             big = None
+        if table_adam == "deferred":
+            if big is None or big.dim() != 2 or big.shape[1] % 4:
+                raise ValueError("FlatBucket: table_adam='deferred' needs a trainable 2-D embedding table of at least 2^20 elements (row "
+                                 "width a multiple of 4) as the bucket's largest parameter; this model has none")
+            if self.eps <= 0.0:
+                raise ValueError("FlatBucket: table_adam='deferred' needs eps > 0 (with eps == 0 dense Adam turns every row that never "
+                                 "had a gradient into NaN: there is nothing to reproduce)")
         segments += [[p] for p in rest]
         order, offs, seg_off, off = [], [], [], 0
         for seg in segments:
@@ -158,6 +181,22 @@ class FlatBucket:
                 big._nr_grad_ready = self._early_allreduce   # ops.MHSAFunction.backward calls it once the table gradient is complete
         if broadcast and self.world > 1:             # DDP construction semantics (src/main.py:82): rank 0's parameters win
             dist.broadcast(self.param, src=0, group=group)
+        self._table = None
+        if table_adam == "deferred":
+            # The table is the bucket's LAST region: the dense kernel runs over what lies in front of it, the row kernels
+            # (nr_adam_rows) over the rows a step read.  row_step[r] = Adam steps row r has had; sched[t] = the two scalars of
+            # step t, filed by the call that does step t and read by the replays of rows that were not in its batch.
+            self._table = big
+            self._table_off = offs[[id(q) for q in order].index(id(big))]
+            self._row_step = torch.zeros(big.shape[0], dtype=torch.int32, device=dev)
+            self._sched = torch.zeros(64, 2, dtype=torch.float32, device=dev)
+            self._no_ids = torch.zeros(1, dtype=torch.int32, device=dev)       # (a step without a batch still files its scalars)
+            self._step_ids = []
+            big._nr_row_sync = self._sync_rows       # model.NAML.NewsEncoder.forward calls it before anything reads the table
+            # state_dict() of the module that owns the table (hence of every module above it) exposes the table as a whole
+            for mod in model.modules():
+                if any(q is big for q in mod._parameters.values()):
+                    mod.register_state_dict_pre_hook(lambda module, prefix, keep_vars: self.flush())
         self._params_changed()
 
     def _params_changed(self, repacked=()):
@@ -204,6 +243,8 @@ class FlatBucket:
             self._early_work.wait()
             self._early_work = None
         self.grad.zero_()
+        if self._table is not None:
+            self._step_ids = []
 
     def _early_allreduce(self):
         """Called from the backward pass right after the table-gradient kernel was enqueued (one backward per step): its
@@ -235,13 +276,79 @@ class FlatBucket:
         from . import _lib
         self.t += 1
         jobs, repacked = self._pack_jobs()
+        n = self.numel
+        if self._table is not None:
+            # the dense kernel stops in front of the table; the table's packed copy is kept current row by row (_rows)
+            n = self._table_off
+            jobs = [j for j in jobs if j.first + j.count <= n]
+            repacked = repacked - {id(self._table)}
         arr = (_lib.PackJob * len(jobs))(*jobs) if jobs else None
         _lib.check(_lib.lib().nr_adam_step_packed(self.param.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                                  self.exp_avg_sq.data_ptr(), self.numel, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                  self.exp_avg_sq.data_ptr(), n, self.lr, self.betas[0], self.betas[1], self.eps,
                                                   self.t, 1.0 / self.world, int(zero_grad), arr, len(jobs),
                                                   torch.cuda.current_stream().cuda_stream),
                    "nr_adam_step_packed")
+        if self._table is not None:
+            ids, self._step_ids = self._step_ids or [self._no_ids], []
+            for v in ids:
+                # every call after the first finds the step's scalars filed and the rows it shares with an earlier one claimed
+                if self._rows(v, self.t - 1, apply=True, zero_grad=zero_grad):
+                    repacked = repacked | {id(self._table)}
         self._params_changed(repacked)
+
+    # -- row-deferred Adam over the table (table_adam="deferred")
+    def _rows(self, ids, upto, apply, zero_grad=True):
+        """nr_adam_rows over the table region: rows of `ids` (None: every row) are brought to `upto` steps by zero-gradient
+        replay, then (apply) stepped once more with their gradient.  Returns True when the table's packed bf16 copy was kept
+        current by the kernel (or there is none), False when a copy exists that the kernel cannot write: it was dropped."""
+        from . import _lib, ops
+        tab, o = self._table, self._table_off
+        V, W = tab.shape
+        if upto + 2 > self._sched.shape[0]:                     # grows by doubling; the copy is ordered on the stream like the kernels
+            grown = torch.zeros(max(2 * self._sched.shape[0], upto + 2), 2, dtype=torch.float32, device=self._sched.device)
+            grown[: self._sched.shape[0]].copy_(self._sched)
+            self._sched = grown
+        d = _lib.AdamRowsDesc(param=self.param.data_ptr() + 4 * o, grad=self.grad.data_ptr() + 4 * o, exp_avg=self.exp_avg.data_ptr() + 4 * o,
+                              exp_avg_sq=self.exp_avg_sq.data_ptr() + 4 * o, rows=V, width=W, row_step=self._row_step.data_ptr(),
+                              sched=self._sched.data_ptr(), sched_capacity=self._sched.shape[0], upto=int(upto), apply=int(apply),
+                              zero_grad=int(zero_grad), lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                              grad_scale=1.0 / self.world)
+        if ids is not None:
+            if ids.dtype != torch.int32 or ids.dim() != 1 or ids.device != self.param.device:
+                raise ValueError("FlatBucket: row ids must be a 1-D int32 tensor on the bucket's device")
+            d.ids, d.ids_stride, d.n_ids = ids.data_ptr(), (ids.stride(0) if ids.numel() > 1 else 1), ids.numel()
+        kept = True
+        ents = ops.table_cache.current(tab)
+        if ents:
+            code, cols, packed = ents[0]
+            ok = (len(ents) == 1 and code == _lib.NR_BF16 and cols % 4 == 0 and W % cols == 0 and packed.dtype == torch.bfloat16
+                  and packed.is_contiguous() and packed.dim() == 2 and packed.shape[0] == V * (W // cols) and packed.shape[1] >= cols
+                  and packed.shape[1] % 4 == 0)
+            if ok:
+                d.pack_dst, d.pack_cols, d.pack_ld = packed.data_ptr(), cols, packed.shape[1]
+            else:
+                ops.table_cache.invalidate(tab)
+                kept = False
+        n = V if ids is None else ids.numel()
+        ws = ops._ws(_lib.lib().nr_adam_rows_workspace_bytes(n), self.param.device)
+        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        _lib.check(_lib.lib().nr_adam_rows(d, torch.cuda.current_stream().cuda_stream), "nr_adam_rows")
+        return kept
+
+    def _sync_rows(self, ids):
+        """Before a forward reads rows `ids` of the table: replay the steps they are behind.  Under autograd the ids are kept:
+        these are the rows the coming step() gives a gradient (or, for a masked slot, the zero gradient dense Adam would see)."""
+        if self.t > 0:
+            self._rows(ids, self.t, apply=False)
+        if torch.is_grad_enabled():
+            self._step_ids.append(ids)
+
+    def flush(self):
+        """Bring every row of a deferred table to step `t`: afterwards the four buffers hold what dense Adam holds.  Called by
+        state_dict(), by the model's state_dict() (a pre-hook), by train.train before a checkpoint and before it returns the model, and by anything else that reads
+        the table as a whole.  A no-op for table_adam='dense'."""
+        if self._table is not None and self.t > 0:
+            self._rows(None, self.t, apply=False)
 
     def step(self):
         self.allreduce()
@@ -249,6 +356,7 @@ class FlatBucket:
 
     # -- checkpoint interop: torch.optim.Adam's state_dict layout (per-parameter exp_avg / exp_avg_sq / step)
     def state_dict(self):
+        self.flush()
         names = {id(p): n for n, p in self._model.named_parameters()}
         st = {}
         for p, (pv, gv) in zip(self.params, self.views):
@@ -257,3 +365,23 @@ class FlatBucket:
             st[names[id(p)]] = {"step": self.t, "exp_avg": self.exp_avg[o:o + p.numel()].view_as(p).clone(),
                                 "exp_avg_sq": self.exp_avg_sq[o:o + p.numel()].view_as(p).clone()}
         return {"state": st, "lr": self.lr, "betas": self.betas, "eps": self.eps}
+
+    def load_state_dict(self, sd):
+        """The inverse of state_dict() (moments and step count; the parameters come with the model's own state_dict).  The
+        layout does not depend on table_adam: a state saved by a dense bucket loads into a deferred one and back."""
+        names = {id(p): n for n, p in self._model.named_parameters()}
+        steps = set()
+        with torch.no_grad():
+            for p, (pv, gv) in zip(self.params, self.views):
+                st = sd["state"][names[id(p)]]
+                o = (pv.data_ptr() - self.param.data_ptr()) // 4
+                self.exp_avg[o:o + p.numel()].view_as(p).copy_(st["exp_avg"])
+                self.exp_avg_sq[o:o + p.numel()].view_as(p).copy_(st["exp_avg_sq"])
+                steps.add(int(st["step"]))
+        if len(steps) != 1:
+            raise ValueError(f"FlatBucket.load_state_dict: one step count for the whole bucket expected, got {sorted(steps)}")
+        self.t = steps.pop()
+        self.lr, self.betas, self.eps = float(sd["lr"]), (float(sd["betas"][0]), float(sd["betas"][1])), float(sd["eps"])
+        if self._table is not None:
+            self._row_step.fill_(self.t)                 # a saved state is a flushed one: every row has had all t steps
+            self._step_ids = []

@@ -11,6 +11,8 @@ gradient all-reduce-mean, Adam, logging -- with the callers either side of the e
           `"host"`: the reference's `DatasetTrain` + `DataLoader` (src/main.py:89-90), kept for comparison and for CPU runs.
   update  `args.dp_mode = "flat"` (default on the GPU): `parallel.FlatBucket` -- one gradient all-reduce, one fused
           HIP Adam kernel; `"ddp"`: `DistributedDataParallel` + `torch.optim.Adam` as src/main.py:76,82.
+          `args.table_adam = "dense"` (default) or `"deferred"` (flat bucket, one rank, NAML): the trainable title table is
+          stepped row by row, bit-identical to the dense update (`parallel.FlatBucket`).
   eval    the [N+1, news_dim] news-vector table stays on the device (encode optionally sharded over the ranks +
           all_gather), history vectors are gathered there, scores and the per-impression AUC / MRR / nDCG are computed
           there (`ops.score_eval`, `ops.eval_metrics`); five numbers per rank leave the device and are SUM-reduced to
@@ -113,6 +115,16 @@ def train(rank, args, news_index, news_combined, embedding_matrix, category_dict
     on_gpu = device.type == "cuda"
     if on_gpu:
         torch.cuda.set_device(device)
+    mode = getattr(args, "dp_mode", None) or ("flat" if on_gpu else "ddp")
+    table_adam = getattr(args, "table_adam", None) or "dense"
+    if table_adam not in parallel.FlatBucket.TABLE_ADAM:
+        raise ValueError(f"table_adam must be 'dense' or 'deferred', got {table_adam!r}")
+    if table_adam == "deferred" and mode != "flat":
+        raise ValueError("table_adam='deferred' is a mode of the flat bucket (dp_mode='flat'): with dp_mode='ddp' torch.optim.Adam "
+                         "owns the optimizer state")
+    if table_adam == "deferred" and args.model != "NAML":
+        raise ValueError("table_adam='deferred' steps NAML's title table row by row; the encoder of " + str(args.model) +
+                         " does not announce the rows it reads")
     world = 1
     if is_distributed:
         _, world = parallel.init_distributed(rank, getattr(args, "nGPU", None), device=device)       # src/main.py:31
@@ -123,10 +135,10 @@ def train(rank, args, news_index, news_combined, embedding_matrix, category_dict
     if getattr(args, "deterministic", False) and on_gpu:       # bit-reproducible gradients (fixed-point integer atomics)
         # (only trainable outputs are ever registered with the fixed-point scratch: a frozen 575 M-value title table is not)
         ops.set_deterministic(True, elements=sum(p.numel() for p in model.parameters() if p.requires_grad) + (1 << 20), device=device)
-    mode = getattr(args, "dp_mode", None) or ("flat" if on_gpu else "ddp")
     net, bucket, optimizer = model, None, None
     if mode == "flat":
-        bucket = parallel.FlatBucket(model, lr=args.lr)        # rank-0 broadcast + one all-reduce + fused Adam per step
+        bucket = parallel.FlatBucket(model, lr=args.lr, table_adam=table_adam)        # rank-0 broadcast + one all-reduce + fused Adam per step
+        model._nr_bucket = bucket                              # (a plain attribute: callers that want the optimizer state find it here)
     elif mode == "ddp":
         if world > 1:
             net = parallel.wrap_ddp(model, device)             # src/main.py:82
@@ -187,11 +199,15 @@ def train(rank, args, news_index, news_combined, embedding_matrix, category_dict
                     ep, rank, cnt * args.batch_size, float(loss_sum) / (cnt + 1), float(acc_sum) / (cnt + 1)))
             if max_steps is not None and step >= max_steps:
                 break
+        if bucket is not None:
+            bucket.flush()                                     # a row-deferred table: every row brought to this step before it is saved
         if rank == 0 and getattr(args, "model_dir", None):
             os.makedirs(args.model_dir, exist_ok=True)
             torch.save(checkpoint_dict(net, category_dict, subcategory_dict), os.path.join(args.model_dir, f"epoch-{ep + 1}.pt"))
         if max_steps is not None and step >= max_steps:
             break
+    if bucket is not None:
+        bucket.flush()
     return model, (torch.stack(losses).float().cpu() if losses else torch.zeros(0))
 
 
