@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -369,6 +369,47 @@ int nr_score_ce_bwd(const float* cand, int ld_cand, const float* user, const int
  * score[i] = <news_vecs[cand_ids[i]], user[imp_of[i]]>, i in [0, n_cand).                     */
 int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, const int32_t* imp_of,
                   const float* user, int ld_user, float* score, int n_cand, int N, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K9  full-corpus top-k recommendation.  The reference only ever scores the candidate lists a behaviors.tsv supplies
+ * (src/main.py:253 `np.dot(news_vec, user_vec)` over the `news_scoring[candidate]` rows of src/dataset.py:64-74); this call
+ * generalises that dot product to EVERY news of the table and keeps, per user, the k best:
+ *   score[u, v] = <news_vecs[v], user[u]>, fp32 operands, fp32 accumulation (v_mfma_f32_16x16x4_f32), v in [1, V)
+ *   out_ids[u, :], out_scores[u, :] = the k best eligible news of user u in the total order
+ *                                     (score descending, then news id ascending)
+ * Row 0 of news_vecs is the unknown / padding news and is never returned.  exclude (optional, [U, E] int32, row stride
+ * ld_exclude, E <= 64): ids user u must not be given, e.g. the clicked history; entries that are 0 or outside [1, V) are
+ * ignored, duplicates are allowed.  A news whose score is NaN is never returned and does not disturb the others.  With fewer
+ * than k eligible news the tail of the row is id 0, score -inf.
+ * One (u, v) score is one fmaf chain over the vector width in a fixed order: its bits are the same in any user tile, in any
+ * corpus slice and for any `splits` (they need not equal nr_score_eval's, which sums in another order).
+ * Two launches: the fused scoring + selection pass over a grid of user tiles x `splits` corpus slices, then a per-user merge
+ * of the slices' lists.  No [U, V] buffer exists anywhere: ws is U * splits * k * 8 bytes.
+ *   N        vector width, a multiple of 4, at most 1024; ld_news, ld_user multiples of 4, buffers 16-byte aligned
+ *   k        1 .. 128
+ *   splits   0: the library chooses (fills the chip for few users, 1-2 for many); > 0: that many slices, at most
+ *            min(256, 8192 / k)
+ *   ws       nr_score_topk_workspace_bytes(d) bytes, 8-byte aligned (the query reads U, V, N, k, splits only; 0 = bad
+ *            descriptor, see nr_last_error)                                                                        */
+#define NR_TOPK_MAX_K 128
+#define NR_TOPK_MAX_N 1024
+#define NR_TOPK_MAX_EXCLUDE 64
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, k;
+  const int32_t* exclude;
+  int ld_exclude, E;
+  int splits;
+  int32_t* out_ids;
+  float* out_scores;
+  void* ws;
+  size_t ws_bytes;
+} nr_topk_desc;
+size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d);
+int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

@@ -481,6 +481,7 @@ int nr_abi_sizes(size_t* out, int n) {
   out[0] = sizeof(nr_mhsa_desc); out[1] = sizeof(nr_conv_desc); out[2] = sizeof(nr_pool_desc); out[3] = sizeof(nr_linear_desc);
   if (n >= 6) { out[4] = sizeof(nr_cast_job); out[5] = sizeof(nr_pack_job); }
   if (n >= 7) out[6] = sizeof(nr_adam_rows_desc);
+  if (n >= 8) out[7] = sizeof(nr_topk_desc);
   return NR_OK;
 }
 

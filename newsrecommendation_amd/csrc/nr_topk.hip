@@ -1,0 +1,315 @@
+// Full-corpus top-k recommendation: score[u, v] = <news_vecs[v], user[u]> over the WHOLE news table and, per user, the k best
+// news under the total order (score descending, news id ascending) -- without the [U, V] score matrix ever existing.
+//
+//   topk_select_kernel<MT>  grid = user tiles x corpus slices, 8 waves.  A workgroup keeps its TU = 16 * MT users' vectors in
+//                           LDS and streams its slice of the table through LDS in chunks of 128 news rows (k-slabs of 32
+//                           columns, double buffered through registers).  Wave w forms the [TU x 16] score tile of news rows
+//                           16w .. 16w + 15 of the chunk on v_mfma_f32_16x16x4_f32; one (u, v) score is ONE fmaf chain over
+//                           the vector width in a fixed order (k-slab, sub-step e, MFMA k-group), whatever the tile, slice or
+//                           user-tile size, so its bits do not depend on where it falls.  The chunk's scores go through an
+//                           LDS tile (32 KiB per 6.5 MFLOP of MFMA work) so that ONE wave sees all 128 scores of a user: it
+//                           compares them with that user's running k-th-best threshold and ballots; nothing passes in the
+//                           common case.  What passes is checked against the exclusion list and replaces the worst of
+//                           the user's k candidates (two per lane, in registers; a wave-wide minimum finds the next worst).
+//   topk_merge_kernel       one workgroup per user: bitonic sort of the splits * k candidates in LDS, the first k written out.
+//
+// A candidate is one 64-bit key: (order-preserving image of the score) << 32 | ~id.  Larger key = better; key 0 = "nothing"
+// (NaN scores map to it and are never kept; it decodes to id 0, score -inf, the fill of a short row).  Ids of a slice arrive in
+// ascending order, so a score that only TIES the threshold can never displace a kept one: the fast test is a strict >.
+#include "nr_common.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int TK_THREADS = 512;
+constexpr int TK_WAVES = TK_THREADS / 64;
+constexpr int TK_ROWS = 128;        // news rows per chunk = 16 per wave
+constexpr int TK_KS = 32;           // columns per k-slab
+constexpr int TK_LDB = TK_KS + 4;   // slab row stride: 16 rows at one column land in 16 different 4-bank groups
+constexpr int TK_LDS_TILE = TK_ROWS + 4;
+constexpr int TK_STAGE_FLOATS = 2 * TK_ROWS * TK_LDB;   // two slabs; the score tile [TU, TK_LDS_TILE] lives in the same bytes
+constexpr size_t TK_LDS_MAX = 160 * 1024;
+constexpr int TK_CUS = 256;         // MI355X; the slice count is host arithmetic (the workspace size depends on it)
+constexpr int TK_MERGE_MAX = 8192;  // candidates one merge workgroup sorts in LDS (64 KiB)
+
+static_assert(64 * TK_LDS_TILE <= TK_STAGE_FLOATS, "score tile must fit the staging buffers");
+
+__host__ __device__ inline int tk_npad(int N) { return (N + TK_KS - 1) / TK_KS * TK_KS; }
+inline size_t tk_lds_bytes(int TU, int N, int k) {
+  return ((size_t)TU * (tk_npad(N) + 4) + TK_STAGE_FLOATS) * sizeof(float) + (size_t)TU * k * sizeof(u64) + (size_t)TU * sizeof(uint32_t);
+}
+inline int tk_user_tile(int N, int k) {
+  for (int tu = 64; tu > 16; tu >>= 1)
+    if (tk_lds_bytes(tu, N, k) <= TK_LDS_MAX) return tu;
+  return 16;
+}
+inline int tk_max_splits(int k) { return TK_MERGE_MAX / k < 256 ? TK_MERGE_MAX / k : 256; }
+// slices: enough workgroups to fill the chip when there are few user tiles, 1-2 when there are many; never more slices than chunks
+inline int tk_auto_splits(int U, int V, int N, int k) {
+  const long tiles = ((long)U + tk_user_tile(N, k) - 1) / tk_user_tile(N, k);
+  long s = (TK_CUS + tiles - 1) / tiles;
+  const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
+  if (s > chunks) s = chunks;
+  if (s > tk_max_splits(k)) s = tk_max_splits(k);
+  return s < 1 ? 1 : (int)s;
+}
+
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (!(s == s)) return 0u;
+  const uint32_t b = __float_as_uint(s + 0.0f);               // -0 -> +0: the two compare equal, so they share a key
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+__device__ __forceinline__ u64 wave_min_u64(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+struct TopkArgs {
+  const float* news;
+  const float* user;
+  const int32_t* exclude;
+  u64* part;              // [U, splits, k]
+  size_t ld_news, ld_user, ld_excl;
+  int V, U, N, k, E, splits, per;
+};
+
+template <int MT>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
+  constexpr int TU = 16 * MT;
+  extern __shared__ __attribute__((aligned(16))) float tk_smem[];
+  const int npad = tk_npad(a.N), ldu = npad + 4;
+  float* sU = tk_smem;                                  // [TU, ldu]   user vectors, zero beyond N and beyond U
+  float* sB = sU + (size_t)TU * ldu;                    // [2, TK_ROWS, TK_LDB] news slabs | [TU, TK_LDS_TILE] scores of a chunk
+  u64* sList = reinterpret_cast<u64*>(sB + TK_STAGE_FLOATS);   // [TU, k]  candidates, 0 = empty
+  uint32_t* sThr = reinterpret_cast<uint32_t*>(sList + (size_t)TU * a.k);   // [TU]  score key of the worst candidate (0: not full)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int u0 = blockIdx.x * TU;
+  const long v_lo = 1 + (long)blockIdx.y * a.per;
+  const long v_hi = v_lo + a.per < a.V ? v_lo + a.per : a.V;
+
+  for (int i = tid; i < TU * (npad / 4); i += TK_THREADS) {
+    const int r = i / (npad / 4), c = (i - r * (npad / 4)) * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (u0 + r < a.U && c < a.N) v = *reinterpret_cast<const f32x4*>(a.user + (size_t)(u0 + r) * a.ld_user + c);
+    *reinterpret_cast<f32x4*>(sU + (size_t)r * ldu + c) = v;
+  }
+  for (int i = tid; i < TU * a.k; i += TK_THREADS) sList[i] = 0ull;
+  if (tid < TU) sThr[tid] = 0u;
+
+  // staging: thread -> rows (tid >> 3) and (tid >> 3) + 64 of the chunk, columns 4 * (tid & 7) .. + 3 of the slab
+  const int srow = tid >> 3, scol = (tid & 7) * 4;
+  const int ksteps = npad / TK_KS;
+  f32x4 g0, g1;
+  auto load_slab = [&](long vc, int ks) {
+    const int c = ks * TK_KS + scol;
+    const long r0 = vc + srow, r1 = r0 + 64;
+    g0 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    g1 = g0;
+    if (c < a.N) {
+      if (r0 < v_hi) g0 = *reinterpret_cast<const f32x4*>(a.news + (size_t)r0 * a.ld_news + c);
+      if (r1 < v_hi) g1 = *reinterpret_cast<const f32x4*>(a.news + (size_t)r1 * a.ld_news + c);
+    }
+  };
+  auto store_slab = [&](int buf) {
+    float* d = sB + (size_t)buf * TK_ROWS * TK_LDB + srow * TK_LDB + scol;
+    *reinterpret_cast<f32x4*>(d) = g0;
+    *reinterpret_cast<f32x4*>(d + 64 * TK_LDB) = g1;
+  };
+
+  const int frow = lane & 15, fk = (lane >> 4) * 8;
+  if (v_lo < v_hi) load_slab(v_lo, 0);
+  for (long vc = v_lo; vc < v_hi; vc += TK_ROWS) {
+    store_slab(0);
+    __syncthreads();
+    f32x4 acc[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ++ks) {
+      if (ks + 1 < ksteps) load_slab(vc, ks + 1);
+      const float* pb = sB + (size_t)(ks & 1) * TK_ROWS * TK_LDB + (wave * 16 + frow) * TK_LDB + fk;
+      const f32x4 b0 = *reinterpret_cast<const f32x4*>(pb), b1 = *reinterpret_cast<const f32x4*>(pb + 4);
+      f32x4 a0[MT], a1[MT];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const float* pa = sU + (size_t)(i * 16 + frow) * ldu + ks * TK_KS + fk;
+        a0[i] = *reinterpret_cast<const f32x4*>(pa);
+        a1[i] = *reinterpret_cast<const f32x4*>(pa + 4);
+      }
+      // sub-step e contracts columns ks * 32 + 8 * g + e, g = 0 .. 3 in the MFMA's own order: the same chain for every (u, v)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i][e], b0[e], acc[i], 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][e], b1[e], acc[i], 0, 0, 0);
+      if (ks + 1 < ksteps) store_slab((ks + 1) & 1);
+      __syncthreads();
+    }
+    if (vc + TK_ROWS < v_hi) load_slab(vc + TK_ROWS, 0);      // in flight while this chunk is selected from
+
+    // acc[i][r] = score of user i * 16 + 4 * (lane >> 4) + r, news row 16 * wave + (lane & 15) of the chunk
+    float* sS = sB;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sS[(i * 16 + 4 * (lane >> 4) + r) * TK_LDS_TILE + wave * 16 + frow] = acc[i][r];
+    __syncthreads();
+
+    const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
+    for (int ul = wave; ul < TU && u0 + ul < a.U; ul += TK_WAVES) {
+      const uint32_t k0 = lane < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane]) : 0u;
+      const uint32_t k1 = lane + 64 < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane + 64]) : 0u;
+      uint32_t thr = sThr[ul];
+      if (__ballot(k0 > thr || k1 > thr) == 0ull) continue;
+      // slow path: this user's candidates in registers (slots lane and lane + 64; slots >= k can never be the minimum)
+      u64* list = sList + (size_t)ul * a.k;
+      u64 c0 = lane < a.k ? list[lane] : ~0ull, c1 = lane + 64 < a.k ? list[lane + 64] : ~0ull;
+      u64 mn = wave_min_u64(c0 < c1 ? c0 : c1);
+      const int32_t ex = (a.exclude != nullptr && lane < a.E) ? a.exclude[(size_t)(u0 + ul) * a.ld_excl + lane] : 0;
+      for (int half = 0; half < 2; ++half) {
+        const uint32_t kh = half ? k1 : k0;
+        u64 pass = __ballot(kh > thr);
+        while (pass) {
+          const int j = __ffsll((long long)pass) - 1;
+          pass &= pass - 1;
+          const uint32_t key = __shfl(kh, j, 64);
+          if (key <= thr) continue;                          // the threshold rose since the ballot
+          const uint32_t id = (uint32_t)(vc + half * 64 + j);
+          if (__ballot(ex == (int32_t)id) != 0ull) continue; // ids are >= 1: the 0 of an unused lane never matches
+          const u64 cand = ((u64)key << 32) | (uint32_t)~id;
+          const u64 at0 = __ballot(c0 == mn);                // replace the worst (an empty slot while there is one)
+          if (at0) {
+            if (lane == __ffsll((long long)at0) - 1) c0 = cand;
+          } else {
+            const u64 at1 = __ballot(c1 == mn);
+            if (lane == __ffsll((long long)at1) - 1) c1 = cand;
+          }
+          mn = wave_min_u64(c0 < c1 ? c0 : c1);
+          thr = (uint32_t)(mn >> 32);
+        }
+      }
+      if (lane < a.k) list[lane] = c0;
+      if (lane + 64 < a.k) list[lane + 64] = c1;
+      if (lane == 0) sThr[ul] = thr;
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+  __syncthreads();
+  for (int i = tid; i < TU * a.k; i += TK_THREADS) {
+    const int ul = i / a.k, j = i - ul * a.k;
+    if (u0 + ul < a.U) a.part[((size_t)(u0 + ul) * a.splits + blockIdx.y) * a.k + j] = sList[i];
+  }
+}
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__ part, int n, int P, int k, int32_t* __restrict__ out_ids,
+                                                          float* __restrict__ out_scores) {
+  extern __shared__ __attribute__((aligned(16))) u64 tk_keys[];
+  const int tid = threadIdx.x;
+  const size_t u = blockIdx.x;
+  for (int i = tid; i < P; i += 256) tk_keys[i] = i < n ? part[u * n + i] : 0ull;
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int t = tid; t < P / 2; t += 256) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const u64 x = tk_keys[lo], y = tk_keys[hi];
+        if ((x < y) == desc && x != y) {
+          tk_keys[lo] = y;
+          tk_keys[hi] = x;
+        }
+      }
+    }
+  __syncthreads();
+  for (int i = tid; i < k; i += 256) {
+    const u64 key = tk_keys[i];
+    out_ids[u * k + i] = key ? (int32_t)~(uint32_t)key : 0;
+    out_scores[u * k + i] = key ? key_score((uint32_t)(key >> 32)) : -__builtin_inff();
+  }
+}
+
+// argument checks shared by the size query and the call; 0 = fine
+int topk_check(const nr_topk_desc* d) {
+  NR_CHECK_ARG(d != nullptr, "score_topk: null descriptor");
+  NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "score_topk: k = %d, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
+  NR_CHECK_ARG(d->V >= 2, "score_topk: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
+  NR_CHECK_ARG(d->U >= 1, "score_topk: U = %d users", d->U);
+  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_topk: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
+               NR_TOPK_MAX_N);
+  NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_topk: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
+  NR_CHECK_ARG(d->splits >= 0 && d->splits <= tk_max_splits(d->k), "score_topk: splits = %d, must be 0 (library's choice) or in [1, %d] for k = %d",
+               d->splits, tk_max_splits(d->k), d->k);
+  return NR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d) {
+  if (topk_check(d) != NR_OK) return 0;
+  const int splits = d->splits > 0 ? d->splits : tk_auto_splits(d->U, d->V, d->N, d->k);
+  return (size_t)d->U * splits * d->k * sizeof(u64);
+}
+
+int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
+  const int rc = topk_check(d);
+  if (rc != NR_OK) return rc;
+  NR_CHECK_ARG(d->news_vecs && d->user && d->out_ids && d->out_scores, "score_topk: null pointer (news_vecs, user, out_ids, out_scores)");
+  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
+                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
+               "score_topk: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_ARG(d->E == 0 || d->exclude == nullptr || d->ld_exclude >= d->E, "score_topk: exclusion row stride %d < E = %d", d->ld_exclude, d->E);
+  const size_t need = nr_score_topk_workspace_bytes(d);
+  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
+               "score_topk: workspace holds %zu bytes, nr_score_topk_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  const int splits = d->splits > 0 ? d->splits : tk_auto_splits(d->U, d->V, d->N, d->k);
+  const int TU = tk_user_tile(d->N, d->k);
+  TopkArgs a;
+  a.news = d->news_vecs; a.user = d->user;
+  a.exclude = d->E > 0 ? d->exclude : nullptr;
+  a.part = reinterpret_cast<u64*>(d->ws);
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_excl = (size_t)d->ld_exclude;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.E = d->E; a.splits = splits;
+  a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
+  const size_t smem = tk_lds_bytes(TU, d->N, d->k);
+  const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
+  {
+    NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
+#define NR_TOPK_LAUNCH(MT)                                                                                                                  \
+  do {                                                                                                                                      \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+    hipLaunchKernelGGL(topk_select_kernel<MT>, grid, dim3(TK_THREADS), smem, s, a);                                                        \
+  } while (0)
+    if (TU == 64) NR_TOPK_LAUNCH(4);
+    else if (TU == 32) NR_TOPK_LAUNCH(2);
+    else NR_TOPK_LAUNCH(1);
+#undef NR_TOPK_LAUNCH
+  }
+  NR_CHECK_LAUNCH();
+  const int n = splits * d->k;
+  int P = 2;
+  while (P < n) P <<= 1;
+  {
+    NrProfScope ps(s, "topk_merge[U=%d,n=%d,k=%d]", d->U, n, d->k);
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)d->U), dim3(256), (size_t)P * sizeof(u64), s, (const u64*)a.part, n, P, d->k, d->out_ids,
+                       d->out_scores);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+}  // extern "C"

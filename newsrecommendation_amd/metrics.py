@@ -40,3 +40,30 @@ def mrr_score(y_true, y_score):
 def ctr_score(y_true, y_score, k=1):
     order = np.argsort(y_score)[::-1]
     return np.mean(np.take(y_true, order[:k]))
+
+
+def topk_reference(a, b=None, *, k, exclude=None):
+    """Host statement of the full-corpus recommendation contract (include/nrhip.h, nr_score_topk); tests check the device
+    against it, no product path calls it.
+
+    `a` is the score matrix [U, V], or, with `b` given, the news vectors [V, N] and `b` the user vectors [U, N]: the scores
+    are then <a[v], b[u]> in float64.  Per user the k best news in the total order (score descending, news id ascending):
+    news 0 (the padding row) is never eligible, nor is an id listed in exclude[u] (entries that are 0 or outside [1, V) mean
+    nothing, duplicates are allowed), nor a news whose score is NaN.  A row with fewer than k eligible news is filled with
+    id 0, score -inf.  Returns (ids int32 [U, k], scores float64 [U, k])."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    U, V = scores.shape
+    ids = np.zeros((U, k), dtype=np.int32)
+    out = np.full((U, k), -np.inf, dtype=np.float64)
+    for u in range(U):
+        ok = ~np.isnan(scores[u])
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        cand = np.flatnonzero(ok)
+        order = cand[np.lexsort((cand, -scores[u, cand]))][:k]      # primary key: score descending; ties: id ascending
+        ids[u, :len(order)] = order
+        out[u, :len(order)] = scores[u, order]
+    return ids, out

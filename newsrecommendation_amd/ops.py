@@ -993,6 +993,42 @@ def score_eval(news_vecs, cand_ids, imp_of, user_vecs) -> torch.Tensor:
     return out
 
 
+@torch.no_grad()
+def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0):
+    """Full-corpus recommendation (nr_score_topk): for every user the k best news of the whole table under the order (score
+    descending, news id ascending), score[u, v] = <news_vecs[v], user_vecs[u]> in exact fp32.  Row 0 of `news_vecs` (the
+    padding news) is never returned; `exclude` ([U, E <= 64] news ids per user, 0 = no entry) neither.  No [U, V] score matrix
+    is formed.  Returns (ids int32 [U, k], scores fp32 [U, k]); a row with fewer than k eligible news ends in id 0, score -inf.
+    `splits`: 0 = the library chooses the number of corpus slices; tests force it."""
+    _need_gpu(news_vecs, user_vecs, exclude)
+    for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"score_topk: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
+                               f"strides {tuple(t.stride())}")
+    V, N = news_vecs.shape
+    U = user_vecs.shape[0]
+    if user_vecs.shape[1] != N:
+        raise RuntimeError(f"score_topk: vector widths differ ({N} vs {user_vecs.shape[1]})")
+    dev = news_vecs.device
+    ids = torch.empty(U, int(k), dtype=torch.int32, device=dev)
+    scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
+    if U == 0:
+        return ids, scores
+    ex, E = None, 0
+    if exclude is not None:
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"score_topk: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        E = exclude.shape[1]
+        ex = exclude.detach().to(torch.int32).contiguous() if E else None
+    d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), exclude=ptr(ex), ld_exclude=E, E=E,
+                      splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores))
+    ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_topk(C.byref(d), _stream()), "nr_score_topk")
+    return ids, scores
+
+
 def stack_rows(a, b, mask_b=None, flags=True):
     """[a ; b] of two int32 id matrices with the same row width (candidate titles, then history titles) and, if asked, the int32
     "needed" flags [1 .. 1 ; mask_b != 0] of the stacked rows -- one launch (nr_stack_rows)."""

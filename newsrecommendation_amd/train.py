@@ -31,7 +31,7 @@ import torch
 import torch.distributed as dist
 from torch.utils.data import DataLoader
 
-from . import ops, parallel
+from . import _lib, ops, parallel
 from .data import DatasetTrain, IndexedTestShard, IndexedTrainShard
 
 
@@ -252,14 +252,10 @@ def _short_history_split(shard, H):
     return cached[1], cached[2]
 
 
-@torch.no_grad()
-def score_shard(model, news_vecs, shard: IndexedTestShard, batch_size, device):
-    """Rows a13 + f2 on the device: user vectors of every impression of the shard (history vectors gathered from the
-    news-vector table), candidate scores (src/main.py:253) and the per-impression ranking metrics.
-    Returns (scores [n_cand] device fp32, sums device fp64 [5] = scored count + 4 metric sums)."""
-    n = len(shard)
-    hist = torch.as_tensor(shard.hist, device=device)
-    mask = torch.as_tensor(shard.mask, device=device)
+def _user_vectors(model, news_vecs, hist, mask, batch_size, device, owner):
+    """User vectors [n, news_dim] fp32 of n histories given as indices into the news-vector table (`hist`, `mask`: device
+    tensors [n, H]).  `owner` carries the host copy of the mask (`owner.mask`) and keeps the short-history split made from it."""
+    n = hist.shape[0]
     user = torch.empty(n, news_vecs.shape[1], dtype=torch.float32, device=device)
     # masked user encoder (src/demo.sh:26): the gather can hand over the compute dtype directly (gather + cast in one pass)
     margs = getattr(model, "args", None)
@@ -273,7 +269,7 @@ def score_shard(model, news_vecs, shard: IndexedTestShard, batch_size, device):
         # user whose first H - 32 slots are all masked is encoded from the LAST 32 slots alone -- one 32 x 32 attention tile per
         # head through the title-shape kernel (2.5 x the item rate of the 64-row kernel) and 32 instead of H pooling rows.  The
         # split is made on the host from the shard's own mask array (no device synchronisation); same vectors.
-        groups, on_device = _short_history_split(shard, H)
+        groups, on_device = _short_history_split(owner, H)
         for g, (idx_np, off) in enumerate(groups):
             if len(idx_np) == 0:
                 continue
@@ -293,6 +289,18 @@ def score_shard(model, news_vecs, shard: IndexedTestShard, batch_size, device):
             else:
                 log_vecs = ops.embed_gather(news_vecs, hist[a:b], code)               # [B, H, news_dim], device gather
                 user[a:b] = model.user_encoder(log_vecs, mask[a:b])                   # src/main.py:247
+    return user
+
+
+@torch.no_grad()
+def score_shard(model, news_vecs, shard: IndexedTestShard, batch_size, device):
+    """Rows a13 + f2 on the device: user vectors of every impression of the shard (history vectors gathered from the
+    news-vector table), candidate scores (src/main.py:253) and the per-impression ranking metrics.
+    Returns (scores [n_cand] device fp32, sums device fp64 [5] = scored count + 4 metric sums)."""
+    n = len(shard)
+    hist = torch.as_tensor(shard.hist, device=device)
+    mask = torch.as_tensor(shard.mask, device=device)
+    user = _user_vectors(model, news_vecs, hist, mask, batch_size, device, shard)
     offsets = torch.as_tensor(shard.offsets, device=device)
     counts = shard.offsets[1:] - shard.offsets[:-1]
     imp_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=device), torch.as_tensor(counts, device=device).long())
@@ -300,6 +308,34 @@ def score_shard(model, news_vecs, shard: IndexedTestShard, batch_size, device):
     scores = ops.score_eval(news_vecs, cand, imp_of, user) if cand.numel() else torch.zeros(0, device=device)
     sums = ops.eval_metrics(scores, torch.as_tensor(shard.label, device=device), offsets, max_cand=int(counts.max()) if n else 0)
     return scores, sums
+
+
+class _Histories:
+    """What _user_vectors needs of a shard: the mask on the host."""
+
+    def __init__(self, mask):
+        self.mask = mask
+
+
+@torch.no_grad()
+def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192):
+    """Full-corpus recommendation: for every user the k best news of the whole table `news_vecs` ([N+1, news_dim], what
+    encode_news returns), none of them the padding news 0.  hist_idx [U, H]: the users' clicked histories as news indices,
+    front padded with 0 (src/dataset.py:17-24); mask [U, H]: 1 for a real slot.  The user vectors come from the code
+    score_shard uses (_user_vectors); scoring and selection are one fused pass (ops.score_topk): no [U, V] score matrix.
+    exclude_history: a user is not given what they already clicked.  The kernel takes at most 64 excluded ids per user: of a
+    history wider than 64 slots only the LAST 64 (the most recent clicks) are excluded.
+    Returns (ids int32 [U, k], scores fp32 [U, k]) on the device, rows sorted by (score descending, id ascending); a row with
+    fewer than k eligible news ends in id 0, score -inf.  Several ranks: the caller shards the users; there is no collective."""
+    device = news_vecs.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    news_vecs = news_vecs.detach().float().contiguous()
+    user = _user_vectors(model, news_vecs, hist, m, batch_size, device, _Histories(mask))
+    exclude = None
+    if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
+        exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
+    return ops.score_topk(news_vecs, user, k, exclude=exclude)
 
 
 @torch.no_grad()

@@ -1,0 +1,117 @@
+#!/usr/bin/env python
+"""Full-corpus top-k recommendation: the fused call (ops.score_topk) against torch.matmul + torch.topk on the same device.
+
+    python tools/topk_probe.py [--news 100001] [--dim 400] [--k 10] [--users 64 8192] [--calls 30] [--warmup 5] [--out FILE]
+
+Both sides take the same fp32 inputs.  Per U: every call is timed with a pair of device events, the two sides alternate call
+by call (so that a disturbance of the machine hits both), and the median, minimum, maximum and inter-quartile spread of the
+timed calls are reported, with the peak device memory of one call above what the inputs occupy.  The fused side's share of the
+fp32 MFMA peak counts the algorithmic 2 * U * V * N FLOPs over the WHOLE call (both launches), against 157.3 TFLOP/s.
+One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from newsrecommendation_amd import ops  # noqa: E402
+
+PEAK_FP32_MATRIX = 157.3e12
+
+
+def fused(news, user, k):
+    return ops.score_topk(news, user, k)
+
+
+def baseline(news, user, k):
+    sc, ids = torch.topk(torch.matmul(user, news[1:].T), k, dim=1)          # row 0 is the padding news
+    return ids + 1, sc
+
+
+def timed(fn, *a):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn(*a)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def peak_bytes(fn, *a):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    out = fn(*a)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - before
+    del out
+    return int(peak)
+
+
+def stats(ms):
+    a = np.asarray(ms)
+    q1, med, q3 = np.percentile(a, [25, 50, 75])
+    return {"median_ms": round(float(med), 4), "min_ms": round(float(a.min()), 4), "max_ms": round(float(a.max()), 4),
+            "iqr_ms": round(float(q3 - q1), 4), "calls": len(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--news", type=int, default=100001)
+    ap.add_argument("--dim", type=int, default=400)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--users", type=int, nargs="+", default=[64, 8192])
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("topk_probe needs a GPU")
+    if args.calls < 20:
+        raise SystemExit("at least 20 timed calls")
+    g = torch.Generator().manual_seed(0)
+    news = (torch.randn(args.news, args.dim, generator=g) * 0.4).cuda()
+    lines = []
+    for U in args.users:
+        user = (torch.randn(U, args.dim, generator=g) * 0.4).cuda()
+        for _ in range(args.warmup):
+            fused(news, user, args.k)
+            baseline(news, user, args.k)
+        torch.cuda.synchronize()
+        t_f, t_b = [], []
+        for _ in range(args.calls):
+            t_f.append(timed(fused, news, user, args.k))
+            t_b.append(timed(baseline, news, user, args.k))
+        ids_f, sc_f = fused(news, user, args.k)
+        ids_b, sc_b = baseline(news, user, args.k)
+        row = {"U": U, "V": args.news, "N": args.dim, "k": args.k, "fused": stats(t_f), "baseline": stats(t_b),
+               "fused_peak_bytes": peak_bytes(fused, news, user, args.k), "baseline_peak_bytes": peak_bytes(baseline, news, user, args.k),
+               "score_matrix_bytes": U * (args.news - 1) * 4,
+               "ids_equal_fraction": round(float((ids_f.long() == ids_b).float().mean()), 6),
+               "max_score_diff": float((sc_f - sc_b).abs().max())}
+        flops = 2.0 * U * args.news * args.dim
+        row["fused_tflops"] = round(flops / (row["fused"]["median_ms"] * 1e-3) / 1e12, 2)
+        row["fused_fraction_of_fp32_mfma_peak"] = round(row["fused_tflops"] * 1e12 / PEAK_FP32_MATRIX, 4)
+        row["baseline_tflops"] = round(flops / (row["baseline"]["median_ms"] * 1e-3) / 1e12, 2)
+        lines.append(row)
+        print(json.dumps(row), flush=True)
+        del user
+    last = lines[-1]
+    spread = max(last["fused"]["iqr_ms"], last["baseline"]["iqr_ms"])
+    verdict = {"U": last["U"], "spread_ms": spread,
+               "time_ok": last["fused"]["median_ms"] <= last["baseline"]["median_ms"] + spread,
+               "memory_ok": last["baseline_peak_bytes"] - last["fused_peak_bytes"] >= last["score_matrix_bytes"]}
+    lines.append(verdict)
+    print(json.dumps(verdict), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.writelines(json.dumps(r) + "\n" for r in lines)
+
+
+if __name__ == "__main__":
+    main()
