@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -410,6 +410,56 @@ typedef struct {
 } nr_topk_desc;
 size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d);
 int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K10  full-corpus rank evaluation.  The reference evaluates by re-ranking the candidates of one impression
+ * (src/main.py:249-263: `np.dot(news_vec, user_vec)` over `news_scoring[candidate]`, then src/metrics.py:6-24 mrr_score /
+ * ndcg_score on those few dozen scores); this call ranks a user's held-out clicks against EVERY news of the table, the
+ * retrieval counterpart of nr_score_topk:
+ *   rank[u, j]  = 1-based position of news targets[u, j] among the eligible news of user u in nr_score_topk's total order
+ *                 (score descending, then news id ascending); eligible = ids 1 .. V-1 that are not in exclude[u] and whose
+ *                 score is not NaN
+ *   rank[u, j]  = 0 ("not ranked"), score -inf, when the target is 0 or outside [1, V), is excluded, has a NaN score, or
+ *                 repeats an earlier entry of its row
+ * Scores are those of nr_score_topk bit for bit (one fmaf chain per (u, v), the same instruction sequence), so
+ * 1 <= rank[u, j] <= k holds exactly when targets[u, j] is in the top-k row of user u, at place rank - 1.
+ *   targets     [U, T] int32, row stride ld_targets, T in 1 .. 64
+ *   exclude     as in nr_topk_desc (optional, [U, E], E <= 64)
+ *   ks, n_ks    HOST array of n_ks <= 8 cut-offs k >= 1 for out_sums (n_ks may be 0)
+ *   out_ranks   [U, T] int32;  out_scores [U, T] fp32
+ *   out_sums    optional DEVICE fp64 [2 + 2 n_ks], OVERWRITTEN: [0] = users with n_u >= 1 ranked targets, [1] = sum MRR_u, then per
+ *               k: sum Recall@k_u, sum nDCG@k_u over those users, with (src/metrics.py:6-24 on the user's whole eligible row,
+ *               binary labels)  MRR_u = mean_j 1 / rank,  Recall@k_u = #{rank <= k} / n_u,
+ *               nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1)  /  sum_{i = 1 .. min(n_u, k)} 1 / log2(i + 1);
+ *               fp64, reduced in a fixed order (bit-reproducible)
+ *   N, ld_news, ld_user, splits: as in nr_topk_desc (splits at most 256); the result does not depend on splits
+ *   ws          nr_score_rank_workspace_bytes(d) bytes, 8-byte aligned (the query reads U, V, N, T, E, n_ks, ks, splits; 0 = bad
+ *               descriptor, see nr_last_error): O(U * T * splits), no [U, V] buffer exists anywhere
+ * Three launches (+ one for out_sums): the scores of the named ids (targets and excluded news, gathered rows through the same
+ * MFMA tile), the counting pass over user tiles x corpus slices, and a per-user finalize.                              */
+#define NR_RANK_MAX_TARGETS 64
+#define NR_RANK_MAX_KS 8
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, T;
+  const int32_t* targets;
+  int ld_targets;
+  const int32_t* exclude;
+  int ld_exclude, E;
+  int splits;
+  const int* ks; /* host */
+  int n_ks;
+  int32_t* out_ranks;
+  float* out_scores;
+  double* out_sums;
+  void* ws;
+  size_t ws_bytes;
+} nr_rank_desc;
+size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d);
+int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

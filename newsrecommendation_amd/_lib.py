@@ -73,6 +73,16 @@ class TopkDesc(C.Structure):
                 ("out_ids", C.c_void_p), ("out_scores", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+NR_RANK_MAX_TARGETS, NR_RANK_MAX_KS = 64, 8
+
+
+class RankDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("T", C.c_int), ("targets", C.c_void_p), ("ld_targets", C.c_int), ("exclude", C.c_void_p),
+                ("ld_exclude", C.c_int), ("E", C.c_int), ("splits", C.c_int), ("ks", C.POINTER(C.c_int)), ("n_ks", C.c_int),
+                ("out_ranks", C.c_void_p), ("out_scores", C.c_void_p), ("out_sums", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -89,7 +99,7 @@ _vp, _i, _f, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint32
 # name -> argtypes ; every entry returns int unless listed in RESTYPES.  Must list exactly the symbols of include/nrhip.h.
 RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": C.c_size_t, "nr_mhsa_workspace_bytes": C.c_size_t, "nr_conv_workspace_bytes": C.c_size_t, "nr_conv_table_workspace_bytes": C.c_size_t, "nr_pool_workspace_bytes": C.c_size_t,
             "nr_linear_workspace_bytes": C.c_size_t, "nr_adam_rows_workspace_bytes": C.c_size_t,
-            "nr_score_topk_workspace_bytes": C.c_size_t}
+            "nr_score_topk_workspace_bytes": C.c_size_t, "nr_score_rank_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
     "nr_last_error": [C.c_char_p, C.c_size_t],
@@ -142,6 +152,8 @@ SIGNATURES = {
     "nr_score_eval": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     "nr_score_topk_workspace_bytes": [C.POINTER(TopkDesc)],
     "nr_score_topk": [C.POINTER(TopkDesc), _vp],
+    "nr_score_rank_workspace_bytes": [C.POINTER(RankDesc)],
+    "nr_score_rank": [C.POINTER(RankDesc), _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -189,7 +201,7 @@ def lib():
                     fn = getattr(L, name)          # AttributeError if the .so lacks a declared symbol
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
-                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc)
+                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

@@ -1,0 +1,373 @@
+// Full-corpus rank evaluation: for every user and each of its held-out targets, the exact 1-based position of that news in the
+// user's ranking of the WHOLE table under the order of nr_score_topk (score descending, news id ascending) -- again without the
+// [U, V] score matrix.  Scores come from the tile of nr_score_tile.h, so they have the bits nr_score_topk sees: "rank <= k"
+// and "is in the top-k row" are the same statement.
+//
+//   rank_named_kernel       one workgroup per 16 users.  Chunk c of the tile is made of the table rows user c of the group NAMES:
+//                           its targets (chunk rows 0 .. 63) and its excluded ids (64 .. 127), gathered by id; of the [16 x 128]
+//                           scores only row c is kept.  One wave then settles everything that needs no other news: which
+//                           targets are ranked at all (in range, not NaN, not excluded, not a repeat), their 64-bit keys
+//                           (score key << 32 | ~id, as in nr_topk.hip) compacted to the front of the row, and for each the number
+//                           of distinct excluded news that beat it.
+//   rank_count_kernel<MT>   the grid and chunking of topk_select_kernel.  A wave owns 2 * MT users of the tile and holds their
+//                           compacted target keys (lane j = target j) and counters in registers; per chunk and user it ballots
+//                           "key of this news > key of target j" for the user's REAL targets only and adds the population
+//                           counts.  No exclusion test here.  Each slice stores its own counts: integers, added in rank_final,
+//                           so the result depends on neither `splits`, the user tile nor any arrival order.
+//   rank_final_kernel       one wave per user, one lane per target: rank = 1 + sum of the slices' counts - excluded news that
+//                           beat it; 0 and -inf for the not-ranked; the user's metric terms in fp64.
+//   rank_reduce_kernel      fixed-order sum of the per-user terms into out_sums (as metrics_reduce_kernel of nr_data.hip).
+#include <math.h>
+
+#include "nr_score_tile.h"
+
+namespace {
+
+constexpr int RK_SLOTS = NR_RANK_MAX_TARGETS;     // chunk rows 0 .. 63: targets, 64 .. 127: excluded ids
+constexpr int RK_MAX_SPLITS = 256;
+static_assert(NR_RANK_MAX_TARGETS == 64 && NR_TOPK_MAX_EXCLUDE == 64 && TK_ROWS == 128, "one lane per target and per excluded id");
+
+inline size_t rk_lds_bytes(int TU, int N) { return tk_tile_floats(TU, N) * sizeof(float); }
+// keys and counters of the counting pass live in registers: the tile is what the vectors and the staging buffers leave room for
+inline int rk_user_tile(int N) {
+  for (int tu = 64; tu > 16; tu >>= 1)
+    if (rk_lds_bytes(tu, N) <= TK_LDS_MAX) return tu;
+  return 16;
+}
+inline int rk_auto_splits(int U, int V, int N) {
+  const long tiles = ((long)U + rk_user_tile(N) - 1) / rk_user_tile(N);
+  long s = (TK_CUS + tiles - 1) / tiles;
+  const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
+  if (s > chunks) s = chunks;
+  if (s > RK_MAX_SPLITS) s = RK_MAX_SPLITS;
+  return s < 1 ? 1 : (int)s;
+}
+
+// workspace: 8-byte arrays first
+struct RankWs {
+  u64* keys;        // [U, T]           keys of the ranked targets, compacted
+  double* terms;    // [U, 2 + 2 n_ks]  counted, MRR_u, then Recall@k_u, nDCG@k_u per k
+  int32_t* part;    // [U, splits, T]   per slice: news of the slice that beat compact target p
+  int32_t* excl;    // [U, T]           distinct excluded news that beat compact target p
+  int32_t* pos;     // [U, T]           target slot j -> compact index, -1 = not ranked
+  int32_t* nu;      // [U]              ranked targets of the user
+  size_t bytes;
+};
+inline RankWs rk_carve(void* ws, int U, int T, int n_ks, int splits) {
+  RankWs w;
+  char* p = reinterpret_cast<char*>(ws);
+  const size_t ut = (size_t)U * T;
+  w.keys = reinterpret_cast<u64*>(p); p += ut * sizeof(u64);
+  w.terms = reinterpret_cast<double*>(p); p += (size_t)U * (2 + 2 * n_ks) * sizeof(double);
+  w.part = reinterpret_cast<int32_t*>(p); p += ut * splits * sizeof(int32_t);
+  w.excl = reinterpret_cast<int32_t*>(p); p += ut * sizeof(int32_t);
+  w.pos = reinterpret_cast<int32_t*>(p); p += ut * sizeof(int32_t);
+  w.nu = reinterpret_cast<int32_t*>(p); p += (size_t)U * sizeof(int32_t);
+  w.bytes = (size_t)(p - reinterpret_cast<char*>(ws));
+  return w;
+}
+
+struct RankArgs {
+  const float* news;
+  const float* user;
+  const int32_t* targets;
+  const int32_t* exclude;
+  RankWs w;
+  size_t ld_news, ld_user, ld_tgt, ld_excl;
+  int V, U, N, T, E, splits, per;
+};
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// lane j's 64-bit value, j the same in every lane
+__device__ __forceinline__ u64 lane_u64(u64 v, int j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 news_key(float score, uint32_t id) { return ((u64)score_key(score) << 32) | (uint32_t)~id; }
+
+// chunk row r = table row ids[r]; an id outside [1, V) is a row of zeros (its score is never looked at)
+struct RankNamedRows {
+  const float* news;
+  size_t ld;
+  const int32_t* ids;   // LDS, [128]
+  int V;
+  __device__ __forceinline__ const float* operator()(int r) const {
+    const int32_t id = ids[r];
+    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
+  }
+};
+
+__global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float rk_smem[];
+  ScoreTile<1> t(rk_smem, a.N);
+  int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [16, 128]
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * 16;
+  const int users = a.U - u0 < 16 ? a.U - u0 : 16;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  for (int i = tid; i < 16 * TK_ROWS; i += TK_THREADS) {
+    const int ul = i / TK_ROWS, s = i - ul * TK_ROWS;
+    int32_t id = 0;
+    if (ul < users) {
+      if (s < a.T) id = a.targets[(size_t)(u0 + ul) * a.ld_tgt + s];
+      else if (s >= RK_SLOTS && s - RK_SLOTS < a.E) id = a.exclude[(size_t)(u0 + ul) * a.ld_excl + s - RK_SLOTS];
+    }
+    sIds[i] = id;
+  }
+  __syncthreads();
+
+  RankNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  t.load_slab(rows, 0);
+  for (int c = 0; c < users; ++c) {
+    f32x4 acc[1];
+    rows.ids = sIds + c * TK_ROWS;
+    t.chunk(rows, acc);
+    if (c + 1 < users) {
+      rows.ids = sIds + (c + 1) * TK_ROWS;
+      t.load_slab(rows, 0);
+    }
+    t.put_scores(acc);
+    if (wave == 0) {
+      const size_t u = (size_t)(u0 + c);
+      const int32_t tg = sIds[c * TK_ROWS + lane], ex = sIds[c * TK_ROWS + RK_SLOTS + lane];
+      const bool t_in = lane < a.T && tg >= 1 && tg < a.V, x_in = lane < a.E && ex >= 1 && ex < a.V;
+      const u64 kt = news_key(t.scores()[c * TK_LDS_TILE + lane], (uint32_t)tg);
+      const u64 kx = news_key(t.scores()[c * TK_LDS_TILE + RK_SLOTS + lane], (uint32_t)ex);
+      bool ranked = t_in && (kt >> 32) != 0;                  // a NaN score has key 0
+      bool x_counts = x_in && (kx >> 32) != 0;                // a NaN news is never counted by the stream: nothing to take back
+      for (int j = 0; j < RK_SLOTS; ++j) {
+        const int32_t tj = __builtin_amdgcn_readlane(tg, j), xj = __builtin_amdgcn_readlane(ex, j);
+        if (j < a.T && lane > j && tg == tj) ranked = false;  // repeats an earlier entry
+        if (j < a.E && tg == xj) ranked = false;              // excluded
+        if (j < a.E && lane > j && ex == xj) x_counts = false;   // each excluded news once
+      }
+      const u64 mask = __ballot(ranked);
+      const int p = __popcll(mask & ((1ull << lane) - 1ull)), n = __popcll(mask);
+      int beaten_by = 0;
+      for (int j = 0; j < a.T; ++j) {
+        const int cnt = __popcll(__ballot(x_counts && kx > lane_u64(kt, j)));
+        if (lane == j) beaten_by = cnt;
+      }
+      if (ranked) {
+        a.w.keys[u * a.T + p] = kt;
+        a.w.excl[u * a.T + p] = beaten_by;
+      }
+      if (lane < a.T) a.w.pos[u * a.T + lane] = ranked ? p : -1;
+      if (lane == 0) a.w.nu[u] = n;
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+}
+
+template <int MT>
+__global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
+  constexpr int TU = 16 * MT, PER_WAVE = TU / TK_WAVES;
+  extern __shared__ __attribute__((aligned(16))) float rk_smem[];
+  ScoreTile<MT> t(rk_smem, a.N);
+  const int lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * TU;
+  const long v_lo = 1 + (long)blockIdx.y * a.per;
+  const long v_hi = v_lo + a.per < a.V ? v_lo + a.per : a.V;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  // user wave + 8 i of the tile: its n[i] compacted target keys, one per lane, and their counters
+  u64 tkey[PER_WAVE];
+  int32_t cnt[PER_WAVE];
+  int n[PER_WAVE];
+#pragma unroll
+  for (int i = 0; i < PER_WAVE; ++i) {
+    const int u = u0 + wave + TK_WAVES * i;
+    n[i] = u < a.U ? __builtin_amdgcn_readfirstlane(a.w.nu[u]) : 0;
+    tkey[i] = lane < n[i] ? a.w.keys[(size_t)u * a.T + lane] : ~0ull;
+    cnt[i] = 0;
+  }
+
+  ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
+  if (v_lo < v_hi) t.load_slab(rows, 0);
+  for (long vc = v_lo; vc < v_hi; vc += TK_ROWS) {
+    f32x4 acc[MT];
+    rows.vc = vc;
+    t.chunk(rows, acc);
+    rows.vc = vc + TK_ROWS;
+    if (rows.vc < v_hi) t.load_slab(rows, 0);                 // in flight while this chunk is counted
+    t.put_scores(acc);
+    const float* sS = t.scores();
+    const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      if (n[i] == 0) continue;
+      const int ul = wave + TK_WAVES * i;
+      // rows beyond the slice end get key 0; a NaN score gives 0 << 32 | ~id, below every target's key
+      const u64 k0 = lane < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane], (uint32_t)(vc + lane)) : 0ull;
+      const u64 k1 = lane + 64 < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane + 64], (uint32_t)(vc + lane + 64)) : 0ull;
+      for (int j = 0; j < n[i]; ++j) {
+        const u64 tk = lane_u64(tkey[i], j);                  // strict >: the target never counts itself
+        const int c = __popcll(__ballot(k0 > tk)) + __popcll(__ballot(k1 > tk));
+        cnt[i] += lane == j ? c : 0;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+#pragma unroll
+  for (int i = 0; i < PER_WAVE; ++i) {
+    const int u = u0 + wave + TK_WAVES * i;
+    if (u < a.U && lane < n[i]) a.w.part[((size_t)u * a.splits + blockIdx.y) * a.T + lane] = cnt[i];
+  }
+}
+
+struct RankKs {
+  int n;
+  int k[NR_RANK_MAX_KS];
+};
+
+__global__ __launch_bounds__(256) void rank_final_kernel(RankWs w, int U, int T, int splits, RankKs ks, int want_terms, int32_t* __restrict__ out_ranks,
+                                                          float* __restrict__ out_scores) {
+  const int lane = threadIdx.x & 63;
+  const size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= (size_t)U) return;
+  const int n = w.nu[u];
+  int rank = 0;
+  float score = -__builtin_inff();
+  if (lane < T) {
+    const int p = w.pos[u * T + lane];
+    if (p >= 0) {
+      int c = -w.excl[u * T + p];
+      for (int s = 0; s < splits; ++s) c += w.part[(u * splits + s) * T + p];
+      rank = 1 + c;
+      score = key_score((uint32_t)(w.keys[u * T + p] >> 32));
+    }
+    out_ranks[u * T + lane] = rank;
+    out_scores[u * T + lane] = score;
+  }
+  if (!want_terms) return;
+  // MRR_u = mean 1 / rank; Recall@k_u = #{rank <= k} / n; nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1) over the ideal
+  // sum_{i <= min(n, k)} 1 / log2(i + 1): src/metrics.py:6-24 on the user's whole eligible row with binary labels
+  double* o = w.terms + u * (2 + 2 * ks.n);
+  const double gain = rank > 0 ? 1.0 / log2((double)rank + 1.0) : 0.0, ideal = 1.0 / log2((double)lane + 2.0);
+  const double rr = wave_sum_d(rank > 0 ? 1.0 / (double)rank : 0.0);
+  if (lane == 0) {
+    o[0] = n > 0 ? 1.0 : 0.0;
+    o[1] = n > 0 ? rr / n : 0.0;
+  }
+  for (int i = 0; i < ks.n; ++i) {
+    const bool hit = rank > 0 && rank <= ks.k[i];
+    const int hits = __popcll(__ballot(hit));
+    const double dcg = wave_sum_d(hit ? gain : 0.0), idcg = wave_sum_d(lane < n && lane < ks.k[i] ? ideal : 0.0);
+    if (lane == 0) {
+      o[2 + 2 * i] = n > 0 ? (double)hits / n : 0.0;
+      o[3 + 2 * i] = n > 0 ? dcg / idcg : 0.0;
+    }
+  }
+}
+
+// fixed-order reduction of the per-user terms: sums[c] = sum_u terms[u, c]
+__global__ __launch_bounds__(1024) void rank_reduce_kernel(const double* __restrict__ terms, int U, int W, double* __restrict__ sums) {
+  __shared__ double sh[2 + 2 * NR_RANK_MAX_KS][16];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int c = 0; c < W; ++c) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < U; i += 1024) acc += terms[(size_t)i * W + c];
+    acc = wave_sum_d(acc);
+    if (lane == 0) sh[c][wid] = acc;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < W) {
+    double v = 0.0;
+    for (int k = 0; k < 16; ++k) v += sh[threadIdx.x][k];
+    sums[threadIdx.x] = v;
+  }
+}
+
+// argument checks shared by the size query and the call; 0 = fine
+int rank_check(const nr_rank_desc* d) {
+  NR_CHECK_ARG(d != nullptr, "score_rank: null descriptor");
+  NR_CHECK_ARG(d->T >= 1 && d->T <= NR_RANK_MAX_TARGETS, "score_rank: T = %d targets per user, must be in [1, %d]", d->T, NR_RANK_MAX_TARGETS);
+  NR_CHECK_ARG(d->V >= 2, "score_rank: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
+  NR_CHECK_ARG(d->U >= 1, "score_rank: U = %d users", d->U);
+  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_rank: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
+               NR_TOPK_MAX_N);
+  NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_rank: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
+  NR_CHECK_ARG(d->n_ks >= 0 && d->n_ks <= NR_RANK_MAX_KS, "score_rank: n_ks = %d cut-offs, at most %d", d->n_ks, NR_RANK_MAX_KS);
+  NR_CHECK_ARG(d->n_ks == 0 || d->ks != nullptr, "score_rank: null pointer (ks) with n_ks = %d", d->n_ks);
+  for (int i = 0; i < d->n_ks; ++i) NR_CHECK_ARG(d->ks[i] >= 1, "score_rank: cut-off k = %d at position %d, must be >= 1", d->ks[i], i);
+  NR_CHECK_ARG(d->splits >= 0 && d->splits <= RK_MAX_SPLITS, "score_rank: splits = %d, must be 0 (library's choice) or in [1, %d]", d->splits,
+               RK_MAX_SPLITS);
+  return NR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d) {
+  if (rank_check(d) != NR_OK) return 0;
+  const int splits = d->splits > 0 ? d->splits : rk_auto_splits(d->U, d->V, d->N);
+  return rk_carve(nullptr, d->U, d->T, d->n_ks, splits).bytes;
+}
+
+int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
+  const int rc = rank_check(d);
+  if (rc != NR_OK) return rc;
+  NR_CHECK_ARG(d->news_vecs && d->user && d->targets && d->out_ranks && d->out_scores,
+               "score_rank: null pointer (news_vecs, user, targets, out_ranks, out_scores)");
+  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
+                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
+               "score_rank: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_ARG(d->ld_targets >= d->T, "score_rank: target row stride %d < T = %d", d->ld_targets, d->T);
+  NR_CHECK_ARG(d->E == 0 || d->exclude == nullptr || d->ld_exclude >= d->E, "score_rank: exclusion row stride %d < E = %d", d->ld_exclude, d->E);
+  const size_t need = nr_score_rank_workspace_bytes(d);
+  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
+               "score_rank: workspace holds %zu bytes, nr_score_rank_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  const int splits = d->splits > 0 ? d->splits : rk_auto_splits(d->U, d->V, d->N);
+  const int TU = rk_user_tile(d->N);
+  RankArgs a;
+  a.news = d->news_vecs; a.user = d->user; a.targets = d->targets;
+  a.exclude = d->exclude;
+  a.w = rk_carve(d->ws, d->U, d->T, d->n_ks, splits);
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_tgt = (size_t)d->ld_targets; a.ld_excl = (size_t)d->ld_exclude;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.T = d->T; a.E = d->exclude != nullptr ? d->E : 0; a.splits = splits;
+  a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
+  {
+    NrProfScope ps(s, "rank_named[U=%d,N=%d,T=%d,E=%d]", d->U, d->N, d->T, a.E);
+    const size_t smem = rk_lds_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_named_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(rank_named_kernel, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  }
+  NR_CHECK_LAUNCH();
+  {
+    const size_t smem = rk_lds_bytes(TU, d->N);
+    const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
+    NrProfScope ps(s, "rank_count[U=%d,V=%d,N=%d,T=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->T, TU, splits);
+#define NR_RANK_LAUNCH(MT)                                                                                                                 \
+  do {                                                                                                                                     \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+    hipLaunchKernelGGL(rank_count_kernel<MT>, grid, dim3(TK_THREADS), smem, s, a);                                                        \
+  } while (0)
+    if (TU == 64) NR_RANK_LAUNCH(4);
+    else if (TU == 32) NR_RANK_LAUNCH(2);
+    else NR_RANK_LAUNCH(1);
+#undef NR_RANK_LAUNCH
+  }
+  NR_CHECK_LAUNCH();
+  RankKs ks;
+  ks.n = d->n_ks;
+  for (int i = 0; i < NR_RANK_MAX_KS; ++i) ks.k[i] = i < d->n_ks ? d->ks[i] : 1;
+  {
+    NrProfScope ps(s, "rank_final[U=%d,T=%d,splits=%d]", d->U, d->T, splits);
+    hipLaunchKernelGGL(rank_final_kernel, dim3((unsigned)((d->U + 3) / 4)), dim3(256), 0, s, a.w, d->U, d->T, splits, ks, d->out_sums != nullptr ? 1 : 0,
+                       d->out_ranks, d->out_scores);
+    if (d->out_sums != nullptr)
+      hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(1024), 0, s, (const double*)a.w.terms, d->U, 2 + 2 * d->n_ks, d->out_sums);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+}  // extern "C"

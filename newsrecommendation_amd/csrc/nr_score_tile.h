@@ -1,0 +1,141 @@
+// The exact-fp32 scoring tile of the full-corpus passes, shared by the top-k selection (nr_topk.hip) and the rank counting
+// (nr_rank.hip).  Both must give one (u, v) pair the SAME bits -- "rank <= k" and "is in the top-k row" are then one
+// statement -- so there is ONE definition of the tile.
+//
+// A workgroup of 8 waves keeps TU = 16 * MT user vectors in LDS and takes news rows in chunks of 128 (k-slabs of 32 columns,
+// double buffered through registers).  Wave w forms the [TU x 16] scores of chunk rows 16w .. 16w + 15 on
+// v_mfma_f32_16x16x4_f32; one (u, v) score is ONE fmaf chain over the vector width in a fixed order (k-slab, sub-step e, MFMA
+// k-group), whatever the tile, the place of the user in it, or the place of the news row in the chunk.  Where a chunk's rows
+// come from is the caller's: a slice of the table (ScoreStreamRows) or rows gathered by id.
+#pragma once
+#include "nr_common.h"
+
+namespace {   // per including unit, as when the tile was nr_topk.hip's own: no name of it reaches other units
+
+typedef unsigned long long u64;
+
+constexpr int TK_THREADS = 512;
+constexpr int TK_WAVES = TK_THREADS / 64;
+constexpr int TK_ROWS = 128;        // news rows per chunk = 16 per wave
+constexpr int TK_KS = 32;           // columns per k-slab
+constexpr int TK_LDB = TK_KS + 4;   // slab row stride: 16 rows at one column land in 16 different 4-bank groups
+constexpr int TK_LDS_TILE = TK_ROWS + 4;
+constexpr int TK_STAGE_FLOATS = 2 * TK_ROWS * TK_LDB;   // two slabs; the score tile [TU, TK_LDS_TILE] lives in the same bytes
+constexpr size_t TK_LDS_MAX = 160 * 1024;
+constexpr int TK_CUS = 256;         // MI355X; the slice count is host arithmetic (the workspace size depends on it)
+
+static_assert(64 * TK_LDS_TILE <= TK_STAGE_FLOATS, "score tile must fit the staging buffers");
+
+__host__ __device__ inline int tk_npad(int N) { return (N + TK_KS - 1) / TK_KS * TK_KS; }
+// LDS floats of the tile itself: the user vectors and the staging buffers
+inline size_t tk_tile_floats(int TU, int N) { return (size_t)TU * (tk_npad(N) + 4) + TK_STAGE_FLOATS; }
+
+// A score as an unsigned key: larger key = better score; NaN -> 0 ("nothing")
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (!(s == s)) return 0u;
+  const uint32_t b = __float_as_uint(s + 0.0f);               // -0 -> +0: the two compare equal, so they share a key
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+// chunk row r = news row vc + r of a table slice that ends at v_hi
+struct ScoreStreamRows {
+  const float* news;
+  size_t ld;
+  long vc, v_hi;
+  __device__ __forceinline__ const float* operator()(int r) const { return vc + r < v_hi ? news + (size_t)(vc + r) * ld : nullptr; }
+};
+
+template <int MT>
+struct ScoreTile {
+  static constexpr int TU = 16 * MT;
+  float* sU;                     // [TU, ldu]   user vectors, zero beyond N and beyond U
+  float* sB;                     // [2, TK_ROWS, TK_LDB] news slabs | [TU, TK_LDS_TILE] scores of a chunk
+  int N, npad, ldu, ksteps;
+  int tid, lane, wave;
+  int srow, scol;                // staging: thread -> rows srow and srow + 64 of the chunk, columns scol .. scol + 3 of the slab
+  int frow, fk;
+  f32x4 g0, g1;
+
+  __device__ __forceinline__ ScoreTile(float* smem, int n) {
+    N = n; npad = tk_npad(n); ldu = npad + 4; ksteps = npad / TK_KS;
+    sU = smem; sB = sU + (size_t)TU * ldu;
+    tid = threadIdx.x; lane = tid & 63; wave = tid >> 6;
+    srow = tid >> 3; scol = (tid & 7) * 4;
+    frow = lane & 15; fk = (lane >> 4) * 8;
+  }
+  __device__ __forceinline__ float* end() const { return sB + TK_STAGE_FLOATS; }
+
+  __device__ __forceinline__ void load_users(const float* user, size_t ld_user, int u0, int U) {
+    for (int i = tid; i < TU * (npad / 4); i += TK_THREADS) {
+      const int r = i / (npad / 4), c = (i - r * (npad / 4)) * 4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (u0 + r < U && c < N) v = *reinterpret_cast<const f32x4*>(user + (size_t)(u0 + r) * ld_user + c);
+      *reinterpret_cast<f32x4*>(sU + (size_t)r * ldu + c) = v;
+    }
+  }
+  // rows(r): address of chunk row r, nullptr = a row of zeros
+  template <class Rows>
+  __device__ __forceinline__ void load_slab(const Rows& rows, int ks) {
+    const int c = ks * TK_KS + scol;
+    g0 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    g1 = g0;
+    if (c < N) {
+      const float* p0 = rows(srow);
+      const float* p1 = rows(srow + 64);
+      if (p0) g0 = *reinterpret_cast<const f32x4*>(p0 + c);
+      if (p1) g1 = *reinterpret_cast<const f32x4*>(p1 + c);
+    }
+  }
+  __device__ __forceinline__ void store_slab(int buf) {
+    float* d = sB + (size_t)buf * TK_ROWS * TK_LDB + srow * TK_LDB + scol;
+    *reinterpret_cast<f32x4*>(d) = g0;
+    *reinterpret_cast<f32x4*>(d + 64 * TK_LDB) = g1;
+  }
+  // Scores of one chunk; slab 0 of it is in g0 / g1 (load_slab(rows, 0)) on entry.
+  // acc[i][r] = score of user i * 16 + 4 * (lane >> 4) + r, news row 16 * wave + (lane & 15) of the chunk
+  template <class Rows>
+  __device__ __forceinline__ void chunk(const Rows& rows, f32x4 (&acc)[MT]) {
+    store_slab(0);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ++ks) {
+      if (ks + 1 < ksteps) load_slab(rows, ks + 1);
+      const float* pb = sB + (size_t)(ks & 1) * TK_ROWS * TK_LDB + (wave * 16 + frow) * TK_LDB + fk;
+      const f32x4 b0 = *reinterpret_cast<const f32x4*>(pb), b1 = *reinterpret_cast<const f32x4*>(pb + 4);
+      f32x4 a0[MT], a1[MT];
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const float* pa = sU + (size_t)(i * 16 + frow) * ldu + ks * TK_KS + fk;
+        a0[i] = *reinterpret_cast<const f32x4*>(pa);
+        a1[i] = *reinterpret_cast<const f32x4*>(pa + 4);
+      }
+      // sub-step e contracts columns ks * 32 + 8 * g + e, g = 0 .. 3 in the MFMA's own order: the same chain for every (u, v)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i][e], b0[e], acc[i], 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][e], b1[e], acc[i], 0, 0, 0);
+      if (ks + 1 < ksteps) store_slab((ks + 1) & 1);
+      __syncthreads();
+    }
+  }
+  // The chunk's scores into the LDS tile (it overlays the staging buffers), so that ONE wave sees all 128 scores of a user:
+  // score of tile user ul, chunk row r at scores()[ul * TK_LDS_TILE + r].  A __syncthreads() must follow the readers.
+  __device__ __forceinline__ void put_scores(const f32x4 (&acc)[MT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sB[(i * 16 + 4 * (lane >> 4) + r) * TK_LDS_TILE + wave * 16 + frow] = acc[i][r];
+    __syncthreads();
+  }
+  __device__ __forceinline__ const float* scores() const { return sB; }
+};
+
+}  // namespace

@@ -1,6 +1,8 @@
 // Full-corpus top-k recommendation: score[u, v] = <news_vecs[v], user[u]> over the WHOLE news table and, per user, the k best
 // news under the total order (score descending, news id ascending) -- without the [U, V] score matrix ever existing.
 //
+// The scoring tile (ScoreTile<MT>) is nr_score_tile.h, shared with the rank counting of nr_rank.hip: one definition, one set of bits.
+//
 //   topk_select_kernel<MT>  grid = user tiles x corpus slices, 8 waves.  A workgroup keeps its TU = 16 * MT users' vectors in
 //                           LDS and streams its slice of the table through LDS in chunks of 128 news rows (k-slabs of 32
 //                           columns, double buffered through registers).  Wave w forms the [TU x 16] score tile of news rows
@@ -16,28 +18,14 @@
 // A candidate is one 64-bit key: (order-preserving image of the score) << 32 | ~id.  Larger key = better; key 0 = "nothing"
 // (NaN scores map to it and are never kept; it decodes to id 0, score -inf, the fill of a short row).  Ids of a slice arrive in
 // ascending order, so a score that only TIES the threshold can never displace a kept one: the fast test is a strict >.
-#include "nr_common.h"
+#include "nr_score_tile.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int TK_THREADS = 512;
-constexpr int TK_WAVES = TK_THREADS / 64;
-constexpr int TK_ROWS = 128;        // news rows per chunk = 16 per wave
-constexpr int TK_KS = 32;           // columns per k-slab
-constexpr int TK_LDB = TK_KS + 4;   // slab row stride: 16 rows at one column land in 16 different 4-bank groups
-constexpr int TK_LDS_TILE = TK_ROWS + 4;
-constexpr int TK_STAGE_FLOATS = 2 * TK_ROWS * TK_LDB;   // two slabs; the score tile [TU, TK_LDS_TILE] lives in the same bytes
-constexpr size_t TK_LDS_MAX = 160 * 1024;
-constexpr int TK_CUS = 256;         // MI355X; the slice count is host arithmetic (the workspace size depends on it)
 constexpr int TK_MERGE_MAX = 8192;  // candidates one merge workgroup sorts in LDS (64 KiB)
 
-static_assert(64 * TK_LDS_TILE <= TK_STAGE_FLOATS, "score tile must fit the staging buffers");
-
-__host__ __device__ inline int tk_npad(int N) { return (N + TK_KS - 1) / TK_KS * TK_KS; }
 inline size_t tk_lds_bytes(int TU, int N, int k) {
-  return ((size_t)TU * (tk_npad(N) + 4) + TK_STAGE_FLOATS) * sizeof(float) + (size_t)TU * k * sizeof(u64) + (size_t)TU * sizeof(uint32_t);
+  return tk_tile_floats(TU, N) * sizeof(float) + (size_t)TU * k * sizeof(u64) + (size_t)TU * sizeof(uint32_t);
 }
 inline int tk_user_tile(int N, int k) {
   for (int tu = 64; tu > 16; tu >>= 1)
@@ -55,14 +43,6 @@ inline int tk_auto_splits(int U, int V, int N, int k) {
   return s < 1 ? 1 : (int)s;
 }
 
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (!(s == s)) return 0u;
-  const uint32_t b = __float_as_uint(s + 0.0f);               // -0 -> +0: the two compare equal, so they share a key
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t key) {
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
 __device__ __forceinline__ u64 wave_min_u64(u64 v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -85,86 +65,29 @@ template <int MT>
 __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
   constexpr int TU = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
-  const int npad = tk_npad(a.N), ldu = npad + 4;
-  float* sU = tk_smem;                                  // [TU, ldu]   user vectors, zero beyond N and beyond U
-  float* sB = sU + (size_t)TU * ldu;                    // [2, TK_ROWS, TK_LDB] news slabs | [TU, TK_LDS_TILE] scores of a chunk
-  u64* sList = reinterpret_cast<u64*>(sB + TK_STAGE_FLOATS);   // [TU, k]  candidates, 0 = empty
+  ScoreTile<MT> t(tk_smem, a.N);                         // scoring tile: nr_score_tile.h
+  u64* sList = reinterpret_cast<u64*>(t.end());          // [TU, k]  candidates, 0 = empty
   uint32_t* sThr = reinterpret_cast<uint32_t*>(sList + (size_t)TU * a.k);   // [TU]  score key of the worst candidate (0: not full)
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
   const int u0 = blockIdx.x * TU;
   const long v_lo = 1 + (long)blockIdx.y * a.per;
   const long v_hi = v_lo + a.per < a.V ? v_lo + a.per : a.V;
 
-  for (int i = tid; i < TU * (npad / 4); i += TK_THREADS) {
-    const int r = i / (npad / 4), c = (i - r * (npad / 4)) * 4;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (u0 + r < a.U && c < a.N) v = *reinterpret_cast<const f32x4*>(a.user + (size_t)(u0 + r) * a.ld_user + c);
-    *reinterpret_cast<f32x4*>(sU + (size_t)r * ldu + c) = v;
-  }
+  t.load_users(a.user, a.ld_user, u0, a.U);
   for (int i = tid; i < TU * a.k; i += TK_THREADS) sList[i] = 0ull;
   if (tid < TU) sThr[tid] = 0u;
 
-  // staging: thread -> rows (tid >> 3) and (tid >> 3) + 64 of the chunk, columns 4 * (tid & 7) .. + 3 of the slab
-  const int srow = tid >> 3, scol = (tid & 7) * 4;
-  const int ksteps = npad / TK_KS;
-  f32x4 g0, g1;
-  auto load_slab = [&](long vc, int ks) {
-    const int c = ks * TK_KS + scol;
-    const long r0 = vc + srow, r1 = r0 + 64;
-    g0 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    g1 = g0;
-    if (c < a.N) {
-      if (r0 < v_hi) g0 = *reinterpret_cast<const f32x4*>(a.news + (size_t)r0 * a.ld_news + c);
-      if (r1 < v_hi) g1 = *reinterpret_cast<const f32x4*>(a.news + (size_t)r1 * a.ld_news + c);
-    }
-  };
-  auto store_slab = [&](int buf) {
-    float* d = sB + (size_t)buf * TK_ROWS * TK_LDB + srow * TK_LDB + scol;
-    *reinterpret_cast<f32x4*>(d) = g0;
-    *reinterpret_cast<f32x4*>(d + 64 * TK_LDB) = g1;
-  };
-
-  const int frow = lane & 15, fk = (lane >> 4) * 8;
-  if (v_lo < v_hi) load_slab(v_lo, 0);
+  ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
+  if (v_lo < v_hi) t.load_slab(rows, 0);
   for (long vc = v_lo; vc < v_hi; vc += TK_ROWS) {
-    store_slab(0);
-    __syncthreads();
     f32x4 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < ksteps; ++ks) {
-      if (ks + 1 < ksteps) load_slab(vc, ks + 1);
-      const float* pb = sB + (size_t)(ks & 1) * TK_ROWS * TK_LDB + (wave * 16 + frow) * TK_LDB + fk;
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(pb), b1 = *reinterpret_cast<const f32x4*>(pb + 4);
-      f32x4 a0[MT], a1[MT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        const float* pa = sU + (size_t)(i * 16 + frow) * ldu + ks * TK_KS + fk;
-        a0[i] = *reinterpret_cast<const f32x4*>(pa);
-        a1[i] = *reinterpret_cast<const f32x4*>(pa + 4);
-      }
-      // sub-step e contracts columns ks * 32 + 8 * g + e, g = 0 .. 3 in the MFMA's own order: the same chain for every (u, v)
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i][e], b0[e], acc[i], 0, 0, 0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][e], b1[e], acc[i], 0, 0, 0);
-      if (ks + 1 < ksteps) store_slab((ks + 1) & 1);
-      __syncthreads();
-    }
-    if (vc + TK_ROWS < v_hi) load_slab(vc + TK_ROWS, 0);      // in flight while this chunk is selected from
-
-    // acc[i][r] = score of user i * 16 + 4 * (lane >> 4) + r, news row 16 * wave + (lane & 15) of the chunk
-    float* sS = sB;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sS[(i * 16 + 4 * (lane >> 4) + r) * TK_LDS_TILE + wave * 16 + frow] = acc[i][r];
-    __syncthreads();
+    rows.vc = vc;
+    t.chunk(rows, acc);
+    rows.vc = vc + TK_ROWS;
+    if (rows.vc < v_hi) t.load_slab(rows, 0);                 // in flight while this chunk is selected from
+    t.put_scores(acc);
+    const float* sS = t.scores();
 
     const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
     for (int ul = wave; ul < TU && u0 + ul < a.U; ul += TK_WAVES) {

@@ -1,4 +1,5 @@
-"""Ranking metrics of the eval loop (src/metrics.py:1-29, src/main.py:255-258): per-impression AUC / MRR / nDCG@k.
+"""Ranking metrics of the eval loop (src/metrics.py:1-29, src/main.py:255-258): per-impression AUC / MRR / nDCG@k, and the host
+statements of the full-corpus contracts (top-k, rank, retrieval metrics).
 Own numpy implementation; AUC is the rank statistic (average ranks for ties) that sklearn's roc_auc_score computes."""
 import numpy as np
 
@@ -67,3 +68,62 @@ def topk_reference(a, b=None, *, k, exclude=None):
         ids[u, :len(order)] = order
         out[u, :len(order)] = scores[u, order]
     return ids, out
+
+
+def rank_reference(a, b=None, *, targets, exclude=None):
+    """Host statement of the full-corpus rank contract (include/nrhip.h, nr_score_rank); tests check the device against it, no
+    product path calls it.
+
+    `a`, `b`, `exclude` and the total order (score descending, news id ascending) are topk_reference's.  targets [U, T] int:
+    entries that are 0 or outside [1, V) mean nothing.  The eligible news of user u are the ids 1 .. V-1 that are not in
+    exclude[u] and whose score is not NaN; rank[u, j] is the 1-based position of targets[u, j] among them in that order, and 0
+    ("not ranked") when the target means nothing, is excluded, has a NaN score or repeats an earlier entry of its row.
+    Returns (ranks int32 [U, T], scores float64 [U, T]); the score is -inf where the rank is 0."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    targets = np.asarray(targets, dtype=np.int64)
+    U, V = scores.shape
+    T = targets.shape[1]
+    ranks = np.zeros((U, T), dtype=np.int32)
+    out = np.full((U, T), -np.inf, dtype=np.float64)
+    for u in range(U):
+        ok = ~np.isnan(scores[u])
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        cand = np.flatnonzero(ok)
+        order = cand[np.lexsort((cand, -scores[u, cand]))]
+        place = np.zeros(V, dtype=np.int64)
+        place[order] = np.arange(1, len(order) + 1)
+        seen = set()
+        for j in range(T):
+            t = int(targets[u, j])
+            if 1 <= t < V and t not in seen and place[t] > 0:
+                ranks[u, j], out[u, j] = place[t], scores[u, t]
+            seen.add(t)
+    return ranks, out
+
+
+def retrieval_metrics_reference(ranks, ks):
+    """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked), and their sums over the
+    users with n_u >= 1 ranked targets:
+      MRR_u = mean_j 1 / rank;  Recall@k_u = #{rank <= k} / n_u;
+      nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1)  /  sum_{i = 1 .. min(n_u, k)} 1 / log2(i + 1)
+    -- mrr_score / ndcg_score above applied to the user's whole eligible corpus row with binary labels.
+    Returns (per_user float64 [U, 2 + 2 len(ks)], sums float64 [2 + 2 len(ks)]): column 0 is 1 for a counted user, column 1
+    MRR_u, then Recall@k_u, nDCG@k_u per k; the row of a user without a ranked target is zero."""
+    ranks = np.asarray(ranks, dtype=np.int64)
+    ks = [int(k) for k in ks]
+    per_user = np.zeros((ranks.shape[0], 2 + 2 * len(ks)), dtype=np.float64)
+    for u, row in enumerate(ranks):
+        r = row[row > 0].astype(np.float64)
+        n = len(r)
+        if n == 0:
+            continue
+        per_user[u, 0], per_user[u, 1] = 1.0, np.sum(1.0 / r) / n
+        for i, k in enumerate(ks):
+            hit = r[r <= k]
+            per_user[u, 2 + 2 * i] = len(hit) / n
+            per_user[u, 3 + 2 * i] = np.sum(1.0 / np.log2(hit + 1.0)) / np.sum(1.0 / np.log2(np.arange(min(n, k)) + 2.0))
+    return per_user, per_user.sum(axis=0)

@@ -1029,6 +1029,54 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0):
     return ids, scores
 
 
+@torch.no_grad()
+def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0):
+    """Full-corpus rank evaluation (nr_score_rank): for every user and each of its targets ([U, T <= 64] news ids, 0 = no entry)
+    the exact 1-based position of that news among the user's eligible news of the whole table, in score_topk's order and with
+    score_topk's score bits: 1 <= rank <= k exactly when the target is in the user's top-k row.  Rank 0, score -inf: the target
+    is 0 or out of range, is in `exclude` ([U, E <= 64]), has a NaN score or repeats an earlier entry of its row.  No [U, V]
+    score matrix is formed.  Returns (ranks int32 [U, T], scores fp32 [U, T], sums): with cut-offs `ks` (at most 8) sums is a
+    DEVICE fp64 tensor [2 + 2 len(ks)] = [users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u]
+    (metrics.retrieval_metrics_reference states the per-user terms); with ks=None no sums are formed and None is returned.
+    `splits`: 0 = the library chooses the number of corpus slices; tests force it."""
+    _need_gpu(news_vecs, user_vecs, targets, exclude)
+    for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"score_rank: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
+                               f"strides {tuple(t.stride())}")
+    V, N = news_vecs.shape
+    U = user_vecs.shape[0]
+    if user_vecs.shape[1] != N:
+        raise RuntimeError(f"score_rank: vector widths differ ({N} vs {user_vecs.shape[1]})")
+    if targets.dim() != 2 or targets.shape[0] != U:
+        raise RuntimeError(f"score_rank: targets must be [U = {U}, T], got {tuple(targets.shape)}")
+    T = targets.shape[1]
+    dev = news_vecs.device
+    want_sums = ks is not None
+    ks = [int(k) for k in (ks or ())]
+    ranks = torch.empty(U, T, dtype=torch.int32, device=dev)
+    scores = torch.empty(U, T, dtype=torch.float32, device=dev)
+    if U == 0:
+        return ranks, scores, torch.zeros(2 + 2 * len(ks), dtype=torch.float64, device=dev) if want_sums else None
+    sums = torch.empty(2 + 2 * len(ks), dtype=torch.float64, device=dev) if want_sums else None     # the call overwrites it
+    tg = targets.detach().to(torch.int32).contiguous()
+    ex, E = None, 0
+    if exclude is not None:
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"score_rank: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        E = exclude.shape[1]
+        ex = exclude.detach().to(torch.int32).contiguous() if E else None
+    ks_host = (C.c_int * max(len(ks), 1))(*ks)
+    d = _lib.RankDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, exclude=ptr(ex),
+                      ld_exclude=E, E=E, splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
+                      out_sums=ptr(sums))
+    ws = _ws(_lib.lib().nr_score_rank_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_rank(C.byref(d), _stream()), "nr_score_rank")
+    return ranks, scores, sums
+
+
 def stack_rows(a, b, mask_b=None, flags=True):
     """[a ; b] of two int32 id matrices with the same row width (candidate titles, then history titles) and, if asked, the int32
     "needed" flags [1 .. 1 ; mask_b != 0] of the stacked rows -- one launch (nr_stack_rows)."""

@@ -338,6 +338,99 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     return ops.score_topk(news_vecs, user, k, exclude=exclude)
 
 
+def _retrieval_sums(ranks, ks):
+    """[users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u] in fp64 from ranks [U, T] (0 = not
+    ranked): metrics.retrieval_metrics_reference as tensor arithmetic on the device of `ranks`."""
+    pos = ranks > 0
+    r = ranks.double().clamp(min=1.0)
+    n = pos.sum(1)
+    nd = n.clamp(min=1).double()
+    counted = (n > 0).double()
+    out = [counted.sum(), (torch.where(pos, 1.0 / r, torch.zeros_like(r)).sum(1) / nd * counted).sum()]
+    ideal = torch.cumsum(1.0 / torch.log2(torch.arange(ranks.shape[1], device=ranks.device).double() + 2.0), 0)
+    for k in ks:
+        hit = pos & (ranks <= int(k))
+        dcg = torch.where(hit, 1.0 / torch.log2(r + 1.0), torch.zeros_like(r)).sum(1)
+        idcg = ideal[(torch.minimum(n, torch.full_like(n, int(k))).clamp(min=1) - 1)]
+        out += [(hit.sum(1).double() / nd * counted).sum(), (dcg / idcg * counted).sum()]
+    return torch.stack(out)
+
+
+@torch.no_grad()
+def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclude_history=True, batch_size=8192):
+    """Full-corpus retrieval evaluation: where does each held-out click of a user stand in that user's ranking of the WHOLE
+    table `news_vecs`?  hist_idx, mask, exclude_history and the user vectors are recommend's (_user_vectors; of a history wider
+    than 64 slots only the LAST 64 are excluded); targets [U, T]: the held-out news indices of every user, 0 = no entry.
+    Scoring and counting are one fused pass (ops.score_rank): no [U, V] score matrix, and the ranks agree with recommend's
+    rows exactly (1 <= rank <= k exactly when the target is in the user's top-k row).
+    Returns (ranks int32 [U, T], scores fp32 [U, T], sums fp64 [2 + 2 len(ks)]) on the device: rank 0 / score -inf for an entry
+    that is 0 or out of range, excluded (a clicked news under exclude_history), NaN-scored or a repeat of an earlier entry;
+    sums = [users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u].
+    More than 64 targets per user: the kernel takes 64 per row, so such a user's non-zero targets (later repeats dropped first)
+    are laid over several rows that share its user vector and exclusion list -- a rank only depends on the user vector, the
+    exclusions and the target itself, so the rows rank independently and exactly.  The user's metric terms, which need all its
+    ranks at once (n_u, the ideal DCG), are then formed here from the gathered ranks in fp64 tensor arithmetic instead of in
+    the kernel's finalize pass; the formulas are the same (metrics.retrieval_metrics_reference).
+    Several ranks: the caller shards the users and the sums add; there is no collective."""
+    device = news_vecs.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
+    news_vecs = news_vecs.detach().float().contiguous()
+    user = _user_vectors(model, news_vecs, hist, m, batch_size, device, _Histories(mask))
+    exclude = None
+    if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
+        exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
+    U, T = tg.shape
+    W = _lib.NR_RANK_MAX_TARGETS
+    if T <= W or U == 0:
+        return ops.score_rank(news_vecs, user, tg, exclude=exclude, ks=ks)
+    # later repeats -> 0 (stable sort by id: the first of equal ids is the earliest entry), then the non-zero entries to the front
+    srt, at = torch.sort(tg, dim=1, stable=True)
+    rep = torch.zeros_like(tg, dtype=torch.bool)
+    rep[:, 1:] = srt[:, 1:] == srt[:, :-1]
+    tg = tg.masked_fill(torch.zeros_like(rep).scatter(1, at, rep), 0)
+    order = torch.argsort((tg == 0).to(torch.int8), dim=1, stable=True)
+    comp = tg.gather(1, order)
+    n_rows = (((tg != 0).sum(1) + W - 1) // W).clamp(min=1)
+    row_user = torch.repeat_interleave(torch.arange(U, device=device), n_rows)
+    block = torch.arange(row_user.numel(), device=device) - (torch.cumsum(n_rows, 0) - n_rows)[row_user]
+    cols = block[:, None] * W + torch.arange(W, device=device)[None, :]
+    live = cols < T
+    cols = cols.clamp(max=T - 1)
+    row_tg = (comp[row_user[:, None], cols] * live).contiguous()
+    r, sc, _ = ops.score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=None if exclude is None else exclude[row_user].contiguous(),
+                              ks=None)
+    ranks_c = torch.zeros(U, T, dtype=torch.int32, device=device)
+    scores_c = torch.full((U, T), float("-inf"), dtype=torch.float32, device=device)
+    ru = row_user[:, None].expand_as(cols)
+    ranks_c[ru[live], cols[live]] = r[live]
+    scores_c[ru[live], cols[live]] = sc[live]
+    ranks = torch.zeros_like(ranks_c).scatter(1, order, ranks_c)
+    scores = torch.zeros_like(scores_c).scatter(1, order, scores_c)
+    return ranks, scores, _retrieval_sums(ranks, ks)
+
+
+def _shard_targets(shard: IndexedTestShard):
+    """The clicked candidates of every impression of a shard, cand[label == 1] per CSR row in list order, as one int32 array
+    [n, T] (T = the most clicks of an impression, at least 1), rows back padded with 0."""
+    n = len(shard)
+    clicked = shard.label == 1
+    imp = np.repeat(np.arange(n), np.diff(shard.offsets))[clicked]
+    per = np.bincount(imp, minlength=n)
+    out = np.zeros((n, max(int(per.max()) if n else 0, 1)), dtype=np.int32)
+    start = np.cumsum(per) - per
+    out[imp, np.arange(len(imp)) - start[imp]] = shard.cand[clicked]
+    return out
+
+
+@torch.no_grad()
+def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100)):
+    """rank_eval over the impressions of a test shard: every impression is one user (its history), its targets are the news it
+    clicked, cand[label == 1] per CSR row in list order, rows back padded with 0.  Returns rank_eval's (ranks, scores, sums)."""
+    return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks)
+
+
 @torch.no_grad()
 def test(rank, args, model, news_index, news_combined, log=logging.info, collect_scores=None, device=None, score_fn=None):
     """One rank of the evaluation job (src/main.py:145-277) on `behaviors_{rank}.tsv`.

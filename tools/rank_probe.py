@@ -1,0 +1,141 @@
+#!/usr/bin/env python
+"""Full-corpus rank evaluation: the fused call (ops.score_rank) against torch.matmul in user blocks + (scores > target).sum on
+the same device.
+
+    python tools/rank_probe.py [--news 100001] [--dim 400] [--targets 4] [--exclude 50] [--users 64 8192] [--block 1024]
+                               [--calls 30] [--warmup 5] [--out FILE]
+
+Both sides take the same fp32 inputs.  The baseline forms the [block, V] scores of a block of users, reads the targets' scores
+out of them and counts, per target, the news that score strictly higher (what the excluded ones contribute is taken back from
+the gathered excluded scores); it leaves out the tie rule, the duplicate handling and the metric sums, all of which the fused
+call does.  Per U: every call is timed with a pair of device events, the two sides alternate call by call (so that a
+disturbance of the machine hits both), and the median, minimum, maximum and inter-quartile spread of the timed calls are
+reported, with the peak device memory of one call above what the inputs occupy.  The fused side's share of the fp32 MFMA peak
+counts the algorithmic 2 * U * V * N FLOPs over the WHOLE call (all launches), against 157.3 TFLOP/s.
+One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from newsrecommendation_amd import ops  # noqa: E402
+
+PEAK_FP32_MATRIX = 157.3e12
+KS = (5, 10, 100)
+
+
+def fused(news, user, targets, exclude, block):
+    return ops.score_rank(news, user, targets, exclude=exclude, ks=KS)
+
+
+def baseline(news, user, targets, exclude, block):
+    ranks = torch.empty(targets.shape, dtype=torch.int64, device=targets.device)
+    for a in range(0, user.shape[0], block):
+        sc = torch.matmul(user[a:a + block], news.T)                          # [block, V]
+        sc[:, 0] = float("-inf")                                              # row 0 is the padding news
+        t = sc.gather(1, targets[a:a + block].long())                         # [block, T]
+        x = sc.gather(1, exclude[a:a + block].long())                         # [block, E]
+        above = torch.stack([(sc > t[:, j:j + 1]).sum(1) for j in range(t.shape[1])], 1)
+        ranks[a:a + block] = 1 + above - (x[:, None, :] > t[:, :, None]).sum(2)
+    return ranks
+
+
+def timed(fn, *a):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn(*a)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def peak_bytes(fn, *a):
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    out = fn(*a)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - before
+    del out
+    return int(peak)
+
+
+def stats(ms):
+    a = np.asarray(ms)
+    q1, med, q3 = np.percentile(a, [25, 50, 75])
+    return {"median_ms": round(float(med), 4), "min_ms": round(float(a.min()), 4), "max_ms": round(float(a.max()), 4),
+            "iqr_ms": round(float(q3 - q1), 4), "calls": len(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--news", type=int, default=100001)
+    ap.add_argument("--dim", type=int, default=400)
+    ap.add_argument("--targets", type=int, default=4)
+    ap.add_argument("--exclude", type=int, default=50)
+    ap.add_argument("--users", type=int, nargs="+", default=[64, 8192])
+    ap.add_argument("--block", type=int, default=1024, help="users per matmul of the baseline")
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rank_probe needs a GPU")
+    if args.calls < 20:
+        raise SystemExit("at least 20 timed calls")
+    g = torch.Generator().manual_seed(0)
+    news = (torch.randn(args.news, args.dim, generator=g) * 0.4).cuda()
+    lines = []
+    for U in args.users:
+        user = (torch.randn(U, args.dim, generator=g) * 0.4).cuda()
+        # distinct ids per user: the first T are the targets, the next E the excluded ones (no target is excluded)
+        # (a random start per user, then steps of a prime that shares no factor with V - 1 = 2^5 5^5 at the default size)
+        n_named, step = args.targets + args.exclude, 7919
+        if np.gcd(step, args.news - 1) != 1 or n_named >= args.news - 1:
+            raise SystemExit(f"--news - 1 must share no factor with {step} and exceed targets + exclude")
+        start = torch.randint(0, args.news - 1, (U, 1), generator=g)
+        named = ((start + torch.arange(n_named)[None, :] * step) % (args.news - 1) + 1).to(torch.int32).cuda()
+        targets, exclude = named[:, :args.targets].contiguous(), named[:, args.targets:].contiguous()
+        a = (news, user, targets, exclude, min(args.block, U))
+        for _ in range(args.warmup):
+            fused(*a)
+            baseline(*a)
+        torch.cuda.synchronize()
+        t_f, t_b = [], []
+        for _ in range(args.calls):
+            t_f.append(timed(fused, *a))
+            t_b.append(timed(baseline, *a))
+        r_f = fused(*a)[0].long()
+        r_b = baseline(*a)
+        row = {"U": U, "V": args.news, "N": args.dim, "T": args.targets, "E": args.exclude, "block": a[4], "fused": stats(t_f),
+               "baseline": stats(t_b), "fused_peak_bytes": peak_bytes(fused, *a), "baseline_peak_bytes": peak_bytes(baseline, *a),
+               "score_block_bytes": a[4] * args.news * 4,
+               "ranks_equal_fraction": round(float((r_f == r_b).float().mean()), 6),
+               "max_rank_diff": int((r_f - r_b).abs().max())}
+        flops = 2.0 * U * args.news * args.dim
+        row["fused_tflops"] = round(flops / (row["fused"]["median_ms"] * 1e-3) / 1e12, 2)
+        row["fused_fraction_of_fp32_mfma_peak"] = round(row["fused_tflops"] * 1e12 / PEAK_FP32_MATRIX, 4)
+        row["baseline_tflops"] = round(flops / (row["baseline"]["median_ms"] * 1e-3) / 1e12, 2)
+        lines.append(row)
+        print(json.dumps(row), flush=True)
+        del user
+    last = lines[-1]
+    spread = max(last["fused"]["iqr_ms"], last["baseline"]["iqr_ms"])
+    verdict = {"U": last["U"], "spread_ms": spread,
+               "time_ok": last["fused"]["median_ms"] <= last["baseline"]["median_ms"] + spread,
+               "memory_ok": last["baseline_peak_bytes"] - last["fused_peak_bytes"] >= last["score_block_bytes"]}
+    lines.append(verdict)
+    print(json.dumps(verdict), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.writelines(json.dumps(r) + "\n" for r in lines)
+
+
+if __name__ == "__main__":
+    main()
