@@ -390,7 +390,18 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  *   splits   0: the library chooses (fills the chip for few users, 1-2 for many); > 0: that many slices, at most
  *            min(256, 8192 / k)
  *   ws       nr_score_topk_workspace_bytes(d) bytes, 8-byte aligned (the query reads U, V, N, k, splits only; 0 = bad
- *            descriptor, see nr_last_error)                                                                        */
+ *            descriptor, see nr_last_error)
+ * Pools (optional; all zero = off, and the call is then the one it was before they existed, bit for bit).  Shared with
+ * nr_score_rank, one definition (pool_key, csrc/nr_score_tile.h):
+ *   prior    [V] fp32.  score[u, v] = fl32(dot[u, v] + prior[v]): dot is the finished fmaf chain above, its bits unchanged;
+ *            the prior is ONE separate fp32 add after it, not a chain step and not contracted into an fma.  out_scores are
+ *            these sums.  prior[v] == -inf makes news v ineligible for every user (the global pool switch); a NaN prior gives
+ *            a NaN score, which falls under the NaN rule above; any other value just follows the arithmetic.
+ *   stamp    [V] int32 and window [U, 2] int32 (row stride ld_window >= 2): news v is eligible for user u only if
+ *            window[u, 0] <= stamp[v] <= window[u, 1], both ends inclusive.  lo > hi is an empty pool: the row is all fill.
+ *            The two come together: one without the other is refused.
+ * Eligible then means all of: id in [1, V), id not in exclude[u], score not NaN, prior not -inf, stamp inside the window.
+ * Order, fill and the independence of `splits` are unchanged; the workspace size does not depend on these fields.      */
 #define NR_TOPK_MAX_K 128
 #define NR_TOPK_MAX_N 1024
 #define NR_TOPK_MAX_EXCLUDE 64
@@ -407,6 +418,10 @@ typedef struct {
   float* out_scores;
   void* ws;
   size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
 } nr_topk_desc;
 size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d);
 int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
@@ -436,7 +451,12 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
  *   ws          nr_score_rank_workspace_bytes(d) bytes, 8-byte aligned (the query reads U, V, N, T, E, n_ks, ks, splits; 0 = bad
  *               descriptor, see nr_last_error): O(U * T * splits), no [U, V] buffer exists anywhere
  * Three launches (+ one for out_sums): the scores of the named ids (targets and excluded news, gathered rows through the same
- * MFMA tile), the counting pass over user tiles x corpus slices, and a per-user finalize.                              */
+ * MFMA tile), the counting pass over user tiles x corpus slices, and a per-user finalize.
+ * Pools: prior, stamp, window, ld_window exactly as in nr_topk_desc (all zero = off: the call as it was, bit for bit; one
+ * of stamp / window without the other is refused).  The score is fl32(dot + prior), the eligible news are additionally those
+ * whose prior is not -inf and whose stamp lies in the user's window, and a target outside its user's pool is "not ranked":
+ * rank 0, score -inf.  An excluded id that is itself outside the pool takes nothing off a rank (it was never counted).  The
+ * statement "1 <= rank <= k exactly when the target is at place rank - 1 of the top-k row" holds for equal pool inputs.   */
 #define NR_RANK_MAX_TARGETS 64
 #define NR_RANK_MAX_KS 8
 typedef struct {
@@ -457,6 +477,10 @@ typedef struct {
   double* out_sums;
   void* ws;
   size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
 } nr_rank_desc;
 size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d);
 int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream);

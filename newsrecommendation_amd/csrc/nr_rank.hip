@@ -75,6 +75,7 @@ struct RankArgs {
   RankWs w;
   size_t ld_news, ld_user, ld_tgt, ld_excl;
   int V, U, N, T, E, splits, per;
+  PoolArgs pool;        // read by the POOL instantiations only
 };
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -101,6 +102,9 @@ struct RankNamedRows {
   }
 };
 
+// POOL (both kernels): the call has a prior and / or stamps + windows; every key then comes from pool_key (nr_score_tile.h), as
+// in topk_select_kernel<MT, true>.  A call without them launches the <false> kernels, the code as it was before pools existed.
+template <bool POOL>
 __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
   ScoreTile<1> t(rk_smem, a.N);
@@ -136,8 +140,19 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
       const size_t u = (size_t)(u0 + c);
       const int32_t tg = sIds[c * TK_ROWS + lane], ex = sIds[c * TK_ROWS + RK_SLOTS + lane];
       const bool t_in = lane < a.T && tg >= 1 && tg < a.V, x_in = lane < a.E && ex >= 1 && ex < a.V;
-      const u64 kt = news_key(t.scores()[c * TK_LDS_TILE + lane], (uint32_t)tg);
-      const u64 kx = news_key(t.scores()[c * TK_LDS_TILE + RK_SLOTS + lane], (uint32_t)ex);
+      u64 kt, kx;
+      if constexpr (POOL) {
+        // prior and stamp gathered by id: the named news get the key the stream gives them -- 0 outside the user's pool.  Such a
+        // target is not ranked; such an excluded news was never counted by the stream, so it must not be taken back either.
+        const int32_t lo = a.pool.lo_of(u), hi = a.pool.hi_of(u);
+        const uint32_t st = t_in ? pool_key(t.scores()[c * TK_LDS_TILE + lane], a.pool.prior_of(tg), a.pool.stamp_of(tg), lo, hi) : 0u;
+        const uint32_t sx = x_in ? pool_key(t.scores()[c * TK_LDS_TILE + RK_SLOTS + lane], a.pool.prior_of(ex), a.pool.stamp_of(ex), lo, hi) : 0u;
+        kt = ((u64)st << 32) | (uint32_t)~(uint32_t)tg;
+        kx = ((u64)sx << 32) | (uint32_t)~(uint32_t)ex;
+      } else {
+        kt = news_key(t.scores()[c * TK_LDS_TILE + lane], (uint32_t)tg);
+        kx = news_key(t.scores()[c * TK_LDS_TILE + RK_SLOTS + lane], (uint32_t)ex);
+      }
       bool ranked = t_in && (kt >> 32) != 0;                  // a NaN score has key 0
       bool x_counts = x_in && (kx >> 32) != 0;                // a NaN news is never counted by the stream: nothing to take back
       for (int j = 0; j < RK_SLOTS; ++j) {
@@ -164,7 +179,7 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
   }
 }
 
-template <int MT>
+template <int MT, bool POOL>
 __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
   constexpr int TU = 16 * MT, PER_WAVE = TU / TK_WAVES;
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
@@ -186,6 +201,15 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
     tkey[i] = lane < n[i] ? a.w.keys[(size_t)u * a.T + lane] : ~0ull;
     cnt[i] = 0;
   }
+  // POOL: lane i keeps the window of this wave's i-th user; an empty one beyond U
+  int32_t w_lo = 1, w_hi = 0;
+  if constexpr (POOL) {
+    const int u = u0 + wave + TK_WAVES * lane;
+    if (lane < PER_WAVE && u < a.U) {
+      w_lo = a.pool.lo_of(u);
+      w_hi = a.pool.hi_of(u);
+    }
+  }
 
   ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
   if (v_lo < v_hi) t.load_slab(rows, 0);
@@ -195,6 +219,19 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
     t.chunk(rows, acc);
     rows.vc = vc + TK_ROWS;
     if (rows.vc < v_hi) t.load_slab(rows, 0);                 // in flight while this chunk is counted
+    // POOL: prior and stamp of the chunk's 128 news, two per lane, once per chunk and wave (coalesced; in flight over the barrier)
+    float p0 = 0.f, p1 = 0.f;
+    int32_t s0 = 0, s1 = 0;
+    if constexpr (POOL) {
+      if (vc + lane < v_hi) {
+        p0 = a.pool.prior_of(vc + lane);
+        s0 = a.pool.stamp_of(vc + lane);
+      }
+      if (vc + lane + 64 < v_hi) {
+        p1 = a.pool.prior_of(vc + lane + 64);
+        s1 = a.pool.stamp_of(vc + lane + 64);
+      }
+    }
     t.put_scores(acc);
     const float* sS = t.scores();
     const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
@@ -203,8 +240,16 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
       if (n[i] == 0) continue;
       const int ul = wave + TK_WAVES * i;
       // rows beyond the slice end get key 0; a NaN score gives 0 << 32 | ~id, below every target's key
-      const u64 k0 = lane < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane], (uint32_t)(vc + lane)) : 0ull;
-      const u64 k1 = lane + 64 < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane + 64], (uint32_t)(vc + lane + 64)) : 0ull;
+      u64 k0, k1;
+      if constexpr (POOL) {
+        // a news outside the user's pool gets 0 << 32 | ~id as well: it never beats a target
+        const int32_t lo = __builtin_amdgcn_readlane(w_lo, i), hi = __builtin_amdgcn_readlane(w_hi, i);
+        k0 = lane < nvalid ? ((u64)pool_key(sS[ul * TK_LDS_TILE + lane], p0, s0, lo, hi) << 32) | (uint32_t)~(uint32_t)(vc + lane) : 0ull;
+        k1 = lane + 64 < nvalid ? ((u64)pool_key(sS[ul * TK_LDS_TILE + lane + 64], p1, s1, lo, hi) << 32) | (uint32_t)~(uint32_t)(vc + lane + 64) : 0ull;
+      } else {
+        k0 = lane < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane], (uint32_t)(vc + lane)) : 0ull;
+        k1 = lane + 64 < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane + 64], (uint32_t)(vc + lane + 64)) : 0ull;
+      }
       for (int j = 0; j < n[i]; ++j) {
         const u64 tk = lane_u64(tkey[i], j);                  // strict >: the target never counts itself
         const int c = __popcll(__ballot(k0 > tk)) + __popcll(__ballot(k1 > tk));
@@ -297,6 +342,9 @@ int rank_check(const nr_rank_desc* d) {
   for (int i = 0; i < d->n_ks; ++i) NR_CHECK_ARG(d->ks[i] >= 1, "score_rank: cut-off k = %d at position %d, must be >= 1", d->ks[i], i);
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= RK_MAX_SPLITS, "score_rank: splits = %d, must be 0 (library's choice) or in [1, %d]", d->splits,
                RK_MAX_SPLITS);
+  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_rank: stamp given without window (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_rank: window given without stamp (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_rank: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
   return NR_OK;
 }
 
@@ -334,25 +382,36 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_tgt = (size_t)d->ld_targets; a.ld_excl = (size_t)d->ld_exclude;
   a.V = d->V; a.U = d->U; a.N = d->N; a.T = d->T; a.E = d->exclude != nullptr ? d->E : 0; a.splits = splits;
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
+  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  const bool pool = a.pool.any();
   {
     NrProfScope ps(s, "rank_named[U=%d,N=%d,T=%d,E=%d]", d->U, d->N, d->T, a.E);
     const size_t smem = rk_lds_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_named_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(rank_named_kernel, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+    const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true>) : reinterpret_cast<const void*>(rank_named_kernel<false>);
+    NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (pool) hipLaunchKernelGGL(rank_named_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+    else hipLaunchKernelGGL(rank_named_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
   }
   NR_CHECK_LAUNCH();
   {
     const size_t smem = rk_lds_bytes(TU, d->N);
     const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
     NrProfScope ps(s, "rank_count[U=%d,V=%d,N=%d,T=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->T, TU, splits);
-#define NR_RANK_LAUNCH(MT)                                                                                                                 \
+#define NR_RANK_LAUNCH(MT, POOL)                                                                                                           \
   do {                                                                                                                                     \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-    hipLaunchKernelGGL(rank_count_kernel<MT>, grid, dim3(TK_THREADS), smem, s, a);                                                        \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                     (int)smem));                                                                                          \
+    hipLaunchKernelGGL((rank_count_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a);                                                 \
   } while (0)
-    if (TU == 64) NR_RANK_LAUNCH(4);
-    else if (TU == 32) NR_RANK_LAUNCH(2);
-    else NR_RANK_LAUNCH(1);
+#define NR_RANK_LAUNCH_MT(MT)           \
+  do {                                  \
+    if (pool) NR_RANK_LAUNCH(MT, true); \
+    else NR_RANK_LAUNCH(MT, false);     \
+  } while (0)
+    if (TU == 64) NR_RANK_LAUNCH_MT(4);
+    else if (TU == 32) NR_RANK_LAUNCH_MT(2);
+    else NR_RANK_LAUNCH_MT(1);
+#undef NR_RANK_LAUNCH_MT
 #undef NR_RANK_LAUNCH
   }
   NR_CHECK_LAUNCH();

@@ -40,6 +40,29 @@ __device__ __forceinline__ float key_score(uint32_t key) {
   return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
 
+// Pools (per-news prior, per-news stamp against a per-user window): the ONE place where a finished dot product becomes the
+// final score of (u, v), as its key.  score = fl32(dot + prior): one separate fp32 add after the chain, never contracted into
+// it (__fadd_rn).  Key 0 = not eligible: a prior of -inf (the global pool switch), a stamp outside [lo, hi] (lo > hi: nobody),
+// or a NaN sum.  The selection, the counting stream and the named ids of the rank pass all come through here, so one (u, v)
+// has one key everywhere; key_score() of it is the score that is returned.
+__device__ __forceinline__ uint32_t pool_key(float dot, float prior, int32_t stamp, int32_t lo, int32_t hi) {
+  const bool in = prior != -__builtin_inff() && stamp >= lo && stamp <= hi;
+  return in ? score_key(__fadd_rn(dot, prior)) : 0u;
+}
+// The optional inputs of a pooled call and their neutral stand-ins: no prior = 0 (dot + 0 has dot's key), no stamps = every
+// stamp 0 inside every window [0, 0].
+struct PoolArgs {
+  const float* prior;       // [V] or null
+  const int32_t* stamp;     // [V] or null
+  const int32_t* window;    // [U, ld_win] (lo, hi) or null; given exactly when stamp is
+  size_t ld_win;
+  __device__ __forceinline__ float prior_of(long v) const { return prior != nullptr ? prior[v] : 0.f; }
+  __device__ __forceinline__ int32_t stamp_of(long v) const { return stamp != nullptr ? stamp[v] : 0; }
+  __device__ __forceinline__ int32_t lo_of(long u) const { return window != nullptr ? window[(size_t)u * ld_win] : 0; }
+  __device__ __forceinline__ int32_t hi_of(long u) const { return window != nullptr ? window[(size_t)u * ld_win + 1] : 0; }
+  bool any() const { return prior != nullptr || stamp != nullptr || window != nullptr; }
+};
+
 // chunk row r = news row vc + r of a table slice that ends at v_hi
 struct ScoreStreamRows {
   const float* news;

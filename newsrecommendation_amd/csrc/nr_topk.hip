@@ -13,6 +13,10 @@
 //                           compares them with that user's running k-th-best threshold and ballots; nothing passes in the
 //                           common case.  What passes is checked against the exclusion list and replaces the worst of
 //                           the user's k candidates (two per lane, in registers; a wave-wide minimum finds the next worst).
+//                           With a prior and / or stamps + windows (the POOL instantiation) a wave also reads the prior and
+//                           stamp of the chunk's 128 news once per chunk, and the keys come from pool_key (nr_score_tile.h):
+//                           fl32(dot + prior), 0 for a news outside the user's pool -- before the ballot, so everything after
+//                           it is unchanged.
 //   topk_merge_kernel       one workgroup per user: bitonic sort of the splits * k candidates in LDS, the first k written out.
 //
 // A candidate is one 64-bit key: (order-preserving image of the score) << 32 | ~id.  Larger key = better; key 0 = "nothing"
@@ -59,9 +63,12 @@ struct TopkArgs {
   u64* part;              // [U, splits, k]
   size_t ld_news, ld_user, ld_excl;
   int V, U, N, k, E, splits, per;
+  PoolArgs pool;          // read by the POOL instantiations only
 };
 
-template <int MT>
+// POOL: the call has a prior and / or stamps + windows; the keys then come from pool_key (nr_score_tile.h).  A call without
+// them launches <MT, false>, the kernel as it was before pools existed.
+template <int MT, bool POOL>
 __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
   constexpr int TU = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
@@ -78,6 +85,16 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
   for (int i = tid; i < TU * a.k; i += TK_THREADS) sList[i] = 0ull;
   if (tid < TU) sThr[tid] = 0u;
 
+  // POOL: lane i keeps the window of this wave's i-th user (tile user wave + 8 i); an empty one beyond U
+  int32_t w_lo = 1, w_hi = 0;
+  if constexpr (POOL) {
+    const int ul = wave + TK_WAVES * lane;
+    if (ul < TU && u0 + ul < a.U) {
+      w_lo = a.pool.lo_of(u0 + ul);
+      w_hi = a.pool.hi_of(u0 + ul);
+    }
+  }
+
   ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
   if (v_lo < v_hi) t.load_slab(rows, 0);
   for (long vc = v_lo; vc < v_hi; vc += TK_ROWS) {
@@ -86,13 +103,33 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
     t.chunk(rows, acc);
     rows.vc = vc + TK_ROWS;
     if (rows.vc < v_hi) t.load_slab(rows, 0);                 // in flight while this chunk is selected from
+    const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
+    // POOL: prior and stamp of the chunk's 128 news, two per lane, once per chunk and wave (coalesced; in flight over the barrier)
+    float p0 = 0.f, p1 = 0.f;
+    int32_t s0 = 0, s1 = 0;
+    if constexpr (POOL) {
+      if (lane < nvalid) {
+        p0 = a.pool.prior_of(vc + lane);
+        s0 = a.pool.stamp_of(vc + lane);
+      }
+      if (lane + 64 < nvalid) {
+        p1 = a.pool.prior_of(vc + lane + 64);
+        s1 = a.pool.stamp_of(vc + lane + 64);
+      }
+    }
     t.put_scores(acc);
     const float* sS = t.scores();
 
-    const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
-    for (int ul = wave; ul < TU && u0 + ul < a.U; ul += TK_WAVES) {
-      const uint32_t k0 = lane < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane]) : 0u;
-      const uint32_t k1 = lane + 64 < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane + 64]) : 0u;
+    for (int ul = wave, iu = 0; ul < TU && u0 + ul < a.U; ul += TK_WAVES, ++iu) {
+      uint32_t k0, k1;
+      if constexpr (POOL) {
+        const int32_t lo = __builtin_amdgcn_readlane(w_lo, iu), hi = __builtin_amdgcn_readlane(w_hi, iu);
+        k0 = lane < nvalid ? pool_key(sS[ul * TK_LDS_TILE + lane], p0, s0, lo, hi) : 0u;
+        k1 = lane + 64 < nvalid ? pool_key(sS[ul * TK_LDS_TILE + lane + 64], p1, s1, lo, hi) : 0u;
+      } else {
+        k0 = lane < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane]) : 0u;
+        k1 = lane + 64 < nvalid ? score_key(sS[ul * TK_LDS_TILE + lane + 64]) : 0u;
+      }
       uint32_t thr = sThr[ul];
       if (__ballot(k0 > thr || k1 > thr) == 0ull) continue;
       // slow path: this user's candidates in registers (slots lane and lane + 64; slots >= k can never be the minimum)
@@ -173,6 +210,9 @@ int topk_check(const nr_topk_desc* d) {
   NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_topk: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= tk_max_splits(d->k), "score_topk: splits = %d, must be 0 (library's choice) or in [1, %d] for k = %d",
                d->splits, tk_max_splits(d->k), d->k);
+  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_topk: stamp given without window (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_topk: window given without stamp (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_topk: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
   return NR_OK;
 }
 
@@ -208,18 +248,27 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_excl = (size_t)d->ld_exclude;
   a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.E = d->E; a.splits = splits;
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
+  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  const bool pool = a.pool.any();
   const size_t smem = tk_lds_bytes(TU, d->N, d->k);
   const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
   {
     NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
-#define NR_TOPK_LAUNCH(MT)                                                                                                                  \
+#define NR_TOPK_LAUNCH(MT, POOL)                                                                                                            \
   do {                                                                                                                                      \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-    hipLaunchKernelGGL(topk_select_kernel<MT>, grid, dim3(TK_THREADS), smem, s, a);                                                        \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                     (int)smem));                                                                                           \
+    hipLaunchKernelGGL((topk_select_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a);                                                 \
   } while (0)
-    if (TU == 64) NR_TOPK_LAUNCH(4);
-    else if (TU == 32) NR_TOPK_LAUNCH(2);
-    else NR_TOPK_LAUNCH(1);
+#define NR_TOPK_LAUNCH_MT(MT)      \
+  do {                             \
+    if (pool) NR_TOPK_LAUNCH(MT, true); \
+    else NR_TOPK_LAUNCH(MT, false);     \
+  } while (0)
+    if (TU == 64) NR_TOPK_LAUNCH_MT(4);
+    else if (TU == 32) NR_TOPK_LAUNCH_MT(2);
+    else NR_TOPK_LAUNCH_MT(1);
+#undef NR_TOPK_LAUNCH_MT
 #undef NR_TOPK_LAUNCH
   }
   NR_CHECK_LAUNCH();

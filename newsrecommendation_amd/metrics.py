@@ -43,7 +43,27 @@ def ctr_score(y_true, y_score, k=1):
     return np.mean(np.take(y_true, order[:k]))
 
 
-def topk_reference(a, b=None, *, k, exclude=None):
+def _pooled(scores, prior, stamp, window):
+    """The pools of the full-corpus contracts (include/nrhip.h, K9): the final float64 scores `dot + prior` and the [U, V] mask of
+    what prior and window leave eligible -- prior[v] != -inf (a NaN prior makes a NaN score: the NaN rule), and
+    window[u, 0] <= stamp[v] <= window[u, 1], both ends inclusive (lo > hi: nobody).  None = off."""
+    U, V = scores.shape
+    ok = np.ones((U, V), dtype=bool)
+    if prior is not None:
+        prior = np.asarray(prior, dtype=np.float64).reshape(V)
+        with np.errstate(invalid="ignore"):
+            scores = scores + prior[None, :]
+        ok &= ~np.isneginf(prior)[None, :]
+    if (stamp is None) != (window is None):
+        raise ValueError("stamp and window come together")
+    if stamp is not None:
+        stamp = np.asarray(stamp, dtype=np.int64).reshape(V)
+        window = np.asarray(window, dtype=np.int64).reshape(U, 2)
+        ok &= (window[:, :1] <= stamp[None, :]) & (stamp[None, :] <= window[:, 1:])
+    return scores, ok
+
+
+def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window=None):
     """Host statement of the full-corpus recommendation contract (include/nrhip.h, nr_score_topk); tests check the device
     against it, no product path calls it.
 
@@ -51,14 +71,17 @@ def topk_reference(a, b=None, *, k, exclude=None):
     are then <a[v], b[u]> in float64.  Per user the k best news in the total order (score descending, news id ascending):
     news 0 (the padding row) is never eligible, nor is an id listed in exclude[u] (entries that are 0 or outside [1, V) mean
     nothing, duplicates are allowed), nor a news whose score is NaN.  A row with fewer than k eligible news is filled with
-    id 0, score -inf.  Returns (ids int32 [U, k], scores float64 [U, k])."""
+    id 0, score -inf.  Returns (ids int32 [U, k], scores float64 [U, k]).
+    Pools: prior [V] is added to the scores (the returned scores are the sums) and -inf in it removes a news for everybody;
+    stamp [V] with window [U, 2] keeps for user u the news with window[u, 0] <= stamp[v] <= window[u, 1] (_pooled)."""
     a = np.asarray(a, dtype=np.float64)
     scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
     U, V = scores.shape
     ids = np.zeros((U, k), dtype=np.int32)
     out = np.full((U, k), -np.inf, dtype=np.float64)
     for u in range(U):
-        ok = ~np.isnan(scores[u])
+        ok = ~np.isnan(scores[u]) & pool[u]
         ok[0] = False
         if exclude is not None:
             ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
@@ -70,7 +93,7 @@ def topk_reference(a, b=None, *, k, exclude=None):
     return ids, out
 
 
-def rank_reference(a, b=None, *, targets, exclude=None):
+def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, window=None):
     """Host statement of the full-corpus rank contract (include/nrhip.h, nr_score_rank); tests check the device against it, no
     product path calls it.
 
@@ -78,16 +101,19 @@ def rank_reference(a, b=None, *, targets, exclude=None):
     entries that are 0 or outside [1, V) mean nothing.  The eligible news of user u are the ids 1 .. V-1 that are not in
     exclude[u] and whose score is not NaN; rank[u, j] is the 1-based position of targets[u, j] among them in that order, and 0
     ("not ranked") when the target means nothing, is excluded, has a NaN score or repeats an earlier entry of its row.
-    Returns (ranks int32 [U, T], scores float64 [U, T]); the score is -inf where the rank is 0."""
+    Returns (ranks int32 [U, T], scores float64 [U, T]); the score is -inf where the rank is 0.
+    Pools: prior, stamp, window as in topk_reference; a target outside its user's pool is not ranked, and an excluded id outside
+    it changes nothing (it was not eligible to begin with)."""
     a = np.asarray(a, dtype=np.float64)
     scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
     targets = np.asarray(targets, dtype=np.int64)
     U, V = scores.shape
     T = targets.shape[1]
     ranks = np.zeros((U, T), dtype=np.int32)
     out = np.full((U, T), -np.inf, dtype=np.float64)
     for u in range(U):
-        ok = ~np.isnan(scores[u])
+        ok = ~np.isnan(scores[u]) & pool[u]
         ok[0] = False
         if exclude is not None:
             ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)

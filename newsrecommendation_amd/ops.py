@@ -993,14 +993,39 @@ def score_eval(news_vecs, cand_ids, imp_of, user_vecs) -> torch.Tensor:
     return out
 
 
+def _pool_args(what, V, U, dev, prior, stamp, window):
+    """The optional pool inputs of score_topk / score_rank as the tensors the descriptor points at: prior fp32 [V], stamp int32
+    [V], window int32 [U, 2], contiguous, on `dev`; None stays None.  stamp and window come together (the library refuses one
+    without the other; so does this check, before anything is converted)."""
+    if (stamp is None) != (window is None):
+        raise RuntimeError(f"{what}: stamp and window come together (got {'stamp' if window is None else 'window'} alone)")
+    for name, t, shape, floating in (("prior", prior, (V,), True), ("stamp", stamp, (V,), False), ("window", window, (U, 2), False)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise RuntimeError(f"{what}: {name} must be a tensor of shape {shape}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        if t.device != dev:
+            raise RuntimeError(f"{what}: {name} is on {t.device}, the news vectors on {dev}")
+        if t.is_floating_point() != floating or t.is_complex() or t.dtype == torch.bool:
+            raise RuntimeError(f"{what}: {name} must be {'floating point' if floating else 'an integer tensor'}, got {t.dtype}")
+    p = None if prior is None else prior.detach().to(torch.float32).contiguous()
+    s = None if stamp is None else stamp.detach().to(torch.int32).contiguous()
+    w = None if window is None else window.detach().to(torch.int32).contiguous()
+    return p, s, w
+
+
 @torch.no_grad()
-def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0):
+def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stamp=None, window=None):
     """Full-corpus recommendation (nr_score_topk): for every user the k best news of the whole table under the order (score
     descending, news id ascending), score[u, v] = <news_vecs[v], user_vecs[u]> in exact fp32.  Row 0 of `news_vecs` (the
     padding news) is never returned; `exclude` ([U, E <= 64] news ids per user, 0 = no entry) neither.  No [U, V] score matrix
     is formed.  Returns (ids int32 [U, k], scores fp32 [U, k]); a row with fewer than k eligible news ends in id 0, score -inf.
-    `splits`: 0 = the library chooses the number of corpus slices; tests force it."""
-    _need_gpu(news_vecs, user_vecs, exclude)
+    `splits`: 0 = the library chooses the number of corpus slices; tests force it.
+    Pools (include/nrhip.h, K9): `prior` [V] floating point -- the score becomes fl32(dot + prior[v]), one fp32 add after the
+    dot product, and the returned scores are these sums; -inf in it takes a news out for every user.  `stamp` [V] and `window`
+    [U, 2] integers, together -- user u is only given news with window[u, 0] <= stamp[v] <= window[u, 1] (lo > hi: an all-fill
+    row).  Without them the call is the plain one, bit for bit."""
+    _need_gpu(news_vecs, user_vecs, exclude, prior, stamp, window)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_topk: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1020,9 +1045,11 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0):
             raise RuntimeError(f"score_topk: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
         E = exclude.shape[1]
         ex = exclude.detach().to(torch.int32).contiguous() if E else None
+    pr, st, win = _pool_args("score_topk", V, U, dev, prior, stamp, window)
     d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), exclude=ptr(ex), ld_exclude=E, E=E,
-                      splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores))
+                      splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
+                      ld_window=2 if win is not None else 0)
     ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
     check(_lib.lib().nr_score_topk(C.byref(d), _stream()), "nr_score_topk")
@@ -1030,7 +1057,7 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0):
 
 
 @torch.no_grad()
-def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0):
+def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, prior=None, stamp=None, window=None):
     """Full-corpus rank evaluation (nr_score_rank): for every user and each of its targets ([U, T <= 64] news ids, 0 = no entry)
     the exact 1-based position of that news among the user's eligible news of the whole table, in score_topk's order and with
     score_topk's score bits: 1 <= rank <= k exactly when the target is in the user's top-k row.  Rank 0, score -inf: the target
@@ -1038,8 +1065,10 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0):
     score matrix is formed.  Returns (ranks int32 [U, T], scores fp32 [U, T], sums): with cut-offs `ks` (at most 8) sums is a
     DEVICE fp64 tensor [2 + 2 len(ks)] = [users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u]
     (metrics.retrieval_metrics_reference states the per-user terms); with ks=None no sums are formed and None is returned.
-    `splits`: 0 = the library chooses the number of corpus slices; tests force it."""
-    _need_gpu(news_vecs, user_vecs, targets, exclude)
+    `splits`: 0 = the library chooses the number of corpus slices; tests force it.
+    Pools: `prior`, `stamp`, `window` as in score_topk, with the same score fl32(dot + prior) and the same eligible news, so the
+    agreement with score_topk's rows holds for equal pool inputs.  A target outside its user's pool has rank 0, score -inf."""
+    _need_gpu(news_vecs, user_vecs, targets, exclude, prior, stamp, window)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_rank: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1067,10 +1096,11 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0):
         E = exclude.shape[1]
         ex = exclude.detach().to(torch.int32).contiguous() if E else None
     ks_host = (C.c_int * max(len(ks), 1))(*ks)
+    pr, st, win = _pool_args("score_rank", V, U, dev, prior, stamp, window)
     d = _lib.RankDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, exclude=ptr(ex),
                       ld_exclude=E, E=E, splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
-                      out_sums=ptr(sums))
+                      out_sums=ptr(sums), prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
     ws = _ws(_lib.lib().nr_score_rank_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
     check(_lib.lib().nr_score_rank(C.byref(d), _stream()), "nr_score_rank")

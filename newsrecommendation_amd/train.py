@@ -317,8 +317,21 @@ class _Histories:
         self.mask = mask
 
 
+def _pool_kwargs(device, prior, news_time, window):
+    """recommend's / rank_eval's pool arguments as ops.score_topk's / ops.score_rank's keywords, on `device`; what is None is left
+    out, so a call without pools is the call it always was."""
+    kw = {}
+    if prior is not None:
+        kw["prior"] = torch.as_tensor(prior).to(device=device, dtype=torch.float32)
+    if news_time is not None:
+        kw["stamp"] = torch.as_tensor(news_time).to(device=device, dtype=torch.int32)
+    if window is not None:
+        kw["window"] = torch.as_tensor(window).to(device=device, dtype=torch.int32)
+    return kw
+
+
 @torch.no_grad()
-def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192):
+def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None):
     """Full-corpus recommendation: for every user the k best news of the whole table `news_vecs` ([N+1, news_dim], what
     encode_news returns), none of them the padding news 0.  hist_idx [U, H]: the users' clicked histories as news indices,
     front padded with 0 (src/dataset.py:17-24); mask [U, H]: 1 for a real slot.  The user vectors come from the code
@@ -326,7 +339,10 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     exclude_history: a user is not given what they already clicked.  The kernel takes at most 64 excluded ids per user: of a
     history wider than 64 slots only the LAST 64 (the most recent clicks) are excluded.
     Returns (ids int32 [U, k], scores fp32 [U, k]) on the device, rows sorted by (score descending, id ascending); a row with
-    fewer than k eligible news ends in id 0, score -inf.  Several ranks: the caller shards the users; there is no collective."""
+    fewer than k eligible news ends in id 0, score -inf.  Several ranks: the caller shards the users; there is no collective.
+    Pools (ops.score_topk): prior [N+1] -- a per-news freshness or popularity term added to the score in fp32, -inf = not in
+    the pool at all; news_time [N+1] integer stamps with window [U, 2] -- user u is only given news with
+    window[u, 0] <= news_time[v] <= window[u, 1].  The caller supplies the arrays (any integer unit of time)."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -335,7 +351,7 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     exclude = None
     if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
         exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
-    return ops.score_topk(news_vecs, user, k, exclude=exclude)
+    return ops.score_topk(news_vecs, user, k, exclude=exclude, **_pool_kwargs(device, prior, news_time, window))
 
 
 def _retrieval_sums(ranks, ks):
@@ -357,7 +373,8 @@ def _retrieval_sums(ranks, ks):
 
 
 @torch.no_grad()
-def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclude_history=True, batch_size=8192):
+def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclude_history=True, batch_size=8192, prior=None, news_time=None,
+              window=None):
     """Full-corpus retrieval evaluation: where does each held-out click of a user stand in that user's ranking of the WHOLE
     table `news_vecs`?  hist_idx, mask, exclude_history and the user vectors are recommend's (_user_vectors; of a history wider
     than 64 slots only the LAST 64 are excluded); targets [U, T]: the held-out news indices of every user, 0 = no entry.
@@ -371,7 +388,10 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     exclusions and the target itself, so the rows rank independently and exactly.  The user's metric terms, which need all its
     ranks at once (n_u, the ideal DCG), are then formed here from the gathered ranks in fp64 tensor arithmetic instead of in
     the kernel's finalize pass; the formulas are the same (metrics.retrieval_metrics_reference).
-    Several ranks: the caller shards the users and the sums add; there is no collective."""
+    Several ranks: the caller shards the users and the sums add; there is no collective.
+    Pools: prior, news_time, window as in recommend -- the click is ranked inside the pool that was live for this user (for an
+    impression: the news published in a window before it), with the prior in the score; a target outside the pool has rank 0.
+    The rows of a user with more than 64 targets share its window as well."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -383,8 +403,9 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
         exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
     U, T = tg.shape
     W = _lib.NR_RANK_MAX_TARGETS
+    pool = _pool_kwargs(device, prior, news_time, window)
     if T <= W or U == 0:
-        return ops.score_rank(news_vecs, user, tg, exclude=exclude, ks=ks)
+        return ops.score_rank(news_vecs, user, tg, exclude=exclude, ks=ks, **pool)
     # later repeats -> 0 (stable sort by id: the first of equal ids is the earliest entry), then the non-zero entries to the front
     srt, at = torch.sort(tg, dim=1, stable=True)
     rep = torch.zeros_like(tg, dtype=torch.bool)
@@ -399,8 +420,10 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     live = cols < T
     cols = cols.clamp(max=T - 1)
     row_tg = (comp[row_user[:, None], cols] * live).contiguous()
+    if "window" in pool:
+        pool["window"] = pool["window"][row_user].contiguous()
     r, sc, _ = ops.score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=None if exclude is None else exclude[row_user].contiguous(),
-                              ks=None)
+                              ks=None, **pool)
     ranks_c = torch.zeros(U, T, dtype=torch.int32, device=device)
     scores_c = torch.full((U, T), float("-inf"), dtype=torch.float32, device=device)
     ru = row_user[:, None].expand_as(cols)
@@ -425,10 +448,11 @@ def _shard_targets(shard: IndexedTestShard):
 
 
 @torch.no_grad()
-def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100)):
+def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100), prior=None, news_time=None, window=None):
     """rank_eval over the impressions of a test shard: every impression is one user (its history), its targets are the news it
-    clicked, cand[label == 1] per CSR row in list order, rows back padded with 0.  Returns rank_eval's (ranks, scores, sums)."""
-    return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks)
+    clicked, cand[label == 1] per CSR row in list order, rows back padded with 0.  Returns rank_eval's (ranks, scores, sums).
+    prior, news_time, window: rank_eval's pools, window [impressions, 2]; the shard holds no times, the caller supplies them."""
+    return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks, prior=prior, news_time=news_time, window=window)
 
 
 @torch.no_grad()

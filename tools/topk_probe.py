@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """Full-corpus top-k recommendation: the fused call (ops.score_topk) against torch.matmul + torch.topk on the same device.
 
-    python tools/topk_probe.py [--news 100001] [--dim 400] [--k 10] [--users 64 8192] [--calls 30] [--warmup 5] [--out FILE]
+    python tools/topk_probe.py [--news 100001] [--dim 400] [--k 10] [--users 64 8192] [--calls 30] [--warmup 5] [--out FILE] [--pool]
 
 Both sides take the same fp32 inputs.  Per U: every call is timed with a pair of device events, the two sides alternate call
 by call (so that a disturbance of the machine hits both), and the median, minimum, maximum and inter-quartile spread of the
 timed calls are reported, with the peak device memory of one call above what the inputs occupy.  The fused side's share of the
 fp32 MFMA peak counts the algorithmic 2 * U * V * N FLOPs over the WHOLE call (both launches), against 157.3 TFLOP/s.
-One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to."""
+One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to.
+--pool: instead of the baseline, the same fused call with a prior and a window (ops.score_topk(..., prior=, stamp=, window=)) at
+the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio."""
 import argparse
 import json
 import os
@@ -52,11 +54,43 @@ def peak_bytes(fn, *a):
     return int(peak)
 
 
+def write(out, lines):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.writelines(json.dumps(r) + "\n" for r in lines)
+
+
 def stats(ms):
     a = np.asarray(ms)
     q1, med, q3 = np.percentile(a, [25, 50, 75])
     return {"median_ms": round(float(med), 4), "min_ms": round(float(a.min()), 4), "max_ms": round(float(a.max()), 4),
             "iqr_ms": round(float(q3 - q1), 4), "calls": len(ms)}
+
+
+def pool_inputs(V, U, g):
+    """The inputs of --pool: a float prior with a tenth of the news switched off (-inf), stamps 0 .. 999 and per user a window
+    that is 500 stamps wide (about half of the corpus is in a user's pool)."""
+    prior = torch.randn(V, generator=g) * 0.1
+    prior[torch.rand(V, generator=g) < 0.1] = float("-inf")
+    stamp = torch.randint(0, 1000, (V,), generator=g, dtype=torch.int32)
+    lo = torch.randint(0, 500, (U,), generator=g, dtype=torch.int32)
+    return prior.cuda(), stamp.cuda(), torch.stack([lo, lo + 499], 1).contiguous().cuda()
+
+
+def pool_row(plain, pooled, calls, warmup):
+    """--pool: the plain fused call and the pooled one, alternating, timed as everything else here."""
+    for _ in range(warmup):
+        plain()
+        pooled()
+    torch.cuda.synchronize()
+    t_p, t_q = [], []
+    for _ in range(calls):
+        t_p.append(timed(plain))
+        t_q.append(timed(pooled))
+    row = {"mode": "pool", "plain": stats(t_p), "pooled": stats(t_q)}
+    row["pooled_over_plain"] = round(row["pooled"]["median_ms"] / row["plain"]["median_ms"], 4)
+    return row
 
 
 def main():
@@ -68,6 +102,7 @@ def main():
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pool", action="store_true", help="time the pooled fused call against the plain fused call")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("topk_probe needs a GPU")
@@ -78,6 +113,15 @@ def main():
     lines = []
     for U in args.users:
         user = (torch.randn(U, args.dim, generator=g) * 0.4).cuda()
+        if args.pool:
+            prior, stamp, window = pool_inputs(args.news, U, g)
+            row = {"U": U, "V": args.news, "N": args.dim, "k": args.k}
+            row.update(pool_row(lambda: ops.score_topk(news, user, args.k), lambda: ops.score_topk(news, user, args.k, prior=prior, stamp=stamp, window=window),
+                                args.calls, args.warmup))
+            row["filled_fraction"] = round(float((ops.score_topk(news, user, args.k, prior=prior, stamp=stamp, window=window)[0] != 0).float().mean()), 6)
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         for _ in range(args.warmup):
             fused(news, user, args.k)
             baseline(news, user, args.k)
@@ -100,6 +144,9 @@ def main():
         lines.append(row)
         print(json.dumps(row), flush=True)
         del user
+    if args.pool:
+        write(args.out, lines)
+        return
     last = lines[-1]
     spread = max(last["fused"]["iqr_ms"], last["baseline"]["iqr_ms"])
     verdict = {"U": last["U"], "spread_ms": spread,
@@ -107,10 +154,7 @@ def main():
                "memory_ok": last["baseline_peak_bytes"] - last["fused_peak_bytes"] >= last["score_matrix_bytes"]}
     lines.append(verdict)
     print(json.dumps(verdict), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.writelines(json.dumps(r) + "\n" for r in lines)
+    write(args.out, lines)
 
 
 if __name__ == "__main__":
