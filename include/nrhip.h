@@ -389,8 +389,8 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  *   k        1 .. 128
  *   splits   0: the library chooses (fills the chip for few users, 1-2 for many); > 0: that many slices, at most
  *            min(256, 8192 / k)
- *   ws       nr_score_topk_workspace_bytes(d) bytes, 8-byte aligned (the query reads U, V, N, k, splits only; 0 = bad
- *            descriptor, see nr_last_error)
+ *   ws       nr_score_topk_workspace_bytes(d) bytes, 8-byte aligned (the size depends on U, V, N, k, splits only; 0 = bad
+ *            descriptor -- a refused group / group_cap pairing included --, see nr_last_error)
  * Pools (optional; all zero = off, and the call is then the one it was before they existed, bit for bit).  Shared with
  * nr_score_rank, one definition (pool_key, csrc/nr_score_tile.h):
  *   prior    [V] fp32.  score[u, v] = fl32(dot[u, v] + prior[v]): dot is the finished fmaf chain above, its bits unchanged;
@@ -401,7 +401,28 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  *            window[u, 0] <= stamp[v] <= window[u, 1], both ends inclusive.  lo > hi is an empty pool: the row is all fill.
  *            The two come together: one without the other is refused.
  * Eligible then means all of: id in [1, V), id not in exclude[u], score not NaN, prior not -inf, stamp inside the window.
- * Order, fill and the independence of `splits` are unchanged; the workspace size does not depend on these fields.      */
+ * Order, fill and the independence of `splits` are unchanged; the workspace size does not depend on these fields.
+ * Group caps (optional; group == NULL with group_cap == 0 = off, and the call is then today's, bit for bit, on the kernel
+ * instantiations it always launched): "at most c news of one category in the row".
+ *   group      [V] int32, one group id per news; a negative id = belongs to no group, never capped
+ *   group_cap  c in [1, NR_TOPK_MAX_K]
+ * The row of user u is then: walk u's eligible news in the total order above (score descending, news id ascending); take a
+ * news unless group[v] >= 0 and c news of that group are already taken; stop after k.  Everything else is as without caps:
+ * eligible means what it means above (id in [1, V), not excluded, score not NaN, prior not -inf, stamp inside the window), and
+ * an ineligible news uses up nothing of its group's cap; the score is fl32(dot + prior), the same fmaf chain, the same bits;
+ * the fill is id 0 / -inf when fewer than k news can be taken (G groups, no ungrouped news and G * c < k: at most G * c
+ * entries); the row does not depend on `splits`, the user tile or the place in it.  c >= k and an all-negative `group` give
+ * the rows of the plain call.  `group` without a cap in [1, 128], or a cap without `group`, is refused (nr_last_error).
+ * The cap lives inside the selection (one exchange per candidate) and in the merge, which walks the sorted
+ * slice lists with the same rule; the workspace size does not depend on these fields either.
+ * Slow case, exact but not fast: while a user's list cannot fill (G * c < k and few ungrouped news) its threshold never
+ * rises, and every chunk of the corpus goes through the per-candidate path for that user.
+ * nr_score_rank does NOT know caps: it keeps describing the uncapped ranking.  What holds across the two: a capped row is a
+ * subsequence of the uncapped order, so the uncapped rank of the entry at place p (0-based) is >= p + 1, the ranks along a
+ * row increase strictly, and the scores are the rank pass's bit for bit.  A capped rank would need per-(user, target,
+ * group) counters; it is not offered.
+ * Layout: group and group_cap sit with the other inputs of the selection rule, behind `splits`; nr_topk_desc and nr_rank_desc
+ * keep ending in the shared tail ws, ws_bytes, prior, stamp, window, ld_window.  nr_abi_sizes follows by sizeof.           */
 #define NR_TOPK_MAX_K 128
 #define NR_TOPK_MAX_N 1024
 #define NR_TOPK_MAX_EXCLUDE 64
@@ -414,6 +435,8 @@ typedef struct {
   const int32_t* exclude;
   int ld_exclude, E;
   int splits;
+  const int32_t* group;  /* optional [V]: group id per news, negative = no group; with group_cap */
+  int group_cap;         /* 1 .. NR_TOPK_MAX_K with group, 0 without */
   int32_t* out_ids;
   float* out_scores;
   void* ws;

@@ -19,6 +19,20 @@
 //                           it is unchanged.
 //   topk_merge_kernel       one workgroup per user: bitonic sort of the splits * k candidates in LDS, the first k written out.
 //
+// Group caps ("at most c news of one group in the row", include/nrhip.h K9; the GROUP instantiation of the selection and
+// topk_merge_group_kernel).  The rows that respect the caps are the independent sets of a partition matroid truncated at k,
+// keys are distinct, so the greedy row is the unique maximum basis and inserting one candidate x of group g is ONE exchange:
+//   g >= 0 and the list holds c keys of g:  x replaces the smallest of those c if it beats it, else it is dropped;
+//   otherwise, the list is not full:        x is inserted;
+//   otherwise:                              x replaces the overall smallest key (it beat the threshold, so it beats that).
+// The threshold stays the score key of the OVERALL worst kept candidate (0 while the list is not full): a saturated group's
+// minimum is >= it, so the fast test remains a correct filter; only the slow path changes.  The groups of the kept candidates
+// are not stored: a slow-path entry re-gathers group[~id] for its two slots per lane, together with the groups of the
+// chunk's 128 news (coalesced) and beside the exclusion row that entry always read -- one memory latency, already paid --
+// so the LDS bytes, the user tile and with them the slice count and the workspace size are those of the plain call.
+// The capped row of the whole corpus lies in the union of the slices' capped rows (a key outside its slice's basis is the
+// minimum of a circuit inside it), so the merge is the same greedy walk over the sorted splits * k keys.
+//
 // A candidate is one 64-bit key: (order-preserving image of the score) << 32 | ~id.  Larger key = better; key 0 = "nothing"
 // (NaN scores map to it and are never kept; it decodes to id 0, score -inf, the fill of a short row).  Ids of a slice arrive in
 // ascending order, so a score that only TIES the threshold can never displace a kept one: the fast test is a strict >.
@@ -65,11 +79,26 @@ struct TopkArgs {
   int V, U, N, k, E, splits, per;
   PoolArgs pool;          // read by the POOL instantiations only
 };
+// A kernel argument of its own, behind TopkArgs: the kernel argument segment of a call without caps keeps its layout up to there.
+struct GroupArgs {
+  const int32_t* group;   // [V], read by the GROUP instantiations only
+  int cap;
+};
+
+// the slow path's group registers: of the kept candidates (g0, g1: an empty slot and a slot >= k belong to no group) and of
+// the chunk's news (n0, n1), two per lane each; nothing at all in a kernel without caps
+template <bool GROUP>
+struct GroupRegs {
+  int32_t g0 = -1, g1 = -1, n0 = -1, n1 = -1;
+};
+template <>
+struct GroupRegs<false> {};
 
 // POOL: the call has a prior and / or stamps + windows; the keys then come from pool_key (nr_score_tile.h).  A call without
-// them launches <MT, false>, the kernel as it was before pools existed.
-template <int MT, bool POOL>
-__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
+// them launches <MT, false, .>, the kernel as it was before pools existed.  GROUP: the call has group caps (the exchange
+// rule at the top of this file); a call without them launches <MT, ., false>, the kernel as it was before caps existed.
+template <int MT, bool POOL, bool GROUP>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, GroupArgs ga) {
   constexpr int TU = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
   ScoreTile<MT> t(tk_smem, a.N);                         // scoring tile: nr_score_tile.h
@@ -137,6 +166,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
       u64 c0 = lane < a.k ? list[lane] : ~0ull, c1 = lane + 64 < a.k ? list[lane + 64] : ~0ull;
       u64 mn = wave_min_u64(c0 < c1 ? c0 : c1);
       const int32_t ex = (a.exclude != nullptr && lane < a.E) ? a.exclude[(size_t)(u0 + ul) * a.ld_excl + lane] : 0;
+      GroupRegs<GROUP> r;
+      if constexpr (GROUP) {
+        if (lane < a.k && c0 != 0ull) r.g0 = ga.group[(uint32_t)~(uint32_t)c0];
+        if (lane + 64 < a.k && c1 != 0ull) r.g1 = ga.group[(uint32_t)~(uint32_t)c1];
+        if (lane < nvalid) r.n0 = ga.group[vc + lane];
+        if (lane + 64 < nvalid) r.n1 = ga.group[vc + lane + 64];
+      }
       for (int half = 0; half < 2; ++half) {
         const uint32_t kh = half ? k1 : k0;
         u64 pass = __ballot(kh > thr);
@@ -148,12 +184,29 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
           const uint32_t id = (uint32_t)(vc + half * 64 + j);
           if (__ballot(ex == (int32_t)id) != 0ull) continue; // ids are >= 1: the 0 of an unused lane never matches
           const u64 cand = ((u64)key << 32) | (uint32_t)~id;
-          const u64 at0 = __ballot(c0 == mn);                // replace the worst (an empty slot while there is one)
-          if (at0) {
-            if (lane == __ffsll((long long)at0) - 1) c0 = cand;
+          if constexpr (GROUP) {
+            const int32_t gc = __shfl(half ? r.n1 : r.n0, j, 64);
+            u64 out = mn;                                    // as below, unless the candidate's group is saturated:
+            if (gc >= 0 && __popcll(__ballot(r.g0 == gc)) + __popcll(__ballot(r.g1 == gc)) >= ga.cap) {
+              const u64 m0 = r.g0 == gc ? c0 : ~0ull, m1 = r.g1 == gc ? c1 : ~0ull;
+              out = wave_min_u64(m0 < m1 ? m0 : m1);         // then only the group's own smallest can make room
+              if (cand < out) continue;
+            }
+            const u64 at0 = __ballot(c0 == out);
+            if (at0) {
+              if (lane == __ffsll((long long)at0) - 1) c0 = cand, r.g0 = gc;
+            } else {
+              const u64 at1 = __ballot(c1 == out);
+              if (lane == __ffsll((long long)at1) - 1) c1 = cand, r.g1 = gc;
+            }
           } else {
-            const u64 at1 = __ballot(c1 == mn);
-            if (lane == __ffsll((long long)at1) - 1) c1 = cand;
+            const u64 at0 = __ballot(c0 == mn);              // replace the worst (an empty slot while there is one)
+            if (at0) {
+              if (lane == __ffsll((long long)at0) - 1) c0 = cand;
+            } else {
+              const u64 at1 = __ballot(c1 == mn);
+              if (lane == __ffsll((long long)at1) - 1) c1 = cand;
+            }
           }
           mn = wave_min_u64(c0 < c1 ? c0 : c1);
           thr = (uint32_t)(mn >> 32);
@@ -172,11 +225,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__ part, int n, int P, int k, int32_t* __restrict__ out_ids,
-                                                          float* __restrict__ out_scores) {
-  extern __shared__ __attribute__((aligned(16))) u64 tk_keys[];
-  const int tid = threadIdx.x;
-  const size_t u = blockIdx.x;
+// one user's n candidates, padded with 0 to P (a power of two), into tk_keys and sorted descending; ends with a barrier
+__device__ __forceinline__ void merge_sort_keys(u64* tk_keys, const u64* __restrict__ part, int n, int P, int tid, size_t u) {
   for (int i = tid; i < P; i += 256) tk_keys[i] = i < n ? part[u * n + i] : 0ull;
   for (int size = 2; size <= P; size <<= 1)
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -192,10 +242,68 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__
       }
     }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__ part, int n, int P, int k, int32_t* __restrict__ out_ids,
+                                                          float* __restrict__ out_scores) {
+  extern __shared__ __attribute__((aligned(16))) u64 tk_keys[];
+  const int tid = threadIdx.x;
+  const size_t u = blockIdx.x;
+  merge_sort_keys(tk_keys, part, n, P, tid, u);
   for (int i = tid; i < k; i += 256) {
     const u64 key = tk_keys[i];
     out_ids[u * k + i] = key ? (int32_t)~(uint32_t)key : 0;
     out_scores[u * k + i] = key ? key_score((uint32_t)(key >> 32)) : -__builtin_inff();
+  }
+}
+
+// The merge of a capped call: after the sort ONE wave walks the keys 64 at a time in sorted order.  Within a group the
+// greedy walk takes exactly the first c keys, so key i is taken when its group is negative or (taken keys of its group in
+// earlier blocks) + (keys of its group at earlier lanes of this block) < c: per distinct group of the block three ballots,
+// no serial walk.  The groups of the <= 128 taken keys live in LDS behind the keys (sTaken, -1 = ungrouped / not yet
+// taken), two per lane in registers while a block is decided.  The walk stops at k taken or at the first key 0 (the sort
+// puts them last; key 0 is never taken); usually within a few blocks.
+__global__ __launch_bounds__(256) void topk_merge_group_kernel(const u64* __restrict__ part, int n, int P, int k,
+                                                                const int32_t* __restrict__ group, int cap, int32_t* __restrict__ out_ids,
+                                                                float* __restrict__ out_scores) {
+  extern __shared__ __attribute__((aligned(16))) u64 tk_keys[];
+  int32_t* sTaken = reinterpret_cast<int32_t*>(tk_keys + P);   // [NR_TOPK_MAX_K]
+  const int tid = threadIdx.x;
+  const size_t u = blockIdx.x;
+  merge_sort_keys(tk_keys, part, n, P, tid, u);
+  if (tid >= 64) return;                                        // no barrier follows
+  const int lane = tid;
+  const u64 below = (1ull << lane) - 1ull;
+  sTaken[lane] = -1;
+  sTaken[lane + 64] = -1;
+  int nt = 0;
+  for (int base = 0; base < P && nt < k; base += 64) {
+    const u64 key = base + lane < P ? tk_keys[base + lane] : 0ull;
+    if (__ballot(key != 0ull) == 0ull) break;
+    const int32_t g = key != 0ull ? group[(uint32_t)~(uint32_t)key] : -1;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // sTaken: written by other lanes of this wave in the block before
+    const int32_t t0 = sTaken[lane], t1 = sTaken[lane + 64];
+    bool take = key != 0ull && g < 0;
+    u64 todo = __ballot(g >= 0);
+    while (todo) {
+      const int32_t gl = __shfl(g, __ffsll((long long)todo) - 1, 64);
+      const u64 same = __ballot(g == gl);
+      const int before = __popcll(__ballot(t0 == gl)) + __popcll(__ballot(t1 == gl));
+      if (g == gl) take = before + __popcll(same & below) < cap;
+      todo &= ~same;
+    }
+    const u64 taken = __ballot(take);
+    const int pos = nt + __popcll(taken & below);
+    if (take && pos < k) {
+      out_ids[u * k + pos] = (int32_t)~(uint32_t)key;
+      out_scores[u * k + pos] = key_score((uint32_t)(key >> 32));
+      sTaken[pos] = g;
+    }
+    nt += __popcll(taken);
+  }
+  for (int i = (nt < k ? nt : k) + lane; i < k; i += 64) {
+    out_ids[u * k + i] = 0;
+    out_scores[u * k + i] = -__builtin_inff();
   }
 }
 
@@ -213,6 +321,9 @@ int topk_check(const nr_topk_desc* d) {
   NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_topk: stamp given without window (the two come together)");
   NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_topk: window given without stamp (the two come together)");
   NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_topk: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_ARG(d->group == nullptr || (d->group_cap >= 1 && d->group_cap <= NR_TOPK_MAX_K),
+               "score_topk: group given with group_cap = %d, the cap must be in [1, %d]", d->group_cap, NR_TOPK_MAX_K);
+  NR_CHECK_ARG(d->group != nullptr || d->group_cap == 0, "score_topk: group_cap = %d given without group (the two come together)", d->group_cap);
   return NR_OK;
 }
 
@@ -249,21 +360,25 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.E = d->E; a.splits = splits;
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
   a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  const GroupArgs ga = {d->group, d->group_cap};
   const bool pool = a.pool.any();
+  const bool grouped = d->group != nullptr;
   const size_t smem = tk_lds_bytes(TU, d->N, d->k);
   const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
   {
     NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
-#define NR_TOPK_LAUNCH(MT, POOL)                                                                                                            \
-  do {                                                                                                                                      \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int)smem));                                                                                           \
-    hipLaunchKernelGGL((topk_select_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a);                                                 \
+#define NR_TOPK_LAUNCH(MT, POOL, GROUP)                                                                                                            \
+  do {                                                                                                                                             \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                     (int)smem));                                                                                                  \
+    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP>), grid, dim3(TK_THREADS), smem, s, a, ga);                                                \
   } while (0)
-#define NR_TOPK_LAUNCH_MT(MT)      \
-  do {                             \
-    if (pool) NR_TOPK_LAUNCH(MT, true); \
-    else NR_TOPK_LAUNCH(MT, false);     \
+#define NR_TOPK_LAUNCH_MT(MT)                            \
+  do {                                                   \
+    if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true); \
+    else if (pool) NR_TOPK_LAUNCH(MT, true, false);      \
+    else if (grouped) NR_TOPK_LAUNCH(MT, false, true);   \
+    else NR_TOPK_LAUNCH(MT, false, false);               \
   } while (0)
     if (TU == 64) NR_TOPK_LAUNCH_MT(4);
     else if (TU == 32) NR_TOPK_LAUNCH_MT(2);
@@ -277,8 +392,14 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   while (P < n) P <<= 1;
   {
     NrProfScope ps(s, "topk_merge[U=%d,n=%d,k=%d]", d->U, n, d->k);
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)d->U), dim3(256), (size_t)P * sizeof(u64), s, (const u64*)a.part, n, P, d->k, d->out_ids,
-                       d->out_scores);
+    if (grouped) {
+      const size_t msmem = (size_t)P * sizeof(u64) + NR_TOPK_MAX_K * sizeof(int32_t);   // up to 64.5 KiB: above the default limit
+      NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_merge_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)msmem));
+      hipLaunchKernelGGL(topk_merge_group_kernel, dim3((unsigned)d->U), dim3(256), msmem, s, (const u64*)a.part, n, P, d->k, d->group,
+                         d->group_cap, d->out_ids, d->out_scores);
+    } else
+      hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)d->U), dim3(256), (size_t)P * sizeof(u64), s, (const u64*)a.part, n, P, d->k, d->out_ids,
+                         d->out_scores);
   }
   NR_CHECK_LAUNCH();
   return NR_OK;

@@ -63,7 +63,7 @@ def _pooled(scores, prior, stamp, window):
     return scores, ok
 
 
-def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window=None):
+def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window=None, group=None, group_cap=None):
     """Host statement of the full-corpus recommendation contract (include/nrhip.h, nr_score_topk); tests check the device
     against it, no product path calls it.
 
@@ -73,7 +73,14 @@ def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window
     nothing, duplicates are allowed), nor a news whose score is NaN.  A row with fewer than k eligible news is filled with
     id 0, score -inf.  Returns (ids int32 [U, k], scores float64 [U, k]).
     Pools: prior [V] is added to the scores (the returned scores are the sums) and -inf in it removes a news for everybody;
-    stamp [V] with window [U, 2] keeps for user u the news with window[u, 0] <= stamp[v] <= window[u, 1] (_pooled)."""
+    stamp [V] with window [U, 2] keeps for user u the news with window[u, 0] <= stamp[v] <= window[u, 1] (_pooled).
+    Group caps: group [V] integer ids (negative = in no group) with group_cap = c in [1, 128], together: the row is the walk
+    down the eligible news in that order which takes a news unless c news of its group are already taken, and stops after k.
+    What is not eligible uses up nothing of a cap."""
+    if (group is None) != (group_cap is None):
+        raise ValueError("group and group_cap come together")
+    if group is not None and not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
     a = np.asarray(a, dtype=np.float64)
     scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
     scores, pool = _pooled(scores, prior, stamp, window)
@@ -87,7 +94,19 @@ def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window
             ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
             ok[ex[(ex >= 1) & (ex < V)]] = False
         cand = np.flatnonzero(ok)
-        order = cand[np.lexsort((cand, -scores[u, cand]))][:k]      # primary key: score descending; ties: id ascending
+        if group is None:
+            order = cand[np.lexsort((cand, -scores[u, cand]))][:k]      # primary key: score descending; ties: id ascending
+        else:
+            grp, taken, order = np.asarray(group, dtype=np.int64).reshape(V), {}, []
+            for v in cand[np.lexsort((cand, -scores[u, cand]))]:
+                g = int(grp[v])
+                if len(order) == k:
+                    break
+                if g >= 0 and taken.get(g, 0) >= int(group_cap):
+                    continue
+                taken[g] = taken.get(g, 0) + 1
+                order.append(v)
+            order = np.asarray(order, dtype=np.int64)
         ids[u, :len(order)] = order
         out[u, :len(order)] = scores[u, order]
     return ids, out

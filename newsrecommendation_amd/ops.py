@@ -1015,7 +1015,7 @@ def _pool_args(what, V, U, dev, prior, stamp, window):
 
 
 @torch.no_grad()
-def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stamp=None, window=None):
+def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stamp=None, window=None, group=None, group_cap=None):
     """Full-corpus recommendation (nr_score_topk): for every user the k best news of the whole table under the order (score
     descending, news id ascending), score[u, v] = <news_vecs[v], user_vecs[u]> in exact fp32.  Row 0 of `news_vecs` (the
     padding news) is never returned; `exclude` ([U, E <= 64] news ids per user, 0 = no entry) neither.  No [U, V] score matrix
@@ -1024,8 +1024,13 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
     Pools (include/nrhip.h, K9): `prior` [V] floating point -- the score becomes fl32(dot + prior[v]), one fp32 add after the
     dot product, and the returned scores are these sums; -inf in it takes a news out for every user.  `stamp` [V] and `window`
     [U, 2] integers, together -- user u is only given news with window[u, 0] <= stamp[v] <= window[u, 1] (lo > hi: an all-fill
-    row).  Without them the call is the plain one, bit for bit."""
-    _need_gpu(news_vecs, user_vecs, exclude, prior, stamp, window)
+    row).  Without them the call is the plain one, bit for bit.
+    Group caps (include/nrhip.h, K9): `group` [V] int32 on the device, one group id per news (a category, say; negative = in no
+    group, never capped) with `group_cap` = c in [1, 128] -- the row is the walk down the same order that skips a news once c
+    news of its group are taken, so at most c per group and still k entries where k can be taken (otherwise the usual fill).
+    One without the other is refused by the library.  Without them the call launches the kernels it always launched.
+    score_rank knows no caps: a capped row is a subsequence of the uncapped order."""
+    _need_gpu(news_vecs, user_vecs, exclude, prior, stamp, window, group)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_topk: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1046,10 +1051,16 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
         E = exclude.shape[1]
         ex = exclude.detach().to(torch.int32).contiguous() if E else None
     pr, st, win = _pool_args("score_topk", V, U, dev, prior, stamp, window)
+    gr = None
+    if group is not None:
+        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
+            raise RuntimeError(f"score_topk: group must be an int32 tensor of shape ({V},) on {dev}, got "
+                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
+        gr = group.detach().contiguous()
     d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), exclude=ptr(ex), ld_exclude=E, E=E,
                       splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
-                      ld_window=2 if win is not None else 0)
+                      ld_window=2 if win is not None else 0, group=ptr(gr), group_cap=0 if group_cap is None else int(group_cap))
     ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
     check(_lib.lib().nr_score_topk(C.byref(d), _stream()), "nr_score_topk")

@@ -331,7 +331,8 @@ def _pool_kwargs(device, prior, news_time, window):
 
 
 @torch.no_grad()
-def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None):
+def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None,
+              news_group=None, group_cap=None):
     """Full-corpus recommendation: for every user the k best news of the whole table `news_vecs` ([N+1, news_dim], what
     encode_news returns), none of them the padding news 0.  hist_idx [U, H]: the users' clicked histories as news indices,
     front padded with 0 (src/dataset.py:17-24); mask [U, H]: 1 for a real slot.  The user vectors come from the code
@@ -342,7 +343,11 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     fewer than k eligible news ends in id 0, score -inf.  Several ranks: the caller shards the users; there is no collective.
     Pools (ops.score_topk): prior [N+1] -- a per-news freshness or popularity term added to the score in fp32, -inf = not in
     the pool at all; news_time [N+1] integer stamps with window [U, 2] -- user u is only given news with
-    window[u, 0] <= news_time[v] <= window[u, 1].  The caller supplies the arrays (any integer unit of time)."""
+    window[u, 0] <= news_time[v] <= window[u, 1].  The caller supplies the arrays (any integer unit of time).
+    Group caps (ops.score_topk): news_group [N+1] integer group ids -- MIND's category or subcategory column, say; negative =
+    in no group -- with group_cap = c: a row holds at most c news of one group and is otherwise the same walk down the order,
+    so it still has k entries wherever k can be taken.  The cap is applied inside the selection, not to a finished row.
+    rank_eval keeps ranking without caps: the uncapped rank of a capped row's entry at place p is >= p + 1."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -351,7 +356,12 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     exclude = None
     if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
         exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
-    return ops.score_topk(news_vecs, user, k, exclude=exclude, **_pool_kwargs(device, prior, news_time, window))
+    kw = _pool_kwargs(device, prior, news_time, window)
+    if news_group is not None:
+        kw["group"] = torch.as_tensor(news_group).to(device=device, dtype=torch.int32)
+    if group_cap is not None:
+        kw["group_cap"] = group_cap
+    return ops.score_topk(news_vecs, user, k, exclude=exclude, **kw)
 
 
 def _retrieval_sums(ranks, ks):

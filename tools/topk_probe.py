@@ -2,6 +2,7 @@
 """Full-corpus top-k recommendation: the fused call (ops.score_topk) against torch.matmul + torch.topk on the same device.
 
     python tools/topk_probe.py [--news 100001] [--dim 400] [--k 10] [--users 64 8192] [--calls 30] [--warmup 5] [--out FILE] [--pool]
+                                [--group G --group-cap C]
 
 Both sides take the same fp32 inputs.  Per U: every call is timed with a pair of device events, the two sides alternate call
 by call (so that a disturbance of the machine hits both), and the median, minimum, maximum and inter-quartile spread of the
@@ -9,7 +10,10 @@ timed calls are reported, with the peak device memory of one call above what the
 fp32 MFMA peak counts the algorithmic 2 * U * V * N FLOPs over the WHOLE call (both launches), against 157.3 TFLOP/s.
 One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to.
 --pool: instead of the baseline, the same fused call with a prior and a window (ops.score_topk(..., prior=, stamp=, window=)) at
-the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio."""
+the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio.
+--group G --group-cap C: likewise, the fused call with group caps (ops.score_topk(..., group=, group_cap=C); G random groups,
+MIND has 18 categories) alternating with the plain fused call; one JSON line per U with both, their ratio and the plain call's
+inter-quartile spread beside the difference of the medians."""
 import argparse
 import json
 import os
@@ -93,6 +97,15 @@ def pool_row(plain, pooled, calls, warmup):
     return row
 
 
+def group_row(plain, capped, calls, warmup):
+    """--group: the plain fused call and the capped one, alternating, timed as everything else here."""
+    row = pool_row(plain, capped, calls, warmup)
+    row = {"mode": "group", "plain": row["plain"], "capped": row["pooled"]}
+    row["capped_over_plain"] = round(row["capped"]["median_ms"] / row["plain"]["median_ms"], 4)
+    row["capped_minus_plain_ms"] = round(row["capped"]["median_ms"] - row["plain"]["median_ms"], 4)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--news", type=int, default=100001)
@@ -103,7 +116,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--pool", action="store_true", help="time the pooled fused call against the plain fused call")
+    ap.add_argument("--group", type=int, default=0, help="with --group-cap: time the capped fused call (this many random groups) against the plain one")
+    ap.add_argument("--group-cap", type=int, default=0)
     args = ap.parse_args()
+    if (args.group > 0) != (args.group_cap > 0) or (args.group > 0 and args.pool):
+        raise SystemExit("--group G and --group-cap C come together, and not with --pool")
     if not torch.cuda.is_available():
         raise SystemExit("topk_probe needs a GPU")
     if args.calls < 20:
@@ -113,6 +130,15 @@ def main():
     lines = []
     for U in args.users:
         user = (torch.randn(U, args.dim, generator=g) * 0.4).cuda()
+        if args.group:
+            group = torch.randint(0, args.group, (args.news,), generator=g, dtype=torch.int32).cuda()
+            row = {"U": U, "V": args.news, "N": args.dim, "k": args.k, "groups": args.group, "group_cap": args.group_cap}
+            row.update(group_row(lambda: ops.score_topk(news, user, args.k), lambda: ops.score_topk(news, user, args.k, group=group, group_cap=args.group_cap),
+                                 args.calls, args.warmup))
+            row["filled_fraction"] = round(float((ops.score_topk(news, user, args.k, group=group, group_cap=args.group_cap)[0] != 0).float().mean()), 6)
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if args.pool:
             prior, stamp, window = pool_inputs(args.news, U, g)
             row = {"U": U, "V": args.news, "N": args.dim, "k": args.k}
@@ -144,7 +170,7 @@ def main():
         lines.append(row)
         print(json.dumps(row), flush=True)
         del user
-    if args.pool:
+    if args.pool or args.group:
         write(args.out, lines)
         return
     last = lines[-1]
