@@ -421,7 +421,26 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  * subsequence of the uncapped order, so the uncapped rank of the entry at place p (0-based) is >= p + 1, the ranks along a
  * row increase strictly, and the scores are the rank pass's bit for bit.  A capped rank would need per-(user, target,
  * group) counters; it is not offered.
- * Layout: group and group_cap sit with the other inputs of the selection rule, behind `splits`; nr_topk_desc and nr_rank_desc
+ * Exclusion lists of any length (optional; excl_offsets == NULL, excl_ids == NULL, n_excl == 0 = off, and the call then
+ * launches the kernel instantiations it always launched).  Shared with nr_score_rank.  The dense list above stops at 64 ids;
+ * "everything this user has been shown" is hundreds to thousands, so it comes in CSR form:
+ *   excl_offsets  [U + 1] int32, non-decreasing: user u's list is excl_ids[excl_offsets[u] .. excl_offsets[u + 1])
+ *   excl_ids      [n_excl] int32 news ids; each user's segment STRICTLY ascending (sorted, no repeats)
+ *   n_excl        entries of excl_ids
+ * Eligible then additionally means "not in user u's segment"; order, fill, NaN rule, pools, group caps, the independence of
+ * `splits` and the workspace size are unchanged.  Entries of a segment that are <= 0 or >= V mean nothing (in a sorted segment
+ * they sit at its two ends).  A segment that is not strictly ascending gives unspecified rows for that user, but never an
+ * access outside excl_ids[0 .. n_excl): the kernels clamp every segment bound into [0, n_excl] (the library cannot check
+ * device arrays on the host and does not synchronise to do so).  One list form per call: E > 0 together with excl_offsets,
+ * excl_offsets without excl_ids or the reverse (unless n_excl == 0), and n_excl < 0 are refused (nr_last_error).
+ * The list is served in the slow path of the selection only: an entry there finds the lower bound of the chunk's first id
+ * in the user's segment with a wave-wide search (64 probes a step, ceil(log64 L) dependent loads) and keeps the at most 128
+ * entries that can fall into the chunk in two registers per lane.  No LDS, so the user tile, the slices, the workspace and
+ * the merge kernels are those of the plain call.
+ * Slow case, exact but not fast (as with group caps): a user whose segment covers nearly the whole corpus never fills its
+ * list, its threshold never rises, and every chunk goes through the per-candidate path for that user.
+ * Layout: excl_offsets, excl_ids, n_excl sit behind `E`, in front of `splits` (n_excl and splits share one 8-byte slot); group
+ * and group_cap sit with the other inputs of the selection rule, behind `splits`; nr_topk_desc and nr_rank_desc
  * keep ending in the shared tail ws, ws_bytes, prior, stamp, window, ld_window.  nr_abi_sizes follows by sizeof.           */
 #define NR_TOPK_MAX_K 128
 #define NR_TOPK_MAX_N 1024
@@ -434,6 +453,9 @@ typedef struct {
   int N, k;
   const int32_t* exclude;
   int ld_exclude, E;
+  const int32_t* excl_offsets; /* optional [U + 1], non-decreasing: user u's list is excl_ids[excl_offsets[u] .. excl_offsets[u+1]) */
+  const int32_t* excl_ids;     /* optional [n_excl] news ids; each user's segment STRICTLY ascending (sorted, no repeats) */
+  int n_excl;                  /* entries of excl_ids; the kernels clamp every segment bound into [0, n_excl] */
   int splits;
   const int32_t* group;  /* optional [V]: group id per news, negative = no group; with group_cap */
   int group_cap;         /* 1 .. NR_TOPK_MAX_K with group, 0 without */
@@ -479,7 +501,12 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
  * of stamp / window without the other is refused).  The score is fl32(dot + prior), the eligible news are additionally those
  * whose prior is not -inf and whose stamp lies in the user's window, and a target outside its user's pool is "not ranked":
  * rank 0, score -inf.  An excluded id that is itself outside the pool takes nothing off a rank (it was never counted).  The
- * statement "1 <= rank <= k exactly when the target is at place rank - 1 of the top-k row" holds for equal pool inputs.   */
+ * statement "1 <= rank <= k exactly when the target is at place rank - 1 of the top-k row" holds for equal pool inputs.
+ * Exclusion lists of any length: excl_offsets, excl_ids, n_excl exactly as in nr_topk_desc (all zero = off: the kernels the
+ * call always launched; the same refusals).  A target found in its user's segment is "not ranked"; a listed news takes one
+ * off the rank of every target it beats, if it is in range and eligible (not NaN, inside the pool).  The named-id pass then
+ * takes a user's list through further chunks of 128 gathered rows (the first 64 ids ride with the targets); the counting
+ * pass, the finalize pass and the workspace are unchanged.  The agreement with nr_score_topk holds for equal lists.       */
 #define NR_RANK_MAX_TARGETS 64
 #define NR_RANK_MAX_KS 8
 typedef struct {
@@ -492,6 +519,9 @@ typedef struct {
   int ld_targets;
   const int32_t* exclude;
   int ld_exclude, E;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
   int splits;
   const int* ks; /* host */
   int n_ks;

@@ -69,7 +69,8 @@ NR_TOPK_MAX_K, NR_TOPK_MAX_N, NR_TOPK_MAX_EXCLUDE = 128, 1024, 64
 
 class TopkDesc(C.Structure):
     _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
-                ("N", C.c_int), ("k", C.c_int), ("exclude", C.c_void_p), ("ld_exclude", C.c_int), ("E", C.c_int), ("splits", C.c_int),
+                ("N", C.c_int), ("k", C.c_int), ("exclude", C.c_void_p), ("ld_exclude", C.c_int), ("E", C.c_int),
+                ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int), ("splits", C.c_int),
                 ("group", C.c_void_p), ("group_cap", C.c_int),
                 ("out_ids", C.c_void_p), ("out_scores", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
                 ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
@@ -81,7 +82,8 @@ NR_RANK_MAX_TARGETS, NR_RANK_MAX_KS = 64, 8
 class RankDesc(C.Structure):
     _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
                 ("N", C.c_int), ("T", C.c_int), ("targets", C.c_void_p), ("ld_targets", C.c_int), ("exclude", C.c_void_p),
-                ("ld_exclude", C.c_int), ("E", C.c_int), ("splits", C.c_int), ("ks", C.POINTER(C.c_int)), ("n_ks", C.c_int),
+                ("ld_exclude", C.c_int), ("E", C.c_int), ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int),
+                ("splits", C.c_int), ("ks", C.POINTER(C.c_int)), ("n_ks", C.c_int),
                 ("out_ranks", C.c_void_p), ("out_scores", C.c_void_p), ("out_sums", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
                 ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
 

@@ -9,6 +9,16 @@
 //                           targets are ranked at all (in range, not NaN, not excluded, not a repeat), their 64-bit keys
 //                           (score key << 32 | ~id, as in nr_topk.hip) compacted to the front of the row, and for each the number
 //                           of distinct excluded news that beat it.
+//   rank_named_csr_kernel   the named pass of a call with exclusion lists in CSR form (include/nrhip.h K9 / K10), any length.
+//                           Chunk 0 of a user is unchanged: targets in rows 0 .. 63, the first 64 listed ids in rows 64 .. 127.
+//                           A user with more listed ids gets further chunks of 128 gathered rows each through the same
+//                           ScoreTile<1> sequence, so every listed news has the key bits the stream gives it.  Wave 0 keeps the
+//                           target keys in registers across the user's chunks, uncompacted (lane j = target j); per chunk it
+//                           adds, per target, the listed news that beat it and clears `ranked` for a target found in the list;
+//                           the compaction happens after the user's last chunk.  "Each listed news once" is the strict order
+//                           of the segment.  The ids of a chunk are staged in LDS one chunk ahead (two buffers), so the pass
+//                           needs no more LDS than rank_named_kernel.  Of the [16 x 128] scores of a chunk one row is used:
+//                           16 x the needed work, DESIGN.md section 5 has the arithmetic.
 //   rank_count_kernel<MT>   the grid and chunking of topk_select_kernel.  A wave owns 2 * MT users of the tile and holds their
 //                           compacted target keys (lane j = target j) and counters in registers; per chunk and user it ballots
 //                           "key of this news > key of target j" for the user's REAL targets only and adds the population
@@ -179,6 +189,131 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
   }
 }
 
+// The ids of chunk q of a user into dst[0 .. 128): chunk 0 = its targets (rows 0 .. 63) and entries 0 .. 63 of its segment
+// ids[b .. b + L) (rows 64 .. 127); chunk q >= 1 = entries 64 + 128 (q - 1) .. of the segment.  0 = no row.
+__device__ __forceinline__ void rank_csr_stage(int32_t* dst, const RankArgs& a, const CsrArgs& ca, size_t u, int q, int32_t b, int32_t L, int tid) {
+  if (tid >= TK_ROWS) return;
+  int32_t id = 0;
+  if (q == 0 && tid < RK_SLOTS) {
+    if (tid < a.T) id = a.targets[u * a.ld_tgt + tid];
+  } else {
+    const long i = q == 0 ? tid - RK_SLOTS : (long)RK_SLOTS + (long)TK_ROWS * (q - 1) + tid;
+    if (i < L) id = ca.ids[(long)b + i];
+  }
+  dst[tid] = id;
+}
+
+template <bool POOL>
+__global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, CsrArgs ca) {
+  extern __shared__ __attribute__((aligned(16))) float rk_smem[];
+  ScoreTile<1> t(rk_smem, a.N);
+  int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [2, 128]: this chunk's ids and the next one's
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * 16;
+  const int users = a.U - u0 < 16 ? a.U - u0 : 16;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  // the walk over (user c of the group, chunk q of its list); every thread keeps the same state
+  int c = 0, q = 0, buf = 0;
+  int32_t seg_b, seg_e;
+  ca.segment(u0, seg_b, seg_e);
+  int32_t L = seg_e - seg_b;
+  rank_csr_stage(sIds, a, ca, (size_t)u0, 0, seg_b, L, tid);
+  __syncthreads();
+
+  RankNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  t.load_slab(rows, 0);
+  // wave 0, across the chunks of one user: lane j = target j
+  int32_t tg = 0;
+  u64 kt = 0ull;
+  bool ranked = false;
+  int beaten_by = 0;
+  int32_t w_lo = 0, w_hi = 0;
+  while (c < users) {
+    // the chunk after this one: the user's next 128 entries, or chunk 0 of the next user
+    const int nq = L > RK_SLOTS ? 1 + (int)(((long)L - RK_SLOTS + TK_ROWS - 1) / TK_ROWS) : 1;
+    int c2 = c, q2 = q + 1;
+    int32_t b2 = seg_b, L2 = L;
+    if (q2 >= nq) {
+      c2 = c + 1;
+      q2 = 0;
+      if (c2 < users) {
+        int32_t e2;
+        ca.segment(u0 + c2, b2, e2);
+        L2 = e2 - b2;
+      }
+    }
+    // staged now, read after the barriers inside chunk(); the buffer's readers finished before the barrier that ended the last turn
+    if (c2 < users) rank_csr_stage(sIds + (buf ^ 1) * TK_ROWS, a, ca, (size_t)(u0 + c2), q2, b2, L2, tid);
+    f32x4 acc[1];
+    rows.ids = sIds + buf * TK_ROWS;
+    t.chunk(rows, acc);
+    if (c2 < users) {
+      rows.ids = sIds + (buf ^ 1) * TK_ROWS;
+      t.load_slab(rows, 0);
+    }
+    t.put_scores(acc);
+    if (wave == 0) {
+      const size_t u = (size_t)(u0 + c);
+      const int32_t* ids = sIds + buf * TK_ROWS;
+      const float* sS = t.scores() + c * TK_LDS_TILE;
+      if (q == 0) {
+        tg = ids[lane];
+        const bool t_in = lane < a.T && tg >= 1 && tg < a.V;
+        if constexpr (POOL) {
+          w_lo = a.pool.lo_of(u);
+          w_hi = a.pool.hi_of(u);
+          const uint32_t st = t_in ? pool_key(sS[lane], a.pool.prior_of(tg), a.pool.stamp_of(tg), w_lo, w_hi) : 0u;
+          kt = ((u64)st << 32) | (uint32_t)~(uint32_t)tg;
+        } else
+          kt = news_key(sS[lane], (uint32_t)tg);
+        ranked = t_in && (kt >> 32) != 0;                     // a NaN score has key 0
+        for (int j = 0; j < a.T; ++j)
+          if (lane > j && tg == __builtin_amdgcn_readlane(tg, j)) ranked = false;   // repeats an earlier entry
+        beaten_by = 0;
+      }
+      // the chunk's listed ids: rows lane (chunks >= 1 only) and lane + 64
+      const int32_t xa = q == 0 ? 0 : ids[lane], xb = ids[lane + RK_SLOTS];
+      const bool a_in = xa >= 1 && xa < a.V, b_in = xb >= 1 && xb < a.V;
+      u64 ka, kb;
+      if constexpr (POOL) {
+        // prior and stamp gathered by id: a listed news gets the key the stream gives it -- 0 outside the user's pool, and then
+        // it was never counted by the stream, so it must not be taken back either
+        const uint32_t sa = a_in ? pool_key(sS[lane], a.pool.prior_of(xa), a.pool.stamp_of(xa), w_lo, w_hi) : 0u;
+        const uint32_t sb = b_in ? pool_key(sS[lane + RK_SLOTS], a.pool.prior_of(xb), a.pool.stamp_of(xb), w_lo, w_hi) : 0u;
+        ka = ((u64)sa << 32) | (uint32_t)~(uint32_t)xa;
+        kb = ((u64)sb << 32) | (uint32_t)~(uint32_t)xb;
+      } else {
+        ka = news_key(sS[lane], (uint32_t)xa);
+        kb = news_key(sS[lane + RK_SLOTS], (uint32_t)xb);
+      }
+      const bool a_counts = a_in && (ka >> 32) != 0, b_counts = b_in && (kb >> 32) != 0;   // a NaN news: nothing to take back
+      for (int j = 0; j < a.T; ++j) {
+        const int32_t tj = __builtin_amdgcn_readlane(tg, j);
+        const u64 ktj = lane_u64(kt, j);
+        const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
+        const int cnt = __popcll(__ballot(a_counts && ka > ktj)) + __popcll(__ballot(b_counts && kb > ktj));
+        if (lane == j) {
+          if (listed) ranked = false;
+          beaten_by += cnt;
+        }
+      }
+      if (q + 1 >= nq) {                                      // the user's last chunk: compact and store
+        const u64 mask = __ballot(ranked);
+        const int p = __popcll(mask & ((1ull << lane) - 1ull)), n = __popcll(mask);
+        if (ranked) {
+          a.w.keys[u * a.T + p] = kt;
+          a.w.excl[u * a.T + p] = beaten_by;
+        }
+        if (lane < a.T) a.w.pos[u * a.T + lane] = ranked ? p : -1;
+        if (lane == 0) a.w.nu[u] = n;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+    c = c2; q = q2; seg_b = b2; L = L2; buf ^= 1;
+  }
+}
+
 template <int MT, bool POOL>
 __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
   constexpr int TU = 16 * MT, PER_WAVE = TU / TK_WAVES;
@@ -337,6 +472,13 @@ int rank_check(const nr_rank_desc* d) {
   NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_rank: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
                NR_TOPK_MAX_N);
   NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_rank: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
+  NR_CHECK_ARG(d->n_excl >= 0, "score_rank: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
+  NR_CHECK_ARG(d->E == 0 || d->excl_offsets == nullptr,
+               "score_rank: the dense list (E = %d) and the CSR lists (excl_offsets) are not combined: one list form per call", d->E);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
+               "score_rank: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
+               "score_rank: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
   NR_CHECK_ARG(d->n_ks >= 0 && d->n_ks <= NR_RANK_MAX_KS, "score_rank: n_ks = %d cut-offs, at most %d", d->n_ks, NR_RANK_MAX_KS);
   NR_CHECK_ARG(d->n_ks == 0 || d->ks != nullptr, "score_rank: null pointer (ks) with n_ks = %d", d->n_ks);
   for (int i = 0; i < d->n_ks; ++i) NR_CHECK_ARG(d->ks[i] >= 1, "score_rank: cut-off k = %d at position %d, must be >= 1", d->ks[i], i);
@@ -384,7 +526,16 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
   a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
   const bool pool = a.pool.any();
-  {
+  const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
+  if (csr) {
+    const CsrArgs ca = {d->excl_offsets, d->excl_ids, d->n_excl};
+    NrProfScope ps(s, "rank_named_csr[U=%d,N=%d,T=%d,n_excl=%d]", d->U, d->N, d->T, d->n_excl);
+    const size_t smem = rk_lds_bytes(16, d->N) + (size_t)2 * TK_ROWS * sizeof(int32_t);
+    const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false>);
+    NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (pool) hipLaunchKernelGGL(rank_named_csr_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca);
+    else hipLaunchKernelGGL(rank_named_csr_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca);
+  } else {
     NrProfScope ps(s, "rank_named[U=%d,N=%d,T=%d,E=%d]", d->U, d->N, d->T, a.E);
     const size_t smem = rk_lds_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
     const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true>) : reinterpret_cast<const void*>(rank_named_kernel<false>);

@@ -63,6 +63,20 @@ struct PoolArgs {
   bool any() const { return prior != nullptr || stamp != nullptr || window != nullptr; }
 };
 
+// Exclusion lists of any length in CSR form (include/nrhip.h, K9): user u's list is ids[offsets[u] .. offsets[u + 1]), strictly
+// ascending.  Read by the CSR instantiations only.  segment() clamps both bounds into [0, n] and keeps e >= b: whatever the
+// offsets hold, no index formed from them leaves ids[0 .. n).
+struct CsrArgs {
+  const int32_t* offsets;   // [U + 1]
+  const int32_t* ids;       // [n]
+  int n;
+  __device__ __forceinline__ void segment(long u, int32_t& b, int32_t& e) const {
+    const int32_t x = offsets[u], y = offsets[u + 1];
+    b = x < 0 ? 0 : (x > n ? n : x);
+    e = y < b ? b : (y > n ? n : y);
+  }
+};
+
 // chunk row r = news row vc + r of a table slice that ends at v_hi
 struct ScoreStreamRows {
   const float* news;

@@ -33,6 +33,15 @@
 // The capped row of the whole corpus lies in the union of the slices' capped rows (a key outside its slice's basis is the
 // minimum of a circuit inside it), so the merge is the same greedy walk over the sorted splits * k keys.
 //
+// Exclusion lists of any length (CSR, include/nrhip.h K9; the CSR instantiation of the selection).  The dense list is one id
+// per lane, read at every slow-path entry; a list of hundreds or thousands of ids does not fit a register row, but a chunk
+// covers the ids [vc, vc + 128) and the user's segment is strictly ascending, so at most 128 of its entries can matter to one
+// entry.  The entry finds the lower bound of vc in the segment (csr_lower_bound: 64 probes a step, the range narrowed by the
+// count of probes < vc, ceil(log64 L) dependent loads), loads the 128 entries from there, two per lane, and keeps those below
+// vc + 128; the per-candidate test is then a ballot over two registers.  The fast path, the exchange, the LDS bytes, the user
+// tile, the slices, the workspace and the merge kernels are untouched.  A user whose list covers nearly the whole corpus never
+// fills its candidates: its threshold stays 0 and every chunk takes the slow path for it -- exact, but slow.
+//
 // A candidate is one 64-bit key: (order-preserving image of the score) << 32 | ~id.  Larger key = better; key 0 = "nothing"
 // (NaN scores map to it and are never kept; it decodes to id 0, score -inf, the fill of a short row).  Ids of a slice arrive in
 // ascending order, so a score that only TIES the threshold can never displace a kept one: the fast test is a strict >.
@@ -85,6 +94,25 @@ struct GroupArgs {
   int cap;
 };
 
+// Lower bound of vc in ids[lo .. hi), ascending: lo + the number of entries < vc.  All 64 lanes call it with the same arguments.
+// While the range holds more than one load (128 entries, two per lane) lane l probes position lo + n (l + 1) / 65 -- 64
+// distinct positions inside the range -- and c, the count of probes < vc, narrows it to the gap between probe c - 1 and probe
+// c.  Every index read lies in [lo, hi) of the call, sorted input or not.  tests/test_exclusion_lists_host.py holds this
+// arithmetic as a numpy model, statement for statement.
+__device__ __forceinline__ int32_t csr_lower_bound(const int32_t* __restrict__ ids, int32_t lo, int32_t hi, int32_t vc, int lane) {
+  while (hi - lo > TK_ROWS) {
+    const long n = hi - lo;
+    const int32_t probe = lo + (int32_t)(n * (lane + 1) / 65);
+    const int c = __popcll(__ballot(ids[probe] < vc));
+    const int32_t last_below = lo + (int32_t)(n * c / 65), first_not = lo + (int32_t)(n * (c + 1) / 65);   // probes c - 1 and c
+    if (c < 64) hi = first_not;
+    if (c > 0) lo = last_below + 1;
+  }
+  const int32_t n = hi - lo;
+  const bool b0 = lane < n && ids[lo + lane] < vc, b1 = lane + 64 < n && ids[lo + lane + 64] < vc;
+  return lo + __popcll(__ballot(b0)) + __popcll(__ballot(b1));
+}
+
 // the slow path's group registers: of the kept candidates (g0, g1: an empty slot and a slot >= k belong to no group) and of
 // the chunk's news (n0, n1), two per lane each; nothing at all in a kernel without caps
 template <bool GROUP>
@@ -96,9 +124,11 @@ struct GroupRegs<false> {};
 
 // POOL: the call has a prior and / or stamps + windows; the keys then come from pool_key (nr_score_tile.h).  A call without
 // them launches <MT, false, .>, the kernel as it was before pools existed.  GROUP: the call has group caps (the exchange
-// rule at the top of this file); a call without them launches <MT, ., false>, the kernel as it was before caps existed.
-template <int MT, bool POOL, bool GROUP>
-__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, GroupArgs ga) {
+// rule at the top of this file); a call without them launches <MT, ., false, .>, the kernel as it was before caps existed.
+// CSR: the call has exclusion lists in CSR form (a kernel argument of its own again, behind GroupArgs) and no dense list; a
+// call without them launches <MT, ., ., false>, the kernel as it was before the lists existed.
+template <int MT, bool POOL, bool GROUP, bool CSR>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, GroupArgs ga, CsrArgs ca) {
   constexpr int TU = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
   ScoreTile<MT> t(tk_smem, a.N);                         // scoring tile: nr_score_tile.h
@@ -122,6 +152,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, Gro
       w_lo = a.pool.lo_of(u0 + ul);
       w_hi = a.pool.hi_of(u0 + ul);
     }
+  }
+
+  // CSR: lane i keeps the segment [x_lo, x_hi) of this wave's i-th user, clamped; an empty one beyond U
+  int32_t x_lo = 0, x_hi = 0;
+  if constexpr (CSR) {
+    const int ul = wave + TK_WAVES * lane;
+    if (ul < TU && u0 + ul < a.U) ca.segment(u0 + ul, x_lo, x_hi);
   }
 
   ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
@@ -165,7 +202,16 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, Gro
       u64* list = sList + (size_t)ul * a.k;
       u64 c0 = lane < a.k ? list[lane] : ~0ull, c1 = lane + 64 < a.k ? list[lane + 64] : ~0ull;
       u64 mn = wave_min_u64(c0 < c1 ? c0 : c1);
-      const int32_t ex = (a.exclude != nullptr && lane < a.E) ? a.exclude[(size_t)(u0 + ul) * a.ld_excl + lane] : 0;
+      int32_t ex = 0, ex1 = 0;                                // CSR: the entries of the user's segment inside [vc, vc + 128)
+      if constexpr (CSR) {
+        const int32_t seg_hi = __builtin_amdgcn_readlane(x_hi, iu);
+        const int32_t from = csr_lower_bound(ca.ids, __builtin_amdgcn_readlane(x_lo, iu), seg_hi, (int32_t)vc, lane);
+        if (lane < seg_hi - from) ex = ca.ids[from + lane];
+        if (lane + 64 < seg_hi - from) ex1 = ca.ids[from + lane + 64];
+        if (ex >= vc + TK_ROWS) ex = 0;
+        if (ex1 >= vc + TK_ROWS) ex1 = 0;
+      } else
+        ex = (a.exclude != nullptr && lane < a.E) ? a.exclude[(size_t)(u0 + ul) * a.ld_excl + lane] : 0;
       GroupRegs<GROUP> r;
       if constexpr (GROUP) {
         if (lane < a.k && c0 != 0ull) r.g0 = ga.group[(uint32_t)~(uint32_t)c0];
@@ -182,7 +228,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, Gro
           const uint32_t key = __shfl(kh, j, 64);
           if (key <= thr) continue;                          // the threshold rose since the ballot
           const uint32_t id = (uint32_t)(vc + half * 64 + j);
-          if (__ballot(ex == (int32_t)id) != 0ull) continue; // ids are >= 1: the 0 of an unused lane never matches
+          if constexpr (CSR) {
+            if (__ballot(ex == (int32_t)id || ex1 == (int32_t)id) != 0ull) continue;
+          } else if (__ballot(ex == (int32_t)id) != 0ull) continue; // ids are >= 1: the 0 of an unused lane never matches
           const u64 cand = ((u64)key << 32) | (uint32_t)~id;
           if constexpr (GROUP) {
             const int32_t gc = __shfl(half ? r.n1 : r.n0, j, 64);
@@ -316,6 +364,13 @@ int topk_check(const nr_topk_desc* d) {
   NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_topk: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
                NR_TOPK_MAX_N);
   NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_topk: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
+  NR_CHECK_ARG(d->n_excl >= 0, "score_topk: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
+  NR_CHECK_ARG(d->E == 0 || d->excl_offsets == nullptr,
+               "score_topk: the dense list (E = %d) and the CSR lists (excl_offsets) are not combined: one list form per call", d->E);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
+               "score_topk: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
+               "score_topk: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= tk_max_splits(d->k), "score_topk: splits = %d, must be 0 (library's choice) or in [1, %d] for k = %d",
                d->splits, tk_max_splits(d->k), d->k);
   NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_topk: stamp given without window (the two come together)");
@@ -363,27 +418,35 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   const GroupArgs ga = {d->group, d->group_cap};
   const bool pool = a.pool.any();
   const bool grouped = d->group != nullptr;
+  const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
+  const CsrArgs ca = {csr ? d->excl_offsets : nullptr, csr ? d->excl_ids : nullptr, csr ? d->n_excl : 0};
   const size_t smem = tk_lds_bytes(TU, d->N, d->k);
   const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
   {
     NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
-#define NR_TOPK_LAUNCH(MT, POOL, GROUP)                                                                                                            \
-  do {                                                                                                                                             \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int)smem));                                                                                                  \
-    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP>), grid, dim3(TK_THREADS), smem, s, a, ga);                                                \
+#define NR_TOPK_LAUNCH(MT, POOL, GROUP, CSR)                                                                                   \
+  do {                                                                                                                         \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP, CSR>),                  \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                  \
+    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP, CSR>), grid, dim3(TK_THREADS), smem, s, a, ga, ca);                \
   } while (0)
-#define NR_TOPK_LAUNCH_MT(MT)                            \
-  do {                                                   \
-    if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true); \
-    else if (pool) NR_TOPK_LAUNCH(MT, true, false);      \
-    else if (grouped) NR_TOPK_LAUNCH(MT, false, true);   \
-    else NR_TOPK_LAUNCH(MT, false, false);               \
+#define NR_TOPK_LAUNCH_PG(MT, CSR)                            \
+  do {                                                        \
+    if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR); \
+    else if (pool) NR_TOPK_LAUNCH(MT, true, false, CSR);      \
+    else if (grouped) NR_TOPK_LAUNCH(MT, false, true, CSR);   \
+    else NR_TOPK_LAUNCH(MT, false, false, CSR);               \
+  } while (0)
+#define NR_TOPK_LAUNCH_MT(MT)            \
+  do {                                   \
+    if (csr) NR_TOPK_LAUNCH_PG(MT, true); \
+    else NR_TOPK_LAUNCH_PG(MT, false);   \
   } while (0)
     if (TU == 64) NR_TOPK_LAUNCH_MT(4);
     else if (TU == 32) NR_TOPK_LAUNCH_MT(2);
     else NR_TOPK_LAUNCH_MT(1);
 #undef NR_TOPK_LAUNCH_MT
+#undef NR_TOPK_LAUNCH_PG
 #undef NR_TOPK_LAUNCH
   }
   NR_CHECK_LAUNCH();

@@ -70,8 +70,10 @@ def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window
     `a` is the score matrix [U, V], or, with `b` given, the news vectors [V, N] and `b` the user vectors [U, N]: the scores
     are then <a[v], b[u]> in float64.  Per user the k best news in the total order (score descending, news id ascending):
     news 0 (the padding row) is never eligible, nor is an id listed in exclude[u] (entries that are 0 or outside [1, V) mean
-    nothing, duplicates are allowed), nor a news whose score is NaN.  A row with fewer than k eligible news is filled with
-    id 0, score -inf.  Returns (ids int32 [U, k], scores float64 [U, k]).
+    nothing, duplicates are allowed), nor a news whose score is NaN.  exclude may be ragged: exclude[u] is any sequence of
+    ids, of any length and in any order -- the dense list of the library and its CSR lists (ops.ExclusionLists) are both
+    stated by it.  A row with fewer than k eligible news is filled with id 0, score -inf.
+    Returns (ids int32 [U, k], scores float64 [U, k]).
     Pools: prior [V] is added to the scores (the returned scores are the sums) and -inf in it removes a news for everybody;
     stamp [V] with window [U, 2] keeps for user u the news with window[u, 0] <= stamp[v] <= window[u, 1] (_pooled).
     Group caps: group [V] integer ids (negative = in no group) with group_cap = c in [1, 128], together: the row is the walk
@@ -116,7 +118,7 @@ def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, 
     """Host statement of the full-corpus rank contract (include/nrhip.h, nr_score_rank); tests check the device against it, no
     product path calls it.
 
-    `a`, `b`, `exclude` and the total order (score descending, news id ascending) are topk_reference's.  targets [U, T] int:
+    `a`, `b`, `exclude` (ragged, any length) and the total order (score descending, news id ascending) are topk_reference's.  targets [U, T] int:
     entries that are 0 or outside [1, V) mean nothing.  The eligible news of user u are the ids 1 .. V-1 that are not in
     exclude[u] and whose score is not NaN; rank[u, j] is the 1-based position of targets[u, j] among them in that order, and 0
     ("not ranked") when the target means nothing, is excluded, has a NaN score or repeats an earlier entry of its row.

@@ -1014,12 +1014,146 @@ def _pool_args(what, V, U, dev, prior, stamp, window):
     return p, s, w
 
 
+class ExclusionLists:
+    """Per-user exclusion lists of any length in the CSR form nr_score_topk / nr_score_rank take (include/nrhip.h, K9):
+    `offsets` int32 [U + 1] and `ids` int32 [nnz], user u's list = ids[offsets[u] : offsets[u + 1]], in canonical form -- per user
+    sorted, unique, only ids >= 1.  Build it once per batch of users and hand it to as many score_topk / score_rank calls as
+    needed (`exclude=`); it lives on the device of what it was built from (or `device=`), and works on the CPU as well.
+      ExclusionLists(t)                  t: integer tensor [U, E] of any width E; 0 or negative = no entry
+      ExclusionLists([a_0, ..., a_U-1])  a sequence of U one-dimensional id arrays (tensors, numpy arrays, lists), any lengths
+      ExclusionLists.from_sorted(offsets, ids)   trusts the caller: nothing is sorted, checked or cleaned (the raw contract)
+    Duplicates, zeros, negatives and any order are fine in the first two; ids >= V are kept and mean nothing to the kernels.
+    Canonicalisation is torch index arithmetic: one sort of the keys u * 2^31 + id, unique_consecutive, bincount -> offsets.
+    More than 2^31 - 1 entries, or an id above 2^31 - 1, is refused."""
+
+    _ID_BITS = 31
+
+    def __init__(self, lists, device=None):
+        if isinstance(lists, torch.Tensor):
+            if lists.dim() != 2 or lists.is_floating_point() or lists.is_complex() or lists.dtype == torch.bool:
+                raise RuntimeError(f"ExclusionLists: a tensor must be an integer [U, E], got {tuple(lists.shape)} {lists.dtype}")
+            t = lists.detach()
+            if device is not None:
+                t = t.to(device)
+            U = t.shape[0]
+            users = torch.arange(U, device=t.device, dtype=torch.int64)[:, None].expand(U, t.shape[1]).reshape(-1)
+            flat = t.reshape(-1).to(torch.int64)
+        else:
+            rows = [torch.as_tensor(r).reshape(-1) for r in lists]
+            for r in rows:
+                if r.numel() and (r.is_floating_point() or r.is_complex() or r.dtype == torch.bool):
+                    raise RuntimeError(f"ExclusionLists: id arrays must be integers, got {r.dtype}")
+            U = len(rows)
+            dev = torch.device(device) if device is not None else (rows[0].device if rows else torch.device("cpu"))
+            lens = torch.tensor([r.numel() for r in rows], dtype=torch.int64)
+            flat = torch.cat([r.to(torch.int64) for r in rows]).to(dev) if rows else torch.zeros(0, dtype=torch.int64, device=dev)
+            users = torch.repeat_interleave(torch.arange(U, dtype=torch.int64), lens).to(dev)
+        self.offsets, self.ids = self._canonical(users, flat, U)
+
+    @classmethod
+    def _canonical(cls, users, flat, U):
+        """offsets, ids of the (user, id) pairs: ids >= 1 only, per user sorted and unique."""
+        keep = flat >= 1
+        users, flat = users[keep], flat[keep]
+        if flat.numel() and int(flat.max()) >= (1 << cls._ID_BITS):
+            raise RuntimeError(f"ExclusionLists: news id {int(flat.max())} does not fit int32")
+        keys = torch.unique_consecutive(torch.sort((users << cls._ID_BITS) + flat).values)
+        if keys.numel() > (1 << 31) - 1:
+            raise RuntimeError(f"ExclusionLists: {keys.numel()} entries, at most 2^31 - 1")
+        counts = torch.bincount(keys >> cls._ID_BITS, minlength=U)
+        offsets = torch.zeros(U + 1, dtype=torch.int64, device=keys.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        return offsets.to(torch.int32), (keys & ((1 << cls._ID_BITS) - 1)).to(torch.int32)
+
+    @classmethod
+    def from_sorted(cls, offsets, ids):
+        """The arrays as they are (converted to contiguous int32 only): per user strictly ascending is the CALLER'S promise."""
+        offsets, ids = torch.as_tensor(offsets), torch.as_tensor(ids)
+        if offsets.dim() != 1 or offsets.numel() < 1 or ids.dim() != 1 or offsets.device != ids.device:
+            raise RuntimeError(f"ExclusionLists.from_sorted: offsets [U + 1] and ids [nnz] on one device, got {tuple(offsets.shape)} on "
+                               f"{offsets.device} and {tuple(ids.shape)} on {ids.device}")
+        if ids.numel() > (1 << 31) - 1:
+            raise RuntimeError(f"ExclusionLists: {ids.numel()} entries, at most 2^31 - 1")
+        self = cls.__new__(cls)
+        self.offsets, self.ids = offsets.detach().to(torch.int32).contiguous(), ids.detach().to(torch.int32).contiguous()
+        return self
+
+    @property
+    def U(self) -> int:
+        return self.offsets.numel() - 1
+
+    @property
+    def device(self):
+        return self.ids.device
+
+    def __len__(self) -> int:
+        return self.U
+
+    def to(self, device):
+        """The same lists on `device` (self if they are there already)."""
+        if torch.device(device) == self.device:
+            return self
+        return ExclusionLists.from_sorted(self.offsets.to(device), self.ids.to(device))
+
+    def _pairs(self):
+        """(user, id) of every entry, int64."""
+        counts = (self.offsets[1:] - self.offsets[:-1]).to(torch.int64)
+        return torch.repeat_interleave(torch.arange(self.U, device=self.device, dtype=torch.int64), counts), self.ids.to(torch.int64)
+
+    def take(self, rows):
+        """The lists of users rows[i], i = 0 .. len(rows) - 1 (repeats and any order allowed), as a new object."""
+        rows = torch.as_tensor(rows).to(device=self.device, dtype=torch.int64).reshape(-1)
+        off = self.offsets.to(torch.int64)
+        counts = (off[1:] - off[:-1])[rows]
+        new_off = torch.zeros(rows.numel() + 1, dtype=torch.int64, device=self.device)
+        new_off[1:] = torch.cumsum(counts, 0)
+        if int(new_off[-1]) > (1 << 31) - 1:
+            raise RuntimeError(f"ExclusionLists: {int(new_off[-1])} entries, at most 2^31 - 1")
+        src = torch.arange(int(new_off[-1]), device=self.device) + torch.repeat_interleave(off[:-1][rows] - new_off[:-1], counts)
+        return ExclusionLists.from_sorted(new_off, self.ids[src])
+
+    def merged(self, other):
+        """The per-user union with `other` (an ExclusionLists of the same U, or anything the constructor takes)."""
+        if not isinstance(other, ExclusionLists):
+            other = ExclusionLists(other, device=self.device)
+        if other.U != self.U:
+            raise RuntimeError(f"ExclusionLists.merged: {self.U} users against {other.U}")
+        (ua, ia), (ub, ib) = self._pairs(), other._pairs()
+        out = ExclusionLists.__new__(ExclusionLists)
+        out.offsets, out.ids = self._canonical(torch.cat([ua, ub.to(self.device)]), torch.cat([ia, ib.to(self.device)]), self.U)
+        return out
+
+
+def _exclude_args(what, exclude, U, dev):
+    """`exclude` of score_topk / score_rank as descriptor fields: the dense list (a tensor [U, E <= 64]: exclude, ld_exclude, E, as
+    always) or the CSR lists (a wider tensor or an ExclusionLists: excl_offsets, excl_ids, n_excl).  Returns (fields, keepalive)."""
+    if exclude is None:
+        return {"exclude": None, "ld_exclude": 0, "E": 0}, None
+    if isinstance(exclude, torch.Tensor):
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"{what}: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        E = exclude.shape[1]
+        if E <= _lib.NR_TOPK_MAX_EXCLUDE:
+            ex = exclude.detach().to(torch.int32).contiguous() if E else None
+            return {"exclude": ptr(ex), "ld_exclude": E, "E": E}, ex
+        exclude = ExclusionLists(exclude)
+    if not isinstance(exclude, ExclusionLists):
+        raise RuntimeError(f"{what}: exclude must be a tensor [U, E] or an ExclusionLists, got {type(exclude)}")
+    if exclude.U != U or exclude.device != dev:
+        raise RuntimeError(f"{what}: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
+    n = exclude.ids.numel()
+    return {"exclude": None, "ld_exclude": 0, "E": 0, "excl_offsets": ptr(exclude.offsets), "excl_ids": ptr(exclude.ids) if n else None,
+            "n_excl": n}, exclude
+
+
 @torch.no_grad()
 def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stamp=None, window=None, group=None, group_cap=None):
     """Full-corpus recommendation (nr_score_topk): for every user the k best news of the whole table under the order (score
     descending, news id ascending), score[u, v] = <news_vecs[v], user_vecs[u]> in exact fp32.  Row 0 of `news_vecs` (the
     padding news) is never returned; `exclude` ([U, E <= 64] news ids per user, 0 = no entry) neither.  No [U, V] score matrix
-    is formed.  Returns (ids int32 [U, k], scores fp32 [U, k]); a row with fewer than k eligible news ends in id 0, score -inf.
+    is formed.  A wider `exclude` tensor or an ExclusionLists (lists of any length, "everything this user was shown") goes
+    through the CSR lists of the library (include/nrhip.h, K9) -- same rows, same bits, as long as E <= 64 could hold them; a
+    tensor of at most 64 columns takes the dense path exactly as it always did.  Returns (ids int32 [U, k], scores fp32 [U, k]); a row with fewer than k eligible news ends in id 0, score -inf.
     `splits`: 0 = the library chooses the number of corpus slices; tests force it.
     Pools (include/nrhip.h, K9): `prior` [V] floating point -- the score becomes fl32(dot + prior[v]), one fp32 add after the
     dot product, and the returned scores are these sums; -inf in it takes a news out for every user.  `stamp` [V] and `window`
@@ -1030,7 +1164,7 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
     news of its group are taken, so at most c per group and still k entries where k can be taken (otherwise the usual fill).
     One without the other is refused by the library.  Without them the call launches the kernels it always launched.
     score_rank knows no caps: a capped row is a subsequence of the uncapped order."""
-    _need_gpu(news_vecs, user_vecs, exclude, prior, stamp, window, group)
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_topk: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1044,12 +1178,7 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
     scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
     if U == 0:
         return ids, scores
-    ex, E = None, 0
-    if exclude is not None:
-        if exclude.dim() != 2 or exclude.shape[0] != U:
-            raise RuntimeError(f"score_topk: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
-        E = exclude.shape[1]
-        ex = exclude.detach().to(torch.int32).contiguous() if E else None
+    ex_fields, ex_keep = _exclude_args("score_topk", exclude, U, dev)
     pr, st, win = _pool_args("score_topk", V, U, dev, prior, stamp, window)
     gr = None
     if group is not None:
@@ -1058,7 +1187,7 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
                                f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
         gr = group.detach().contiguous()
     d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
-                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), exclude=ptr(ex), ld_exclude=E, E=E,
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), **ex_fields,
                       splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
                       ld_window=2 if win is not None else 0, group=ptr(gr), group_cap=0 if group_cap is None else int(group_cap))
     ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
@@ -1072,14 +1201,15 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, pri
     """Full-corpus rank evaluation (nr_score_rank): for every user and each of its targets ([U, T <= 64] news ids, 0 = no entry)
     the exact 1-based position of that news among the user's eligible news of the whole table, in score_topk's order and with
     score_topk's score bits: 1 <= rank <= k exactly when the target is in the user's top-k row.  Rank 0, score -inf: the target
-    is 0 or out of range, is in `exclude` ([U, E <= 64]), has a NaN score or repeats an earlier entry of its row.  No [U, V]
+    is 0 or out of range, is in `exclude` ([U, E <= 64]; wider, or an ExclusionLists of any length: the CSR lists, as in
+    score_topk), has a NaN score or repeats an earlier entry of its row.  No [U, V]
     score matrix is formed.  Returns (ranks int32 [U, T], scores fp32 [U, T], sums): with cut-offs `ks` (at most 8) sums is a
     DEVICE fp64 tensor [2 + 2 len(ks)] = [users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u]
     (metrics.retrieval_metrics_reference states the per-user terms); with ks=None no sums are formed and None is returned.
     `splits`: 0 = the library chooses the number of corpus slices; tests force it.
     Pools: `prior`, `stamp`, `window` as in score_topk, with the same score fl32(dot + prior) and the same eligible news, so the
     agreement with score_topk's rows holds for equal pool inputs.  A target outside its user's pool has rank 0, score -inf."""
-    _need_gpu(news_vecs, user_vecs, targets, exclude, prior, stamp, window)
+    _need_gpu(news_vecs, user_vecs, targets, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_rank: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1100,17 +1230,12 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, pri
         return ranks, scores, torch.zeros(2 + 2 * len(ks), dtype=torch.float64, device=dev) if want_sums else None
     sums = torch.empty(2 + 2 * len(ks), dtype=torch.float64, device=dev) if want_sums else None     # the call overwrites it
     tg = targets.detach().to(torch.int32).contiguous()
-    ex, E = None, 0
-    if exclude is not None:
-        if exclude.dim() != 2 or exclude.shape[0] != U:
-            raise RuntimeError(f"score_rank: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
-        E = exclude.shape[1]
-        ex = exclude.detach().to(torch.int32).contiguous() if E else None
+    ex_fields, ex_keep = _exclude_args("score_rank", exclude, U, dev)
     ks_host = (C.c_int * max(len(ks), 1))(*ks)
     pr, st, win = _pool_args("score_rank", V, U, dev, prior, stamp, window)
     d = _lib.RankDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
-                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, exclude=ptr(ex),
-                      ld_exclude=E, E=E, splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, **ex_fields,
+                      splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
                       out_sums=ptr(sums), prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
     ws = _ws(_lib.lib().nr_score_rank_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4

@@ -330,15 +330,37 @@ def _pool_kwargs(device, prior, news_time, window):
     return kw
 
 
+def _exclusions(hist, m, exclude_history, seen, device):
+    """What recommend / rank_eval hand to ops.score_topk / ops.score_rank as `exclude`: None, the masked history as a tensor [U, H]
+    (H <= 64: the dense list, the call as it always was) or an ops.ExclusionLists (a wider history, or any `seen`: history
+    union seen, of any length)."""
+    masked = None
+    if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
+        masked = (hist * (m != 0).to(torch.int32)).contiguous()
+    if seen is None:
+        if masked is not None and masked.shape[1] > _lib.NR_TOPK_MAX_EXCLUDE:
+            return ops.ExclusionLists(masked)
+        return masked
+    lists = seen.to(device) if isinstance(seen, ops.ExclusionLists) else ops.ExclusionLists(seen, device=device)
+    if lists.U != hist.shape[0]:
+        raise RuntimeError(f"seen: lists for {lists.U} users, the call has {hist.shape[0]}")
+    return lists if masked is None else lists.merged(masked)
+
+
 @torch.no_grad()
 def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None,
-              news_group=None, group_cap=None):
+              news_group=None, group_cap=None, seen=None):
     """Full-corpus recommendation: for every user the k best news of the whole table `news_vecs` ([N+1, news_dim], what
     encode_news returns), none of them the padding news 0.  hist_idx [U, H]: the users' clicked histories as news indices,
     front padded with 0 (src/dataset.py:17-24); mask [U, H]: 1 for a real slot.  The user vectors come from the code
     score_shard uses (_user_vectors); scoring and selection are one fused pass (ops.score_topk): no [U, V] score matrix.
-    exclude_history: a user is not given what they already clicked.  The kernel takes at most 64 excluded ids per user: of a
-    history wider than 64 slots only the LAST 64 (the most recent clicks) are excluded.
+    exclude_history: a user is not given what they already clicked -- the WHOLE history, whatever its width.  A history of at
+    most 64 slots goes through the kernel's dense list (64 ids per user is where that path ends); a wider one goes through
+    exclusion lists of any length (ops.ExclusionLists, the CSR lists of include/nrhip.h K9).
+    seen: news a user must not be given beyond its history -- "everything this user has been shown", hundreds to thousands of
+    ids: an ops.ExclusionLists (build it once per batch of users), a tensor [U, E] of any width (0 = no entry) or a sequence
+    of U id arrays.  The row is then the k best of what is left, still k entries wherever k can be taken: the filter acts
+    inside the selection, not on a finished row.
     Returns (ids int32 [U, k], scores fp32 [U, k]) on the device, rows sorted by (score descending, id ascending); a row with
     fewer than k eligible news ends in id 0, score -inf.  Several ranks: the caller shards the users; there is no collective.
     Pools (ops.score_topk): prior [N+1] -- a per-news freshness or popularity term added to the score in fp32, -inf = not in
@@ -353,9 +375,7 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
     news_vecs = news_vecs.detach().float().contiguous()
     user = _user_vectors(model, news_vecs, hist, m, batch_size, device, _Histories(mask))
-    exclude = None
-    if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
-        exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
     kw = _pool_kwargs(device, prior, news_time, window)
     if news_group is not None:
         kw["group"] = torch.as_tensor(news_group).to(device=device, dtype=torch.int32)
@@ -384,10 +404,12 @@ def _retrieval_sums(ranks, ks):
 
 @torch.no_grad()
 def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclude_history=True, batch_size=8192, prior=None, news_time=None,
-              window=None):
+              window=None, seen=None):
     """Full-corpus retrieval evaluation: where does each held-out click of a user stand in that user's ranking of the WHOLE
-    table `news_vecs`?  hist_idx, mask, exclude_history and the user vectors are recommend's (_user_vectors; of a history wider
-    than 64 slots only the LAST 64 are excluded); targets [U, T]: the held-out news indices of every user, 0 = no entry.
+    table `news_vecs`?  hist_idx, mask, exclude_history, seen and the user vectors are recommend's (_user_vectors; the whole
+    history is excluded: up to 64 slots through the kernel's dense list, a wider one -- or any `seen`, the further news per
+    user that are out of the ranking -- through ops.ExclusionLists, lists of any length); targets [U, T]: the held-out news
+    indices of every user, 0 = no entry.
     Scoring and counting are one fused pass (ops.score_rank): no [U, V] score matrix, and the ranks agree with recommend's
     rows exactly (1 <= rank <= k exactly when the target is in the user's top-k row).
     Returns (ranks int32 [U, T], scores fp32 [U, T], sums fp64 [2 + 2 len(ks)]) on the device: rank 0 / score -inf for an entry
@@ -408,9 +430,7 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
     news_vecs = news_vecs.detach().float().contiguous()
     user = _user_vectors(model, news_vecs, hist, m, batch_size, device, _Histories(mask))
-    exclude = None
-    if exclude_history and hist.dim() == 2 and hist.shape[1] > 0:
-        exclude = (hist * (m != 0).to(torch.int32))[:, -_lib.NR_TOPK_MAX_EXCLUDE:].contiguous()
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
     U, T = tg.shape
     W = _lib.NR_RANK_MAX_TARGETS
     pool = _pool_kwargs(device, prior, news_time, window)
@@ -432,8 +452,11 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     row_tg = (comp[row_user[:, None], cols] * live).contiguous()
     if "window" in pool:
         pool["window"] = pool["window"][row_user].contiguous()
-    r, sc, _ = ops.score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=None if exclude is None else exclude[row_user].contiguous(),
-                              ks=None, **pool)
+    if isinstance(exclude, ops.ExclusionLists):
+        row_excl = exclude.take(row_user)                     # the rows of a user share its lists
+    else:
+        row_excl = None if exclude is None else exclude[row_user].contiguous()
+    r, sc, _ = ops.score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=row_excl, ks=None, **pool)
     ranks_c = torch.zeros(U, T, dtype=torch.int32, device=device)
     scores_c = torch.full((U, T), float("-inf"), dtype=torch.float32, device=device)
     ru = row_user[:, None].expand_as(cols)
@@ -458,11 +481,13 @@ def _shard_targets(shard: IndexedTestShard):
 
 
 @torch.no_grad()
-def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100), prior=None, news_time=None, window=None):
+def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100), prior=None, news_time=None, window=None, seen=None):
     """rank_eval over the impressions of a test shard: every impression is one user (its history), its targets are the news it
     clicked, cand[label == 1] per CSR row in list order, rows back padded with 0.  Returns rank_eval's (ranks, scores, sums).
-    prior, news_time, window: rank_eval's pools, window [impressions, 2]; the shard holds no times, the caller supplies them."""
-    return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks, prior=prior, news_time=news_time, window=window)
+    prior, news_time, window: rank_eval's pools, window [impressions, 2]; the shard holds no times, the caller supplies them.
+    seen: rank_eval's, one list per impression."""
+    return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks, prior=prior, news_time=news_time, window=window,
+                     seen=seen)
 
 
 @torch.no_grad()

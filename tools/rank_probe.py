@@ -3,7 +3,7 @@
 the same device.
 
     python tools/rank_probe.py [--news 100001] [--dim 400] [--targets 4] [--exclude 50] [--users 64 8192] [--block 1024]
-                               [--calls 30] [--warmup 5] [--out FILE] [--pool]
+                               [--calls 30] [--warmup 5] [--out FILE] [--pool] [--seen L]
 
 Both sides take the same fp32 inputs.  The baseline forms the [block, V] scores of a block of users, reads the targets' scores
 out of them and counts, per target, the news that score strictly higher (what the excluded ones contribute is taken back from
@@ -14,7 +14,11 @@ reported, with the peak device memory of one call above what the inputs occupy. 
 counts the algorithmic 2 * U * V * N FLOPs over the WHOLE call (all launches), against 157.3 TFLOP/s.
 One JSON line per U, and a last line with the two requirements at the largest U.  Needs a GPU: there is nothing to fall back to.
 --pool: instead of the baseline, the same fused call with a prior and a window (ops.score_rank(..., prior=, stamp=, window=)) at
-the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio."""
+the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio.
+--seen L: likewise, the fused call with a list of L random ids per user through the CSR path (ops.ExclusionLists, built once)
+alternating with the fused call with the dense list (--exclude ids per user); one JSON line per U with both, the ratio of the
+medians and, from the library's own launch timer, the share of the named-id pass in each call beside the arithmetic
+2 % x (1 + ceil((L - 64) / 128))."""
 import argparse
 import json
 import os
@@ -24,7 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from newsrecommendation_amd import ops  # noqa: E402
+from newsrecommendation_amd import _lib, ops  # noqa: E402
 
 PEAK_FP32_MATRIX = 157.3e12
 KS = (5, 10, 100)
@@ -106,6 +110,22 @@ def pool_row(plain, pooled, calls, warmup):
     return row
 
 
+def named_share(call, reps=5):
+    """The share of the named-id pass in the launches of `call`, by the library's per-launch timer."""
+    call()
+    torch.cuda.synchronize()
+    _lib.prof_enable(1)
+    _lib.prof_collect()
+    for _ in range(reps):
+        call()
+    torch.cuda.synchronize()
+    got = _lib.prof_collect()
+    _lib.prof_enable(0)
+    total = sum(ms for _, ms in got.values())
+    named = sum(ms for label, (_, ms) in got.items() if label.startswith("rank_named"))
+    return round(named / total, 4) if total > 0 else None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--news", type=int, default=100001)
@@ -118,7 +138,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--pool", action="store_true", help="time the pooled fused call against the plain fused call")
+    ap.add_argument("--seen", type=int, default=0, help="time the fused call with L random ids per user in CSR lists against the dense list")
     args = ap.parse_args()
+    if args.seen and args.pool:
+        raise SystemExit("--seen L comes alone")
     if not torch.cuda.is_available():
         raise SystemExit("rank_probe needs a GPU")
     if args.calls < 20:
@@ -137,6 +160,18 @@ def main():
         named = ((start + torch.arange(n_named)[None, :] * step) % (args.news - 1) + 1).to(torch.int32).cuda()
         targets, exclude = named[:, :args.targets].contiguous(), named[:, args.targets:].contiguous()
         a = (news, user, targets, exclude, min(args.block, U))
+        if args.seen:
+            lists = ops.ExclusionLists(torch.randint(1, args.news, (U, args.seen), generator=g, dtype=torch.int32).cuda())
+            csr = lambda: ops.score_rank(news, user, targets, exclude=lists, ks=KS)
+            row = {"U": U, "V": args.news, "N": args.dim, "T": args.targets, "E": args.exclude, "seen": args.seen, "listed_ids": int(lists.ids.numel())}
+            got = pool_row(lambda: fused(*a), csr, args.calls, args.warmup)
+            row.update({"mode": "seen", "dense": got["plain"], "csr": got["pooled"]})
+            row["csr_over_dense"] = round(row["csr"]["median_ms"] / row["dense"]["median_ms"], 4)
+            row["named_share_dense"], row["named_share_csr"] = named_share(lambda: fused(*a)), named_share(csr)
+            row["named_share_formula"] = round(0.02 * (1 + max(0, -(-(args.seen - 64) // 128))), 4)
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if args.pool:
             prior, stamp, window = pool_inputs(args.news, U, g)
             pooled = lambda: ops.score_rank(news, user, targets, exclude=exclude, ks=KS, prior=prior, stamp=stamp, window=window)
@@ -168,7 +203,7 @@ def main():
         lines.append(row)
         print(json.dumps(row), flush=True)
         del user
-    if args.pool:
+    if args.pool or args.seen:
         write(args.out, lines)
         return
     last = lines[-1]

@@ -2,7 +2,7 @@
 """Full-corpus top-k recommendation: the fused call (ops.score_topk) against torch.matmul + torch.topk on the same device.
 
     python tools/topk_probe.py [--news 100001] [--dim 400] [--k 10] [--users 64 8192] [--calls 30] [--warmup 5] [--out FILE] [--pool]
-                                [--group G --group-cap C]
+                                [--group G --group-cap C] [--seen L]
 
 Both sides take the same fp32 inputs.  Per U: every call is timed with a pair of device events, the two sides alternate call
 by call (so that a disturbance of the machine hits both), and the median, minimum, maximum and inter-quartile spread of the
@@ -13,7 +13,10 @@ One JSON line per U, and a last line with the two requirements at the largest U.
 the same shapes, alternating with the plain fused call and timed the same way; one JSON line per U with both and their ratio.
 --group G --group-cap C: likewise, the fused call with group caps (ops.score_topk(..., group=, group_cap=C); G random groups,
 MIND has 18 categories) alternating with the plain fused call; one JSON line per U with both, their ratio and the plain call's
-inter-quartile spread beside the difference of the medians."""
+inter-quartile spread beside the difference of the medians.
+--seen L: likewise, the fused call with a list of L random ids per user through the CSR path (ops.ExclusionLists, built once)
+alternating with the fused call with the dense list of 50 random ids per user (E = 50); one JSON line per U with both and the
+ratio of the medians."""
 import argparse
 import json
 import os
@@ -106,6 +109,14 @@ def group_row(plain, capped, calls, warmup):
     return row
 
 
+def seen_row(dense, csr, calls, warmup):
+    """--seen: the fused call with the dense list and the one with CSR lists, alternating, timed as everything else here."""
+    row = pool_row(dense, csr, calls, warmup)
+    row = {"mode": "seen", "dense": row["plain"], "csr": row["pooled"]}
+    row["csr_over_dense"] = round(row["csr"]["median_ms"] / row["dense"]["median_ms"], 4)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--news", type=int, default=100001)
@@ -118,9 +129,12 @@ def main():
     ap.add_argument("--pool", action="store_true", help="time the pooled fused call against the plain fused call")
     ap.add_argument("--group", type=int, default=0, help="with --group-cap: time the capped fused call (this many random groups) against the plain one")
     ap.add_argument("--group-cap", type=int, default=0)
+    ap.add_argument("--seen", type=int, default=0, help="time the fused call with L random ids per user in CSR lists against the dense list of 50")
     args = ap.parse_args()
     if (args.group > 0) != (args.group_cap > 0) or (args.group > 0 and args.pool):
         raise SystemExit("--group G and --group-cap C come together, and not with --pool")
+    if args.seen and (args.pool or args.group):
+        raise SystemExit("--seen L comes alone")
     if not torch.cuda.is_available():
         raise SystemExit("topk_probe needs a GPU")
     if args.calls < 20:
@@ -130,6 +144,15 @@ def main():
     lines = []
     for U in args.users:
         user = (torch.randn(U, args.dim, generator=g) * 0.4).cuda()
+        if args.seen:
+            dense = torch.randint(1, args.news, (U, 50), generator=g, dtype=torch.int32).cuda()
+            lists = ops.ExclusionLists(torch.randint(1, args.news, (U, args.seen), generator=g, dtype=torch.int32).cuda())
+            row = {"U": U, "V": args.news, "N": args.dim, "k": args.k, "E": 50, "seen": args.seen, "listed_ids": int(lists.ids.numel())}
+            row.update(seen_row(lambda: ops.score_topk(news, user, args.k, exclude=dense), lambda: ops.score_topk(news, user, args.k, exclude=lists),
+                                args.calls, args.warmup))
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+            continue
         if args.group:
             group = torch.randint(0, args.group, (args.news,), generator=g, dtype=torch.int32).cuda()
             row = {"U": U, "V": args.news, "N": args.dim, "k": args.k, "groups": args.group, "group_cap": args.group_cap}
@@ -170,7 +193,7 @@ def main():
         lines.append(row)
         print(json.dumps(row), flush=True)
         del user
-    if args.pool or args.group:
+    if args.pool or args.group or args.seen:
         write(args.out, lines)
         return
     last = lines[-1]
