@@ -417,10 +417,10 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  * slice lists with the same rule; the workspace size does not depend on these fields either.
  * Slow case, exact but not fast: while a user's list cannot fill (G * c < k and few ungrouped news) its threshold never
  * rises, and every chunk of the corpus goes through the per-candidate path for that user.
- * nr_score_rank does NOT know caps: it keeps describing the uncapped ranking.  What holds across the two: a capped row is a
- * subsequence of the uncapped order, so the uncapped rank of the entry at place p (0-based) is >= p + 1, the ranks along a
- * row increase strictly, and the scores are the rank pass's bit for bit.  A capped rank would need per-(user, target,
- * group) counters; it is not offered.
+ * nr_score_rank knows the same caps (K10, group / group_cap / n_groups): with equal inputs its capped rank is the place in this
+ * row.  Without them it describes the uncapped ranking, of which a capped row is a subsequence: the uncapped rank of the
+ * entry at place p (0-based) is >= p + 1, the ranks along a row increase strictly, and the scores are the rank pass's bit
+ * for bit.
  * Exclusion lists of any length (optional; excl_offsets == NULL, excl_ids == NULL, n_excl == 0 = off, and the call then
  * launches the kernel instantiations it always launched).  Shared with nr_score_rank.  The dense list above stops at 64 ids;
  * "everything this user has been shown" is hundreds to thousands, so it comes in CSR form:
@@ -506,9 +506,45 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream);
  * call always launched; the same refusals).  A target found in its user's segment is "not ranked"; a listed news takes one
  * off the rank of every target it beats, if it is in range and eligible (not NaN, inside the pool).  The named-id pass then
  * takes a user's list through further chunks of 128 gathered rows (the first 64 ids ride with the targets); the counting
- * pass, the finalize pass and the workspace are unchanged.  The agreement with nr_score_topk holds for equal lists.       */
+ * pass, the finalize pass and the workspace are unchanged.  The agreement with nr_score_topk holds for equal lists.
+ * Group caps (optional; group == NULL, group_cap == 0, n_groups == 0 = off: the call as it is without them -- the same
+ * launches, the same workspace bytes): the rank in the CAPPED ranking nr_score_topk(..., group, group_cap) serves.
+ *   group      [V] int32, one group id per news; a negative id = belongs to no group (as in nr_topk_desc)
+ *   group_cap  c in [1, NR_TOPK_MAX_K]
+ *   n_groups   G in [1, NR_RANK_MAX_GROUPS]: the group ids lie in [0, G)
+ *   T          at most NR_RANK_MAX_CAPPED_TARGETS per row in a capped call (lay a user with more over several rows)
+ * "Eligible" means what it means above: id in [1, V), not excluded (dense list or CSR list), score not NaN, prior not -inf,
+ * stamp inside the user's window.  For user u and target t, in the total order (score descending, id ascending), let n_g(t)
+ * be the number of eligible news of group g that beat t and n_-(t) the number of eligible ungrouped news that beat t; the
+ * uncapped rank is 1 + n_-(t) + sum_g n_g(t).  The capped walk of nr_score_topk takes exactly the first c news of each
+ * group, so
+ *   t is CAPPED OUT when group[t] >= 0 and n_{group[t]}(t) >= c: it is in no capped row for any k;
+ *   otherwise capped_rank(t) = 1 + n_-(t) + sum_g min(c, n_g(t)) = uncapped_rank(t) - sum_g max(0, n_g(t) - c).
+ * What is not eligible uses up nothing of a cap (an excluded or listed id, a NaN news, a news outside the pool): the
+ * named-id pass takes back, PER GROUP, the excluded / listed news that beat the target (in range and with key != 0 only, each
+ * once), and the stream never counts a key-0 news.
+ *   out_ranks   the capped rank; 0 with score -inf for what is not ranked today (no entry, out of range, excluded, NaN, outside
+ *               the pool, a repeat); -1 WITH ITS FINITE SCORE for a capped-out target: a legitimate held-out click that this
+ *               recommender can never show
+ *   out_sums    n_u counts the targets with rank != 0; a rank of -1 adds nothing to MRR, Recall@k or nDCG@k; the ideal DCG
+ *               stays sum_{i <= min(n_u, k)} 1 / log2(i + 1) -- the ideal is what an uncapped recommender could have shown,
+ *               so a cap that hides clicks lowers nDCG@k instead of shrinking its denominator.  Without a negative rank the
+ *               sums are what they are without caps, bit for bit.
+ * For equal inputs, 1 <= capped_rank <= k exactly when the target is at place capped_rank - 1 of the row of
+ * nr_score_topk(..., group, group_cap), with identical score bits, for every k <= 128.
+ * Refused (nr_last_error): group without a cap in [1, 128]; a cap, or n_groups, without group; n_groups outside [1, 512]
+ * with group; T > NR_RANK_MAX_CAPPED_TARGETS with group.  A group id >= n_groups gives unspecified ranks for the users it
+ * concerns, never an access outside the workspace: the kernels treat such a news as ungrouped (the library does not
+ * synchronise to validate device arrays, as with the CSR lists).
+ * Cost: one prep launch per call (two 64-bit "news of this chunk in group g" masks per chunk of 128 ids and group), one memset
+ * of the [U, T, G] int32 counters, and in the counting pass about 8 VALU instructions per (chunk, user, real target, block of
+ * 64 groups).  The per-(user, target, group) counters are integers, added with integer atomics once per slice: the result does
+ * not depend on splits, the user tile or any arrival order.  Workspace: + U * T * (G + 2) * 4 + chunks * G * 16 bytes.
+ * Layout: group, group_cap, n_groups sit behind out_sums, in front of the shared tail.                                     */
 #define NR_RANK_MAX_TARGETS 64
 #define NR_RANK_MAX_KS 8
+#define NR_RANK_MAX_GROUPS 512
+#define NR_RANK_MAX_CAPPED_TARGETS 4
 typedef struct {
   const float* news_vecs;
   int ld_news, V;
@@ -528,6 +564,9 @@ typedef struct {
   int32_t* out_ranks;
   float* out_scores;
   double* out_sums;
+  const int32_t* group;  /* optional [V]: group id per news, negative = no group; with group_cap and n_groups */
+  int group_cap;         /* 1 .. NR_TOPK_MAX_K with group, 0 without */
+  int n_groups;          /* 1 .. NR_RANK_MAX_GROUPS with group, 0 without: group ids lie in [0, n_groups) */
   void* ws;
   size_t ws_bytes;
   const float* prior;    /* optional [V] */

@@ -77,6 +77,7 @@ class TopkDesc(C.Structure):
 
 
 NR_RANK_MAX_TARGETS, NR_RANK_MAX_KS = 64, 8
+NR_RANK_MAX_GROUPS, NR_RANK_MAX_CAPPED_TARGETS = 512, 4
 
 
 class RankDesc(C.Structure):
@@ -84,7 +85,8 @@ class RankDesc(C.Structure):
                 ("N", C.c_int), ("T", C.c_int), ("targets", C.c_void_p), ("ld_targets", C.c_int), ("exclude", C.c_void_p),
                 ("ld_exclude", C.c_int), ("E", C.c_int), ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int),
                 ("splits", C.c_int), ("ks", C.POINTER(C.c_int)), ("n_ks", C.c_int),
-                ("out_ranks", C.c_void_p), ("out_scores", C.c_void_p), ("out_sums", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("out_ranks", C.c_void_p), ("out_scores", C.c_void_p), ("out_sums", C.c_void_p),
+                ("group", C.c_void_p), ("group_cap", C.c_int), ("n_groups", C.c_int), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
                 ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
 
 

@@ -27,7 +27,26 @@
 //   rank_final_kernel       one wave per user, one lane per target: rank = 1 + sum of the slices' counts - excluded news that
 //                           beat it; 0 and -inf for the not-ranked; the user's metric terms in fp64.
 //   rank_reduce_kernel      fixed-order sum of the per-user terms into out_sums (as metrics_reduce_kernel of nr_data.hip).
+//
+// Group caps (include/nrhip.h K10: the rank in the capped ranking of nr_score_topk(..., group, group_cap)) need, per user and
+// target, the number n_g of eligible news of EVERY group g that beat the target.  The GROUP instantiations add that to the same
+// passes; a call without `group` launches the instantiations it always launched.
+//   rank_group_masks_kernel once per call, independent of the users: for every chunk of 128 ids the counting pass will see (the
+//                           chunk starts of its slices, v_lo = 1 + slice * per) and every group g, the two 64-bit masks "news
+//                           of this chunk in group g".  A group id outside [0, G) sets no bit: such a news is ungrouped.
+//   named kernels, GROUP    gather group[id] of the targets and of the excluded / listed ids; for every target slot j and listed
+//                           news that beats it (in range, key != 0, once): counters[u, j, group] -= 1 (integer atomics into the
+//                           zeroed [U, T, G] array), so what is not eligible uses up nothing of a cap.
+//   rank_count_kernel<MT, POOL, GB>   GB = blocks of 64 groups, lane = group inside a block.  The ballots k0 > tk, k1 > tk are the
+//                           128-bit "beats target j" mask in SGPRs; each lane ANDs it with its group's masks of the chunk and
+//                           accumulates the population counts in registers [users of the wave][4 targets][GB]; once per slice
+//                           they are added to counters[u, slot of target j, g] with integer atomics.  Integers: independent of
+//                           `splits`, tile and arrival order.  The total count is untouched.
+//   rank_final_group_kernel n_g from the counters; capped out (rank -1, score kept) when the target's own group has n_g >= c,
+//                           else rank = uncapped - sum_g max(0, n_g - c); the metric terms as in rank_final_kernel.
 #include <math.h>
+
+#include <type_traits>
 
 #include "nr_score_tile.h"
 
@@ -44,7 +63,25 @@ inline int rk_user_tile(int N) {
     if (rk_lds_bytes(tu, N) <= TK_LDS_MAX) return tu;
   return 16;
 }
-inline int rk_auto_splits(int U, int V, int N) {
+// group caps: blocks of 64 groups as the counting pass instantiates them (1, 2, 4, 8), and the user tile whose per-wave counters
+// (TU / 8 users x 4 targets x blocks) are 64 registers or fewer
+inline int rk_group_blocks(int G) {
+  const int b = (G + 63) / 64;
+  return b <= 1 ? 1 : b <= 2 ? 2 : b <= 4 ? 4 : 8;
+}
+inline int rk_group_user_tile(int N, int G) {
+  const int tu = rk_user_tile(N), gb = rk_group_blocks(G), most = gb <= 2 ? 64 : gb == 4 ? 32 : 16;
+  return tu < most ? tu : most;
+}
+inline int rk_auto_splits(int U, int V, int N, int tile = 0) {
+  if (tile > 0) {
+    const long tiles = ((long)U + tile - 1) / tile;
+    long s = (TK_CUS + tiles - 1) / tiles;
+    const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
+    if (s > chunks) s = chunks;
+    if (s > RK_MAX_SPLITS) s = RK_MAX_SPLITS;
+    return s < 1 ? 1 : (int)s;
+  }
   const long tiles = ((long)U + rk_user_tile(N) - 1) / rk_user_tile(N);
   long s = (TK_CUS + tiles - 1) / tiles;
   const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
@@ -77,6 +114,36 @@ inline RankWs rk_carve(void* ws, int U, int T, int n_ks, int splits) {
   return w;
 }
 
+// group caps: read by the GROUP instantiations only
+struct GroupArgs {
+  const int32_t* group;   // [V]
+  const u64* masks;       // [splits * cps, G, 2]  news of chunk (slice, q) in group g: rows 0 .. 63, rows 64 .. 127
+  int32_t* cnt;           // [U, T, G]             eligible news of group g that beat target slot j (zeroed, then atomics)
+  int32_t* slot;          // [U, T]                compact index p -> target slot j
+  int32_t* tgrp;          // [U, T]                group of target slot j, -1 = none
+  int G, cap, cps;        // cps = chunks per slice
+  // the group of news id (in [1, V)); an id outside [0, G) is "no group": nothing outside the workspace is ever addressed
+  __device__ __forceinline__ int32_t of(int32_t id) const {
+    const int32_t g = group[id];
+    return (uint32_t)g < (uint32_t)G ? g : -1;
+  }
+};
+// the last kernel argument: GroupArgs with caps, nothing without -- the arguments in front of it keep their places
+struct NoGroupArgs {};
+template <bool GROUP>
+using GroupArgsIf = typename std::conditional<GROUP, GroupArgs, NoGroupArgs>::type;
+inline GroupArgs rk_group_carve(void* ws, size_t at, int U, int T, int G, int splits, int cps, size_t* end) {
+  GroupArgs g = {};
+  char* p = reinterpret_cast<char*>(ws) + ((at + 7) & ~(size_t)7);
+  const size_t ut = (size_t)U * T;
+  g.masks = reinterpret_cast<const u64*>(p); p += (size_t)splits * cps * G * 2 * sizeof(u64);
+  g.cnt = reinterpret_cast<int32_t*>(p); p += ut * G * sizeof(int32_t);
+  g.slot = reinterpret_cast<int32_t*>(p); p += ut * sizeof(int32_t);
+  g.tgrp = reinterpret_cast<int32_t*>(p); p += ut * sizeof(int32_t);
+  *end = (size_t)(p - reinterpret_cast<char*>(ws));
+  return g;
+}
+
 struct RankArgs {
   const float* news;
   const float* user;
@@ -88,6 +155,11 @@ struct RankArgs {
   PoolArgs pool;        // read by the POOL instantiations only
 };
 
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -114,8 +186,9 @@ struct RankNamedRows {
 
 // POOL (both kernels): the call has a prior and / or stamps + windows; every key then comes from pool_key (nr_score_tile.h), as
 // in topk_select_kernel<MT, true>.  A call without them launches the <false> kernels, the code as it was before pools existed.
-template <bool POOL>
-__global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
+// GROUP (all passes): the call has group caps, see the head of the file; `ga` is read by the GROUP instantiations only.
+template <bool POOL, bool GROUP = false>
+__global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a, GroupArgsIf<GROUP> ga) {
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
   ScoreTile<1> t(rk_smem, a.N);
   int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [16, 128]
@@ -174,9 +247,22 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a) {
       const u64 mask = __ballot(ranked);
       const int p = __popcll(mask & ((1ull << lane) - 1ull)), n = __popcll(mask);
       int beaten_by = 0;
-      for (int j = 0; j < a.T; ++j) {
-        const int cnt = __popcll(__ballot(x_counts && kx > lane_u64(kt, j)));
-        if (lane == j) beaten_by = cnt;
+      if constexpr (GROUP) {
+        // lane = excluded news: what the total takes back, its group takes back as well, per target slot
+        const int32_t gx = x_counts ? ga.of(ex) : -1;
+        for (int j = 0; j < a.T; ++j) {
+          const bool beats = x_counts && kx > lane_u64(kt, j);
+          const int cnt = __popcll(__ballot(beats));
+          if (lane == j) beaten_by = cnt;
+          if (beats && gx >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + gx], -1);
+        }
+        if (lane < a.T) ga.tgrp[u * a.T + lane] = t_in ? ga.of(tg) : -1;
+        if (ranked) ga.slot[u * a.T + p] = lane;
+      } else {
+        for (int j = 0; j < a.T; ++j) {
+          const int cnt = __popcll(__ballot(x_counts && kx > lane_u64(kt, j)));
+          if (lane == j) beaten_by = cnt;
+        }
       }
       if (ranked) {
         a.w.keys[u * a.T + p] = kt;
@@ -203,8 +289,8 @@ __device__ __forceinline__ void rank_csr_stage(int32_t* dst, const RankArgs& a, 
   dst[tid] = id;
 }
 
-template <bool POOL>
-__global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, CsrArgs ca) {
+template <bool POOL, bool GROUP = false>
+__global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, CsrArgs ca, GroupArgsIf<GROUP> ga) {
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
   ScoreTile<1> t(rk_smem, a.N);
   int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [2, 128]: this chunk's ids and the next one's
@@ -288,14 +374,32 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, 
         kb = news_key(sS[lane + RK_SLOTS], (uint32_t)xb);
       }
       const bool a_counts = a_in && (ka >> 32) != 0, b_counts = b_in && (kb >> 32) != 0;   // a NaN news: nothing to take back
-      for (int j = 0; j < a.T; ++j) {
-        const int32_t tj = __builtin_amdgcn_readlane(tg, j);
-        const u64 ktj = lane_u64(kt, j);
-        const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
-        const int cnt = __popcll(__ballot(a_counts && ka > ktj)) + __popcll(__ballot(b_counts && kb > ktj));
-        if (lane == j) {
-          if (listed) ranked = false;
-          beaten_by += cnt;
+      if constexpr (GROUP) {
+        // what the total takes back, the listed news' group takes back as well, per target slot
+        const int32_t grp_a = a_counts ? ga.of(xa) : -1, grp_b = b_counts ? ga.of(xb) : -1;
+        for (int j = 0; j < a.T; ++j) {
+          const int32_t tj = __builtin_amdgcn_readlane(tg, j);
+          const u64 ktj = lane_u64(kt, j);
+          const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
+          const bool a_beats = a_counts && ka > ktj, b_beats = b_counts && kb > ktj;
+          const int cnt = __popcll(__ballot(a_beats)) + __popcll(__ballot(b_beats));
+          if (lane == j) {
+            if (listed) ranked = false;
+            beaten_by += cnt;
+          }
+          if (a_beats && grp_a >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + grp_a], -1);
+          if (b_beats && grp_b >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + grp_b], -1);
+        }
+      } else {
+        for (int j = 0; j < a.T; ++j) {
+          const int32_t tj = __builtin_amdgcn_readlane(tg, j);
+          const u64 ktj = lane_u64(kt, j);
+          const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
+          const int cnt = __popcll(__ballot(a_counts && ka > ktj)) + __popcll(__ballot(b_counts && kb > ktj));
+          if (lane == j) {
+            if (listed) ranked = false;
+            beaten_by += cnt;
+          }
         }
       }
       if (q + 1 >= nq) {                                      // the user's last chunk: compact and store
@@ -307,6 +411,10 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, 
         }
         if (lane < a.T) a.w.pos[u * a.T + lane] = ranked ? p : -1;
         if (lane == 0) a.w.nu[u] = n;
+        if constexpr (GROUP) {
+          if (lane < a.T) ga.tgrp[u * a.T + lane] = tg >= 1 && tg < a.V ? ga.of(tg) : -1;
+          if (ranked) ga.slot[u * a.T + p] = lane;
+        }
       }
     }
     __syncthreads();                                          // the score tile is the next chunk's staging buffer
@@ -314,9 +422,37 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, 
   }
 }
 
-template <int MT, bool POOL>
-__global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
+// One wave per (chunk of the counting pass, block of 64 groups), lane = group: the chunk's 128 group ids sit two per lane, and
+// every lane collects the bits of the ids that are in its group.  Rows beyond the slice end set no bit.
+__global__ __launch_bounds__(256) void rank_group_masks_kernel(const int32_t* __restrict__ group, u64* __restrict__ masks, int V, int G, int per,
+                                                                int cps, int n_chunks) {
+  const int lane = threadIdx.x & 63;
+  const long ci = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ci >= n_chunks) return;
+  const long slice = ci / cps, q = ci - slice * cps;
+  const long v_lo = 1 + slice * per;
+  const long v_hi = v_lo + per < V ? v_lo + per : V;
+  const long vc = v_lo + q * TK_ROWS;
+  const int32_t g0 = vc + lane < v_hi ? group[vc + lane] : -1, g1 = vc + lane + 64 < v_hi ? group[vc + lane + 64] : -1;
+  const int32_t mine = (int32_t)blockIdx.y * 64 + lane;
+  u64 m0 = 0ull, m1 = 0ull;
+  for (int r = 0; r < 64; ++r) {
+    if (__builtin_amdgcn_readlane(g0, r) == mine) m0 |= 1ull << r;
+    if (__builtin_amdgcn_readlane(g1, r) == mine) m1 |= 1ull << r;
+  }
+  if (mine < G) {
+    masks[((size_t)ci * G + mine) * 2] = m0;
+    masks[((size_t)ci * G + mine) * 2 + 1] = m1;
+  }
+}
+
+// GB = 0: no group caps, the kernel as it was before they existed.  GB >= 1: blocks of 64 groups, at most NR_RANK_MAX_CAPPED_TARGETS
+// targets per row; the counters gcnt[user of the wave][target][block] stay in registers (lane = group), so the host picks the user
+// tile that keeps PER_WAVE * 4 * GB at 64 registers or fewer.
+template <int MT, bool POOL, int GB = 0>
+__global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a, GroupArgsIf<(GB > 0)> ga) {
   constexpr int TU = 16 * MT, PER_WAVE = TU / TK_WAVES;
+  constexpr int TC = NR_RANK_MAX_CAPPED_TARGETS, GBN = GB > 0 ? GB : 1;
   extern __shared__ __attribute__((aligned(16))) float rk_smem[];
   ScoreTile<MT> t(rk_smem, a.N);
   const int lane = t.lane, wave = t.wave;
@@ -335,6 +471,19 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
     n[i] = u < a.U ? __builtin_amdgcn_readfirstlane(a.w.nu[u]) : 0;
     tkey[i] = lane < n[i] ? a.w.keys[(size_t)u * a.T + lane] : ~0ull;
     cnt[i] = 0;
+  }
+  int32_t gcnt[GB > 0 ? PER_WAVE : 1][TC][GBN];
+  int32_t slot[GB > 0 ? PER_WAVE : 1];
+  if constexpr (GB > 0) {
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int u = u0 + wave + TK_WAVES * i;
+      slot[i] = lane < n[i] ? ga.slot[(size_t)u * a.T + lane] : 0;
+#pragma unroll
+      for (int j = 0; j < TC; ++j)
+#pragma unroll
+        for (int b = 0; b < GB; ++b) gcnt[i][j][b] = 0;
+    }
   }
   // POOL: lane i keeps the window of this wave's i-th user; an empty one beyond U
   int32_t w_lo = 1, w_hi = 0;
@@ -367,6 +516,20 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
         s1 = a.pool.stamp_of(vc + lane + 64);
       }
     }
+    // GROUP: the chunk's masks of this lane's group in every block, once per chunk and wave (in flight over the barrier)
+    u64 gm0[GBN], gm1[GBN];
+    if constexpr (GB > 0) {
+      const size_t ci = (size_t)blockIdx.y * ga.cps + (size_t)((vc - v_lo) / TK_ROWS);
+#pragma unroll
+      for (int b = 0; b < GB; ++b) {
+        const int g = b * 64 + lane;
+        gm0[b] = gm1[b] = 0ull;
+        if (g < ga.G) {
+          gm0[b] = ga.masks[(ci * ga.G + g) * 2];
+          gm1[b] = ga.masks[(ci * ga.G + g) * 2 + 1];
+        }
+      }
+    }
     t.put_scores(acc);
     const float* sS = t.scores();
     const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
@@ -385,10 +548,23 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
         k0 = lane < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane], (uint32_t)(vc + lane)) : 0ull;
         k1 = lane + 64 < nvalid ? news_key(sS[ul * TK_LDS_TILE + lane + 64], (uint32_t)(vc + lane + 64)) : 0ull;
       }
-      for (int j = 0; j < n[i]; ++j) {
-        const u64 tk = lane_u64(tkey[i], j);                  // strict >: the target never counts itself
-        const int c = __popcll(__ballot(k0 > tk)) + __popcll(__ballot(k1 > tk));
-        cnt[i] += lane == j ? c : 0;
+      if constexpr (GB > 0) {
+#pragma unroll
+        for (int j = 0; j < TC; ++j) {
+          if (j >= n[i]) break;
+          const u64 tk = lane_u64(tkey[i], j);                // strict >: the target never counts itself
+          const u64 b0 = __ballot(k0 > tk), b1 = __ballot(k1 > tk);      // the 128 news of the chunk that beat target j
+          cnt[i] += lane == j ? __popcll(b0) + __popcll(b1) : 0;
+#pragma unroll
+          for (int b = 0; b < GB; ++b)
+            if (b * 64 < ga.G) gcnt[i][j][b] += __popcll(b0 & gm0[b]) + __popcll(b1 & gm1[b]);
+        }
+      } else {
+        for (int j = 0; j < n[i]; ++j) {
+          const u64 tk = lane_u64(tkey[i], j);                  // strict >: the target never counts itself
+          const int c = __popcll(__ballot(k0 > tk)) + __popcll(__ballot(k1 > tk));
+          cnt[i] += lane == j ? c : 0;
+        }
       }
     }
     __syncthreads();                                          // the score tile is the next chunk's staging buffer
@@ -398,12 +574,51 @@ __global__ __launch_bounds__(TK_THREADS) void rank_count_kernel(RankArgs a) {
     const int u = u0 + wave + TK_WAVES * i;
     if (u < a.U && lane < n[i]) a.w.part[((size_t)u * a.splits + blockIdx.y) * a.T + lane] = cnt[i];
   }
+  if constexpr (GB > 0) {
+    // this slice's per-group counts into the [U, T, G] counters: integer atomics, any order gives the same sum
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int u = u0 + wave + TK_WAVES * i;
+#pragma unroll
+      for (int j = 0; j < TC; ++j) {
+        if (j >= n[i]) break;                                 // n[i] = 0 beyond U
+        const int sj = __builtin_amdgcn_readlane(slot[i], j);
+#pragma unroll
+        for (int b = 0; b < GB; ++b) {
+          const int g = b * 64 + lane;
+          if (g < ga.G && gcnt[i][j][b] != 0) atomicAdd(&ga.cnt[((size_t)u * a.T + sj) * ga.G + g], gcnt[i][j][b]);
+        }
+      }
+    }
+  }
 }
 
 struct RankKs {
   int n;
   int k[NR_RANK_MAX_KS];
 };
+
+// MRR_u = mean 1 / rank; Recall@k_u = #{rank <= k} / n; nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1) over the ideal
+// sum_{i <= min(n, k)} 1 / log2(i + 1): src/metrics.py:6-24 on the user's whole eligible row with binary labels.  One wave per
+// user, lane = target slot; n = the user's ranked targets.  A rank <= 0 adds nothing (0: not ranked; -1: capped out, counted in n).
+__device__ __forceinline__ void rank_terms(const RankWs& w, size_t u, int lane, int n, int rank, const RankKs& ks) {
+  double* o = w.terms + u * (2 + 2 * ks.n);
+  const double gain = rank > 0 ? 1.0 / log2((double)rank + 1.0) : 0.0, ideal = 1.0 / log2((double)lane + 2.0);
+  const double rr = wave_sum_d(rank > 0 ? 1.0 / (double)rank : 0.0);
+  if (lane == 0) {
+    o[0] = n > 0 ? 1.0 : 0.0;
+    o[1] = n > 0 ? rr / n : 0.0;
+  }
+  for (int i = 0; i < ks.n; ++i) {
+    const bool hit = rank > 0 && rank <= ks.k[i];
+    const int hits = __popcll(__ballot(hit));
+    const double dcg = wave_sum_d(hit ? gain : 0.0), idcg = wave_sum_d(lane < n && lane < ks.k[i] ? ideal : 0.0);
+    if (lane == 0) {
+      o[2 + 2 * i] = n > 0 ? (double)hits / n : 0.0;
+      o[3 + 2 * i] = n > 0 ? dcg / idcg : 0.0;
+    }
+  }
+}
 
 __global__ __launch_bounds__(256) void rank_final_kernel(RankWs w, int U, int T, int splits, RankKs ks, int want_terms, int32_t* __restrict__ out_ranks,
                                                           float* __restrict__ out_scores) {
@@ -425,8 +640,7 @@ __global__ __launch_bounds__(256) void rank_final_kernel(RankWs w, int U, int T,
     out_scores[u * T + lane] = score;
   }
   if (!want_terms) return;
-  // MRR_u = mean 1 / rank; Recall@k_u = #{rank <= k} / n; nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1) over the ideal
-  // sum_{i <= min(n, k)} 1 / log2(i + 1): src/metrics.py:6-24 on the user's whole eligible row with binary labels
+  // the text of rank_terms, kept in place so that this kernel stays instruction for instruction what it was before group caps
   double* o = w.terms + u * (2 + 2 * ks.n);
   const double gain = rank > 0 ? 1.0 / log2((double)rank + 1.0) : 0.0, ideal = 1.0 / log2((double)lane + 2.0);
   const double rr = wave_sum_d(rank > 0 ? 1.0 / (double)rank : 0.0);
@@ -443,6 +657,46 @@ __global__ __launch_bounds__(256) void rank_final_kernel(RankWs w, int U, int T,
       o[3 + 2 * i] = n > 0 ? dcg / idcg : 0.0;
     }
   }
+}
+
+// The finalize pass of a call with group caps.  counters[u, j, g] = n_g of target slot j (stream count minus what the named
+// pass took back).  Capped out: the target's own group already has c news in front of it -- rank -1, the score stays.  Otherwise
+// every group gives back what it has beyond c: rank = uncapped - sum_g max(0, n_g - c).  n (the ranked targets, capped-out ones
+// included) and the metric terms are rank_final_kernel's; a rank of -1 is no hit and adds no reciprocal rank.
+__global__ __launch_bounds__(256) void rank_final_group_kernel(RankWs w, const int32_t* __restrict__ gcnt, const int32_t* __restrict__ tgrp, int G, int cap,
+                                                                int U, int T, int splits, RankKs ks, int want_terms, int32_t* __restrict__ out_ranks,
+                                                                float* __restrict__ out_scores) {
+  const int lane = threadIdx.x & 63;
+  const size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= (size_t)U) return;
+  const int n = w.nu[u];
+  int over = 0;
+  for (int j = 0; j < T; ++j) {
+    int o = 0;
+    for (int g = lane; g < G; g += 64) {
+      const int ng = gcnt[(u * T + j) * G + g];
+      o += ng > cap ? ng - cap : 0;
+    }
+    o = wave_sum_i(o);
+    if (lane == j) over = o;
+  }
+  int rank = 0;
+  float score = -__builtin_inff();
+  if (lane < T) {
+    const int p = w.pos[u * T + lane];
+    if (p >= 0) {
+      int c = -w.excl[u * T + p];
+      for (int s = 0; s < splits; ++s) c += w.part[(u * splits + s) * T + p];
+      const int gt = tgrp[u * T + lane];
+      const bool capped_out = gt >= 0 && gcnt[(u * T + lane) * G + gt] >= cap;
+      rank = capped_out ? -1 : 1 + c - over;
+      score = key_score((uint32_t)(w.keys[u * T + p] >> 32));
+    }
+    out_ranks[u * T + lane] = rank;
+    out_scores[u * T + lane] = score;
+  }
+  if (!want_terms) return;
+  rank_terms(w, u, lane, n, rank, ks);
 }
 
 // fixed-order reduction of the per-user terms: sums[c] = sum_u terms[u, c]
@@ -487,7 +741,31 @@ int rank_check(const nr_rank_desc* d) {
   NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_rank: stamp given without window (the two come together)");
   NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_rank: window given without stamp (the two come together)");
   NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_rank: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_ARG(d->group == nullptr || (d->group_cap >= 1 && d->group_cap <= NR_TOPK_MAX_K),
+               "score_rank: group given with group_cap = %d, the cap must be in [1, %d]", d->group_cap, NR_TOPK_MAX_K);
+  NR_CHECK_ARG(d->group != nullptr || d->group_cap == 0, "score_rank: group_cap = %d given without group (the two come together)", d->group_cap);
+  NR_CHECK_ARG(d->group != nullptr || d->n_groups == 0, "score_rank: n_groups = %d given without group (the two come together)", d->n_groups);
+  NR_CHECK_ARG(d->group == nullptr || (d->n_groups >= 1 && d->n_groups <= NR_RANK_MAX_GROUPS),
+               "score_rank: group given with n_groups = %d, must be in [1, %d]", d->n_groups, NR_RANK_MAX_GROUPS);
+  NR_CHECK_ARG(d->group == nullptr || d->T <= NR_RANK_MAX_CAPPED_TARGETS,
+               "score_rank: T = %d targets per row with group caps, at most %d (lay a user with more over several rows)", d->T,
+               NR_RANK_MAX_CAPPED_TARGETS);
   return NR_OK;
+}
+
+// slices, slice length and chunks per slice of a call; with group caps the user tile, and with it the library's choice of slices, is
+// the capped one
+struct RankPlan {
+  int TU, splits, per, cps;
+};
+inline RankPlan rk_plan(const nr_rank_desc* d) {
+  RankPlan p;
+  const bool grp = d->group != nullptr;
+  p.TU = grp ? rk_group_user_tile(d->N, d->n_groups) : rk_user_tile(d->N);
+  p.splits = d->splits > 0 ? d->splits : grp ? rk_auto_splits(d->U, d->V, d->N, p.TU) : rk_auto_splits(d->U, d->V, d->N);
+  p.per = (int)(((long)d->V - 1 + p.splits - 1) / p.splits);
+  p.cps = (p.per + TK_ROWS - 1) / TK_ROWS;
+  return p;
 }
 
 }  // namespace
@@ -496,8 +774,10 @@ extern "C" {
 
 size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d) {
   if (rank_check(d) != NR_OK) return 0;
-  const int splits = d->splits > 0 ? d->splits : rk_auto_splits(d->U, d->V, d->N);
-  return rk_carve(nullptr, d->U, d->T, d->n_ks, splits).bytes;
+  const RankPlan pl = rk_plan(d);
+  size_t bytes = rk_carve(nullptr, d->U, d->T, d->n_ks, pl.splits).bytes;
+  if (d->group != nullptr) rk_group_carve(nullptr, bytes, d->U, d->T, d->n_groups, pl.splits, pl.cps, &bytes);
+  return bytes;
 }
 
 int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
@@ -515,15 +795,28 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
                "score_rank: workspace holds %zu bytes, nr_score_rank_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
-  const int splits = d->splits > 0 ? d->splits : rk_auto_splits(d->U, d->V, d->N);
-  const int TU = rk_user_tile(d->N);
+  const RankPlan pl = rk_plan(d);
+  const int splits = pl.splits, TU = pl.TU;
+  const bool grp = d->group != nullptr;
   RankArgs a;
   a.news = d->news_vecs; a.user = d->user; a.targets = d->targets;
   a.exclude = d->exclude;
   a.w = rk_carve(d->ws, d->U, d->T, d->n_ks, splits);
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_tgt = (size_t)d->ld_targets; a.ld_excl = (size_t)d->ld_exclude;
   a.V = d->V; a.U = d->U; a.N = d->N; a.T = d->T; a.E = d->exclude != nullptr ? d->E : 0; a.splits = splits;
-  a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
+  a.per = pl.per;
+  GroupArgs ga = {};
+  if (grp) {
+    size_t end;
+    ga = rk_group_carve(d->ws, a.w.bytes, d->U, d->T, d->n_groups, splits, pl.cps, &end);
+    ga.group = d->group; ga.G = d->n_groups; ga.cap = d->group_cap; ga.cps = pl.cps;
+    const int n_chunks = splits * pl.cps, gb = (d->n_groups + 63) / 64;
+    NrProfScope ps(s, "rank_group_masks[V=%d,G=%d,chunks=%d]", d->V, d->n_groups, n_chunks);
+    NR_CHECK_HIP(hipMemsetAsync(ga.cnt, 0, (size_t)d->U * d->T * d->n_groups * sizeof(int32_t), s));
+    hipLaunchKernelGGL(rank_group_masks_kernel, dim3((unsigned)((n_chunks + 3) / 4), (unsigned)gb), dim3(256), 0, s, d->group,
+                       const_cast<u64*>(ga.masks), d->V, d->n_groups, pl.per, pl.cps, n_chunks);
+    NR_CHECK_LAUNCH();
+  }
   a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
   const bool pool = a.pool.any();
   const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
@@ -531,17 +824,31 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
     const CsrArgs ca = {d->excl_offsets, d->excl_ids, d->n_excl};
     NrProfScope ps(s, "rank_named_csr[U=%d,N=%d,T=%d,n_excl=%d]", d->U, d->N, d->T, d->n_excl);
     const size_t smem = rk_lds_bytes(16, d->N) + (size_t)2 * TK_ROWS * sizeof(int32_t);
-    const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false>);
-    NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (pool) hipLaunchKernelGGL(rank_named_csr_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca);
-    else hipLaunchKernelGGL(rank_named_csr_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca);
+    if (grp) {
+      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true, true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false, true>);
+      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      if (pool) hipLaunchKernelGGL((rank_named_csr_kernel<true, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, ga);
+      else hipLaunchKernelGGL((rank_named_csr_kernel<false, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, ga);
+    } else {
+      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false>);
+      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      if (pool) hipLaunchKernelGGL(rank_named_csr_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, NoGroupArgs{});
+      else hipLaunchKernelGGL(rank_named_csr_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, NoGroupArgs{});
+    }
   } else {
     NrProfScope ps(s, "rank_named[U=%d,N=%d,T=%d,E=%d]", d->U, d->N, d->T, a.E);
     const size_t smem = rk_lds_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
-    const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true>) : reinterpret_cast<const void*>(rank_named_kernel<false>);
-    NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    if (pool) hipLaunchKernelGGL(rank_named_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
-    else hipLaunchKernelGGL(rank_named_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+    if (grp) {
+      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true, true>) : reinterpret_cast<const void*>(rank_named_kernel<false, true>);
+      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      if (pool) hipLaunchKernelGGL((rank_named_kernel<true, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ga);
+      else hipLaunchKernelGGL((rank_named_kernel<false, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ga);
+    } else {
+      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true>) : reinterpret_cast<const void*>(rank_named_kernel<false>);
+      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      if (pool) hipLaunchKernelGGL(rank_named_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, NoGroupArgs{});
+      else hipLaunchKernelGGL(rank_named_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, NoGroupArgs{});
+    }
   }
   NR_CHECK_LAUNCH();
   {
@@ -552,17 +859,41 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
   do {                                                                                                                                     \
     NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                      (int)smem));                                                                                          \
-    hipLaunchKernelGGL((rank_count_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a);                                                 \
+    hipLaunchKernelGGL((rank_count_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a, NoGroupArgs{});                                               \
   } while (0)
-#define NR_RANK_LAUNCH_MT(MT)           \
-  do {                                  \
-    if (pool) NR_RANK_LAUNCH(MT, true); \
-    else NR_RANK_LAUNCH(MT, false);     \
+#define NR_RANK_LAUNCH_GROUP(MT, POOL, GB)                                                                                                 \
+  do {                                                                                                                                     \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT, POOL, GB>),                                 \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                              \
+    hipLaunchKernelGGL((rank_count_kernel<MT, POOL, GB>), grid, dim3(TK_THREADS), smem, s, a, ga);                                   \
   } while (0)
-    if (TU == 64) NR_RANK_LAUNCH_MT(4);
-    else if (TU == 32) NR_RANK_LAUNCH_MT(2);
-    else NR_RANK_LAUNCH_MT(1);
+#define NR_RANK_LAUNCH_MT(MT, GB)                                  \
+  do {                                                             \
+    if constexpr (GB == 0) {                                       \
+      if (pool) NR_RANK_LAUNCH(MT, true);                          \
+      else NR_RANK_LAUNCH(MT, false);                              \
+    } else {                                                       \
+      if (pool) NR_RANK_LAUNCH_GROUP(MT, true, (GB > 0 ? GB : 1)); \
+      else NR_RANK_LAUNCH_GROUP(MT, false, (GB > 0 ? GB : 1));     \
+    }                                                              \
+  } while (0)
+#define NR_RANK_LAUNCH_TU(GB)                    \
+  do {                                           \
+    if (TU == 64) NR_RANK_LAUNCH_MT(4, GB);      \
+    else if (TU == 32) NR_RANK_LAUNCH_MT(2, GB); \
+    else NR_RANK_LAUNCH_MT(1, GB);               \
+  } while (0)
+    const int gb = grp ? rk_group_blocks(d->n_groups) : 0;    // rk_group_user_tile: TU <= 32 with 4 blocks, 16 with 8
+    if (gb == 0) NR_RANK_LAUNCH_TU(0);
+    else if (gb == 1) NR_RANK_LAUNCH_TU(1);
+    else if (gb == 2) NR_RANK_LAUNCH_TU(2);
+    else if (gb == 4) {
+      if (TU == 32) NR_RANK_LAUNCH_MT(2, 4);
+      else NR_RANK_LAUNCH_MT(1, 4);
+    } else NR_RANK_LAUNCH_MT(1, 8);
+#undef NR_RANK_LAUNCH_TU
 #undef NR_RANK_LAUNCH_MT
+#undef NR_RANK_LAUNCH_GROUP
 #undef NR_RANK_LAUNCH
   }
   NR_CHECK_LAUNCH();
@@ -571,8 +902,12 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
   for (int i = 0; i < NR_RANK_MAX_KS; ++i) ks.k[i] = i < d->n_ks ? d->ks[i] : 1;
   {
     NrProfScope ps(s, "rank_final[U=%d,T=%d,splits=%d]", d->U, d->T, splits);
-    hipLaunchKernelGGL(rank_final_kernel, dim3((unsigned)((d->U + 3) / 4)), dim3(256), 0, s, a.w, d->U, d->T, splits, ks, d->out_sums != nullptr ? 1 : 0,
-                       d->out_ranks, d->out_scores);
+    if (grp)
+      hipLaunchKernelGGL(rank_final_group_kernel, dim3((unsigned)((d->U + 3) / 4)), dim3(256), 0, s, a.w, (const int32_t*)ga.cnt, (const int32_t*)ga.tgrp,
+                         d->n_groups, d->group_cap, d->U, d->T, splits, ks, d->out_sums != nullptr ? 1 : 0, d->out_ranks, d->out_scores);
+    else
+      hipLaunchKernelGGL(rank_final_kernel, dim3((unsigned)((d->U + 3) / 4)), dim3(256), 0, s, a.w, d->U, d->T, splits, ks, d->out_sums != nullptr ? 1 : 0,
+                         d->out_ranks, d->out_scores);
     if (d->out_sums != nullptr)
       hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(1024), 0, s, (const double*)a.w.terms, d->U, 2 + 2 * d->n_ks, d->out_sums);
   }

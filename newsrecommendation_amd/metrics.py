@@ -114,7 +114,7 @@ def topk_reference(a, b=None, *, k, exclude=None, prior=None, stamp=None, window
     return ids, out
 
 
-def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, window=None):
+def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, window=None, group=None, group_cap=None):
     """Host statement of the full-corpus rank contract (include/nrhip.h, nr_score_rank); tests check the device against it, no
     product path calls it.
 
@@ -124,7 +124,16 @@ def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, 
     ("not ranked") when the target means nothing, is excluded, has a NaN score or repeats an earlier entry of its row.
     Returns (ranks int32 [U, T], scores float64 [U, T]); the score is -inf where the rank is 0.
     Pools: prior, stamp, window as in topk_reference; a target outside its user's pool is not ranked, and an excluded id outside
-    it changes nothing (it was not eligible to begin with)."""
+    it changes nothing (it was not eligible to begin with).
+    Group caps: group [V] integer ids (negative = in no group) with group_cap = c in [1, 128], together, as in topk_reference.
+    The rank is then the place in the CAPPED ranking: the walk down the eligible news in the total order that takes a news
+    unless c news of its group are already taken -- topk_reference's walk, not stopped at any k.  A target the walk skips is
+    "capped out": rank -1, and it KEEPS its score (a legitimate held-out click the capped recommender never shows).  What is
+    not eligible uses up nothing of a cap; what is not ranked without caps stays at rank 0, score -inf."""
+    if (group is None) != (group_cap is None):
+        raise ValueError("group and group_cap come together")
+    if group is not None and not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
     a = np.asarray(a, dtype=np.float64)
     scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
     scores, pool = _pooled(scores, prior, stamp, window)
@@ -142,19 +151,33 @@ def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, 
         cand = np.flatnonzero(ok)
         order = cand[np.lexsort((cand, -scores[u, cand]))]
         place = np.zeros(V, dtype=np.int64)
-        place[order] = np.arange(1, len(order) + 1)
+        if group is None:
+            place[order] = np.arange(1, len(order) + 1)
+        else:
+            grp, taken, n_taken = np.asarray(group, dtype=np.int64).reshape(V), {}, 0
+            for v in order:
+                g = int(grp[v])
+                if g >= 0 and taken.get(g, 0) >= int(group_cap):
+                    place[v] = -1                                # eligible, and skipped by the walk
+                    continue
+                taken[g] = taken.get(g, 0) + 1
+                n_taken += 1
+                place[v] = n_taken
         seen = set()
         for j in range(T):
             t = int(targets[u, j])
-            if 1 <= t < V and t not in seen and place[t] > 0:
+            if 1 <= t < V and t not in seen and place[t] != 0:
                 ranks[u, j], out[u, j] = place[t], scores[u, t]
             seen.add(t)
     return ranks, out
 
 
 def retrieval_metrics_reference(ranks, ks):
-    """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked), and their sums over the
-    users with n_u >= 1 ranked targets:
+    """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
+    group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds
+    nothing to MRR, Recall@k or nDCG@k while the ideal DCG keeps its min(n_u, k) terms -- the ideal is what a recommender
+    without the cap could have shown, so hiding a click costs nDCG instead of shrinking its denominator.  Without a negative
+    rank the result is what it always was.
       MRR_u = mean_j 1 / rank;  Recall@k_u = #{rank <= k} / n_u;
       nDCG@k_u = sum_{rank <= k} 1 / log2(rank + 1)  /  sum_{i = 1 .. min(n_u, k)} 1 / log2(i + 1)
     -- mrr_score / ndcg_score above applied to the user's whole eligible corpus row with binary labels.
@@ -165,7 +188,7 @@ def retrieval_metrics_reference(ranks, ks):
     per_user = np.zeros((ranks.shape[0], 2 + 2 * len(ks)), dtype=np.float64)
     for u, row in enumerate(ranks):
         r = row[row > 0].astype(np.float64)
-        n = len(r)
+        n = int(np.count_nonzero(row))
         if n == 0:
             continue
         per_user[u, 0], per_user[u, 1] = 1.0, np.sum(1.0 / r) / n

@@ -1163,7 +1163,7 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
     group, never capped) with `group_cap` = c in [1, 128] -- the row is the walk down the same order that skips a news once c
     news of its group are taken, so at most c per group and still k entries where k can be taken (otherwise the usual fill).
     One without the other is refused by the library.  Without them the call launches the kernels it always launched.
-    score_rank knows no caps: a capped row is a subsequence of the uncapped order."""
+    score_rank_capped takes the same two arguments and gives the place in this capped row."""
     _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
@@ -1208,8 +1208,31 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, pri
     (metrics.retrieval_metrics_reference states the per-user terms); with ks=None no sums are formed and None is returned.
     `splits`: 0 = the library chooses the number of corpus slices; tests force it.
     Pools: `prior`, `stamp`, `window` as in score_topk, with the same score fl32(dot + prior) and the same eligible news, so the
-    agreement with score_topk's rows holds for equal pool inputs.  A target outside its user's pool has rank 0, score -inf."""
-    _need_gpu(news_vecs, user_vecs, targets, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window)
+    agreement with score_topk's rows holds for equal pool inputs.  A target outside its user's pool has rank 0, score -inf.
+    This call knows no group caps and describes the uncapped ranking; score_rank_capped ranks in the capped one."""
+    return _score_rank(news_vecs, user_vecs, targets, exclude, ks, splits, prior, stamp, window, None, None, None)
+
+
+@torch.no_grad()
+def score_rank_capped(news_vecs, user_vecs, targets, group, group_cap, n_groups=None, exclude=None, ks=(), splits=0, prior=None, stamp=None,
+                      window=None):
+    """score_rank under the group caps of score_topk (include/nrhip.h, K10): `group` [V] int32 on the device and `group_cap` = c as
+    in score_topk -- the rank is the place in the capped ranking score_topk(..., group, group_cap) serves: 1 <= rank <= k exactly
+    when the target is at place rank - 1 of that row, same score bits.  A target that ranking never shows, because c better
+    news of its own group stand in front of it, has rank -1 and keeps its score; in the sums it counts in n_u and adds nothing
+    else.  What is not ranked by score_rank stays at rank 0, score -inf.  At most 4 targets per row
+    (_lib.NR_RANK_MAX_CAPPED_TARGETS); train.rank_eval_capped lays wider users over several rows.
+    `n_groups`: the group ids lie in [0, n_groups), at most 512; None takes group.max() + 1 from the device, which is one
+    synchronisation -- pass it where that matters.  Everything else is score_rank's, and it is a function of its own because
+    score_rank's argument list is pinned: that call keeps launching the kernels it always launched."""
+    if group is None:
+        raise RuntimeError("score_rank_capped: group is None; the call without caps is score_rank")
+    return _score_rank(news_vecs, user_vecs, targets, exclude, ks, splits, prior, stamp, window, group, group_cap, n_groups)
+
+
+def _score_rank(news_vecs, user_vecs, targets, exclude, ks, splits, prior, stamp, window, group, group_cap, n_groups):
+    """score_rank (group None) and score_rank_capped: one descriptor, one library call."""
+    _need_gpu(news_vecs, user_vecs, targets, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"score_rank: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1233,10 +1256,19 @@ def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, pri
     ex_fields, ex_keep = _exclude_args("score_rank", exclude, U, dev)
     ks_host = (C.c_int * max(len(ks), 1))(*ks)
     pr, st, win = _pool_args("score_rank", V, U, dev, prior, stamp, window)
+    gr = None
+    if group is not None:
+        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
+            raise RuntimeError(f"score_rank: group must be an int32 tensor of shape ({V},) on {dev}, got "
+                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
+        gr = group.detach().contiguous()
+        if n_groups is None:
+            n_groups = max(int(gr.max().item()) + 1, 1)                  # the one synchronisation; all ids negative: one empty group
     d = _lib.RankDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, **ex_fields,
                       splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
-                      out_sums=ptr(sums), prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+                      out_sums=ptr(sums), prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0,
+                      group=ptr(gr), group_cap=0 if group_cap is None else int(group_cap), n_groups=0 if n_groups is None else int(n_groups))
     ws = _ws(_lib.lib().nr_score_rank_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
     check(_lib.lib().nr_score_rank(C.byref(d), _stream()), "nr_score_rank")

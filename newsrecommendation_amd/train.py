@@ -369,7 +369,7 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     Group caps (ops.score_topk): news_group [N+1] integer group ids -- MIND's category or subcategory column, say; negative =
     in no group -- with group_cap = c: a row holds at most c news of one group and is otherwise the same walk down the order,
     so it still has k entries wherever k can be taken.  The cap is applied inside the selection, not to a finished row.
-    rank_eval keeps ranking without caps: the uncapped rank of a capped row's entry at place p is >= p + 1."""
+    rank_eval_capped takes the same two arguments and ranks the held-out clicks in this capped ranking."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -386,10 +386,11 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
 
 def _retrieval_sums(ranks, ks):
     """[users with a ranked target, sum MRR_u, then per k: sum Recall@k_u, sum nDCG@k_u] in fp64 from ranks [U, T] (0 = not
-    ranked): metrics.retrieval_metrics_reference as tensor arithmetic on the device of `ranks`."""
+    ranked; -1 = capped out: counted in n_u, nothing else): metrics.retrieval_metrics_reference as tensor arithmetic on the
+    device of `ranks`."""
     pos = ranks > 0
     r = ranks.double().clamp(min=1.0)
-    n = pos.sum(1)
+    n = (ranks != 0).sum(1)
     nd = n.clamp(min=1).double()
     counted = (n > 0).double()
     out = [counted.sum(), (torch.where(pos, 1.0 / r, torch.zeros_like(r)).sum(1) / nd * counted).sum()]
@@ -423,7 +424,29 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     Several ranks: the caller shards the users and the sums add; there is no collective.
     Pools: prior, news_time, window as in recommend -- the click is ranked inside the pool that was live for this user (for an
     impression: the news published in a window before it), with the prior in the score; a target outside the pool has rank 0.
-    The rows of a user with more than 64 targets share its window as well."""
+    The rows of a user with more than 64 targets share its window as well.
+    This call knows no group caps and describes the uncapped ranking; rank_eval_capped ranks in the capped one."""
+    return _rank_eval(model, news_vecs, hist_idx, mask, targets, ks, exclude_history, batch_size, prior, news_time, window, seen, None, None)
+
+
+@torch.no_grad()
+def rank_eval_capped(model, news_vecs, hist_idx, mask, targets, news_group, group_cap, ks=(5, 10, 100), exclude_history=True, batch_size=8192,
+                     prior=None, news_time=None, window=None, seen=None):
+    """rank_eval under the group caps of recommend: news_group [N+1] integer group ids (negative = in no group) and group_cap = c.
+    The ranks are the places in the capped ranking recommend(..., news_group, group_cap) serves (1 <= rank <= k exactly when the
+    click is at place rank - 1 of that row, same score bits), and a click that ranking can never show (c better news of its own
+    group in front of it) has rank -1 and keeps its score; in the sums it counts in n_u and adds nothing to MRR, Recall@k or
+    nDCG@k, and the ideal DCG keeps its min(n_u, k) terms.  What rank_eval does not rank stays at rank 0, score -inf.  The kernel
+    takes 4 targets per row here (_lib.NR_RANK_MAX_CAPPED_TARGETS), so rank_eval's several-rows layout starts at 5 targets
+    instead of 65.  The number of groups is max(news_group) + 1, at most 512.  Everything else is rank_eval's; it is a function of
+    its own because rank_eval's argument list is pinned."""
+    if news_group is None:
+        raise RuntimeError("rank_eval_capped: news_group is None; the call without caps is rank_eval")
+    return _rank_eval(model, news_vecs, hist_idx, mask, targets, ks, exclude_history, batch_size, prior, news_time, window, seen, news_group, group_cap)
+
+
+def _rank_eval(model, news_vecs, hist_idx, mask, targets, ks, exclude_history, batch_size, prior, news_time, window, seen, news_group, group_cap):
+    """rank_eval (news_group None: ops.score_rank) and rank_eval_capped (ops.score_rank_capped)."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -434,8 +457,15 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
     U, T = tg.shape
     W = _lib.NR_RANK_MAX_TARGETS
     pool = _pool_kwargs(device, prior, news_time, window)
+    score_rank = ops.score_rank
+    if news_group is not None:
+        grp = torch.as_tensor(news_group)
+        pool["n_groups"] = max(int(grp.max()) + 1, 1) if grp.numel() else 1
+        pool["group"] = grp.to(device=device, dtype=torch.int32)
+        pool["group_cap"] = group_cap
+        score_rank, W = ops.score_rank_capped, _lib.NR_RANK_MAX_CAPPED_TARGETS
     if T <= W or U == 0:
-        return ops.score_rank(news_vecs, user, tg, exclude=exclude, ks=ks, **pool)
+        return score_rank(news_vecs, user, tg, exclude=exclude, ks=ks, **pool)
     # later repeats -> 0 (stable sort by id: the first of equal ids is the earliest entry), then the non-zero entries to the front
     srt, at = torch.sort(tg, dim=1, stable=True)
     rep = torch.zeros_like(tg, dtype=torch.bool)
@@ -456,7 +486,7 @@ def rank_eval(model, news_vecs, hist_idx, mask, targets, ks=(5, 10, 100), exclud
         row_excl = exclude.take(row_user)                     # the rows of a user share its lists
     else:
         row_excl = None if exclude is None else exclude[row_user].contiguous()
-    r, sc, _ = ops.score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=row_excl, ks=None, **pool)
+    r, sc, _ = score_rank(news_vecs, user[row_user].contiguous(), row_tg, exclude=row_excl, ks=None, **pool)
     ranks_c = torch.zeros(U, T, dtype=torch.int32, device=device)
     scores_c = torch.full((U, T), float("-inf"), dtype=torch.float32, device=device)
     ru = row_user[:, None].expand_as(cols)
@@ -488,6 +518,14 @@ def rank_shard(model, news_vecs, shard: IndexedTestShard, ks=(5, 10, 100), prior
     seen: rank_eval's, one list per impression."""
     return rank_eval(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), ks=ks, prior=prior, news_time=news_time, window=window,
                      seen=seen)
+
+
+@torch.no_grad()
+def rank_shard_capped(model, news_vecs, shard: IndexedTestShard, news_group, group_cap, ks=(5, 10, 100), prior=None, news_time=None, window=None,
+                      seen=None):
+    """rank_shard under group caps: rank_eval_capped over the impressions of a test shard."""
+    return rank_eval_capped(model, news_vecs, shard.hist, shard.mask, _shard_targets(shard), news_group, group_cap, ks=ks, prior=prior,
+                            news_time=news_time, window=window, seen=seen)
 
 
 @torch.no_grad()

@@ -3,7 +3,7 @@
 the same device.
 
     python tools/rank_probe.py [--news 100001] [--dim 400] [--targets 4] [--exclude 50] [--users 64 8192] [--block 1024]
-                               [--calls 30] [--warmup 5] [--out FILE] [--pool] [--seen L]
+                               [--calls 30] [--warmup 5] [--out FILE] [--pool] [--seen L] [--group G --group-cap c]
 
 Both sides take the same fp32 inputs.  The baseline forms the [block, V] scores of a block of users, reads the targets' scores
 out of them and counts, per target, the news that score strictly higher (what the excluded ones contribute is taken back from
@@ -18,7 +18,12 @@ the same shapes, alternating with the plain fused call and timed the same way; o
 --seen L: likewise, the fused call with a list of L random ids per user through the CSR path (ops.ExclusionLists, built once)
 alternating with the fused call with the dense list (--exclude ids per user); one JSON line per U with both, the ratio of the
 medians and, from the library's own launch timer, the share of the named-id pass in each call beside the arithmetic
-2 % x (1 + ceil((L - 64) / 128))."""
+2 % x (1 + ceil((L - 64) / 128)).
+--group G --group-cap c: likewise, the capped fused call (ops.score_rank_capped(..., group, group_cap, n_groups=G): G random groups,
+every tenth news in none, at most 4 targets per row) alternating with the plain fused call; one JSON line per U with both, the
+ratio of the medians, the fractions of capped-out (-1) targets and of targets the cap moved up, and from the library's launch
+timer the share of the mask and counting launches.  The arithmetic beside it: about 8 VALU instructions per (chunk, user,
+target, block of 64 groups) against 416 MFMAs per wave and chunk at N = 400."""
 import argparse
 import json
 import os
@@ -110,6 +115,21 @@ def pool_row(plain, pooled, calls, warmup):
     return row
 
 
+def launch_shares(call, prefixes, reps=5):
+    """The share of the launches whose label starts with each prefix in the launches of `call`, by the library's per-launch timer."""
+    call()
+    torch.cuda.synchronize()
+    _lib.prof_enable(1)
+    _lib.prof_collect()
+    for _ in range(reps):
+        call()
+    torch.cuda.synchronize()
+    got = _lib.prof_collect()
+    _lib.prof_enable(0)
+    total = sum(ms for _, ms in got.values())
+    return {p: round(sum(ms for label, (_, ms) in got.items() if label.startswith(p)) / total, 4) if total > 0 else None for p in prefixes}
+
+
 def named_share(call, reps=5):
     """The share of the named-id pass in the launches of `call`, by the library's per-launch timer."""
     call()
@@ -139,9 +159,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--pool", action="store_true", help="time the pooled fused call against the plain fused call")
     ap.add_argument("--seen", type=int, default=0, help="time the fused call with L random ids per user in CSR lists against the dense list")
+    ap.add_argument("--group", type=int, default=0, help="with --group-cap: time the capped fused call (this many random groups) against the plain one")
+    ap.add_argument("--group-cap", type=int, default=0)
     args = ap.parse_args()
     if args.seen and args.pool:
         raise SystemExit("--seen L comes alone")
+    if bool(args.group) != bool(args.group_cap) or (args.group and (args.pool or args.seen)):
+        raise SystemExit("--group G and --group-cap c come together, and alone")
+    if args.group and args.targets > _lib.NR_RANK_MAX_CAPPED_TARGETS:
+        raise SystemExit(f"a capped call takes at most {_lib.NR_RANK_MAX_CAPPED_TARGETS} targets per row")
     if not torch.cuda.is_available():
         raise SystemExit("rank_probe needs a GPU")
     if args.calls < 20:
@@ -169,6 +195,23 @@ def main():
             row["csr_over_dense"] = round(row["csr"]["median_ms"] / row["dense"]["median_ms"], 4)
             row["named_share_dense"], row["named_share_csr"] = named_share(lambda: fused(*a)), named_share(csr)
             row["named_share_formula"] = round(0.02 * (1 + max(0, -(-(args.seen - 64) // 128))), 4)
+            lines.append(row)
+            print(json.dumps(row), flush=True)
+            continue
+        if args.group:
+            group = torch.randint(0, args.group, (args.news,), generator=g, dtype=torch.int32)
+            group[3::10] = -1                                                     # every tenth news is in no group
+            group = group.cuda()
+            capped = lambda: ops.score_rank_capped(news, user, targets, group, args.group_cap, n_groups=args.group, exclude=exclude, ks=KS)
+            row = {"U": U, "V": args.news, "N": args.dim, "T": args.targets, "E": args.exclude, "groups": args.group, "group_cap": args.group_cap}
+            got = pool_row(lambda: fused(*a), capped, args.calls, args.warmup)
+            row.update({"mode": "group", "plain": got["plain"], "capped": got["pooled"]})
+            row["capped_over_plain"] = round(row["capped"]["median_ms"] / row["plain"]["median_ms"], 4)
+            r_c, r_p = capped()[0], fused(*a)[0]
+            row["capped_out_fraction"] = round(float((r_c == -1).float().mean()), 6)
+            row["moved_up_fraction"] = round(float(((r_c > 0) & (r_c < r_p)).float().mean()), 6)
+            row["consistent"] = bool((((r_c == 0) == (r_p == 0)) & ((r_c <= 0) | (r_c <= r_p))).all())
+            row["launch_shares"] = launch_shares(capped, ("rank_group_masks", "rank_named", "rank_count", "rank_final"))
             lines.append(row)
             print(json.dumps(row), flush=True)
             continue
@@ -203,7 +246,7 @@ def main():
         lines.append(row)
         print(json.dumps(row), flush=True)
         del user
-    if args.pool or args.seen:
+    if args.pool or args.seen or args.group:
         write(args.out, lines)
         return
     last = lines[-1]
