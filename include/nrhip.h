@@ -211,7 +211,12 @@ int nr_mhsa_bwd(const nr_mhsa_desc* d, const void* qkv, const void* dy, void* dq
  * (the layout nr_mhsa_fwd produces; the Python surface class packs the reference's [n, h, L, d] views into it).
  * mask: [n, L] key-side 0/1 or NULL.  y: [n*L, N] dtype, heads concatenated (src/model/model_utils.py:94).
  * p_out / seed_out: optional dropout on y (element index m*N + c), 0 = none.
- * bwd: dqkv [n*L, 3N] dtype = gradient of the three projections given dy [n*L, N].                          */
+ * bwd: dqkv [n*L, 3N] dtype = gradient of the three projections given dy [n*L, N].
+ * Input domain (here and in nr_mhsa_fwd / nr_mhsa_bwd with a materialised Q|K|V): scores s = q.k / sqrt(d_head) with
+ * |s| <= 60, and the maximum over ALL keys of a row at most 45 above the maximum over its VALID keys.  The kernels factor
+ * the row maximum out of exp(s) and take it over every key, masked ones included: a masked key more than ~87 above every
+ * valid key under a maximum above ~60 makes the valid terms and the scaled 1e-8 underflow in fp32, and the result is then
+ * not the reference's.  (The gathering forward, proj_table, takes the maximum over the valid keys of a one-run mask.)   */
 int nr_sdpa_fwd(const void* qkv, const float* mask, void* y, int n, int L, int heads, int d_head, int dtype, float p_out,
                 uint32_t seed_out, nr_stream_t stream);
 int nr_sdpa_bwd(const void* qkv, const float* mask, const void* dy, void* dqkv, int n, int L, int heads, int d_head,

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import metric_row_as_device
+from helpers import MASKS, masks as _masks, metric_row_as_device
 from oracle import nr_oracle as O
 from newsrecommendation_amd import _lib, data as D, ops, train as TR
 
@@ -198,27 +198,6 @@ def test_naml_bf16_eval_job_against_the_fp64_oracle(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------- the gathering kernel
-MASKS = ("ones", "front", "back", "middle", "holes", "single", "none_valid")
-
-
-def _masks(n, L, g):
-    """[n, L] 0/1 key masks, pattern i % 7 of MASKS for sequence i; returns (mask, pattern index per sequence)."""
-    pos = torch.arange(L)[None, :]
-    kind = torch.arange(n) % len(MASKS)
-    ln = torch.randint(1, L + 1, (n,), generator=g)
-    start = (torch.rand(n, generator=g) * (L - ln + 1)).long().clamp(max=L - ln)
-    run = (pos >= start[:, None]) & (pos < (start + ln)[:, None])
-    front = pos >= (L - ln)[:, None]
-    back = pos < ln[:, None]
-    holes = (torch.rand(n, L, generator=g) < 0.6) & front
-    holes[:, -1] = True
-    single = pos == torch.randint(0, L, (n,), generator=g)[:, None]
-    m = torch.ones(n, L, dtype=torch.bool)
-    for k, pat in enumerate((m, front, back, run, holes, single, torch.zeros(n, L, dtype=torch.bool))):
-        m = torch.where((kind == k)[:, None], pat, m)
-    return m.float(), kind
-
-
 def _one_run(mask):
     """[n] bool: the unmasked positions of the sequence form one non-empty run."""
     d = torch.diff(torch.nn.functional.pad(mask, (1, 1)), dim=1)
