@@ -54,6 +54,8 @@ struct EpiArgs {
   int a_gap;              // LDS-DMA kernel: RowSrc::gap of the A operand (set by the launcher)
   const int32_t* a_idx;   // with row_count: the A row of compacted row m is a_idx[m] (A itself stored in live-list order) instead of row_idx[m]
   int a_dense;            // with row_count (weights-in-registers kernel): A row of compacted row m is m itself; row_idx only scatters the output
+  int tail_cus;           // LDS-DMA kernel (set by its launcher): > 0 = compact SCATTER with the 256-row tile, workgroups mapped by
+                          // nr_scatter_tail_role with this many resident workgroups (the CU count); 0 = the plain tile mapping
 };
 
 // C-level launchers (enqueue only).  dtype selects T.

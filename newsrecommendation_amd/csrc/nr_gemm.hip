@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "nr_gemm.h"
+#include "nr_scatter_tail.h"
 
 namespace {
 
@@ -937,6 +938,13 @@ int launch_nt_wide_e(const RowSrc& A, const void* B, int ldb, int M, int N, int 
 //   (chunk ^ P[(row >> 2) & 3], P = {0,2,3,1}) so that the later ds_read_b128 fragment reads of the
 //   linear LDS image are bank-conflict free (swizzle on the source side, LDS stays lane-linear).
 // Row overruns are clamped (the rows are never stored); the K tail relies on B's zero padding.
+// Tile mapping: workgroup b -> row tile (b / (8 nchunks)) * 8 + b % 8, column chunk (b / 8) % nchunks, all k-steps.  The compact
+// id-sorted scatter with the 256-row tile (one workgroup per CU: the tiles run in rounds of as many as there are CUs) maps by
+// nr_scatter_tail_role instead: the tiles of the last, partly filled round are split over K among the CUs that would idle,
+// every part running the ring over its own k-steps and then the unchanged scatter epilogue on its partial sums (the
+// epilogue -- dropout scale, run merging, fp32 atomics -- is linear in the accumulators).  Not in deterministic mode.
+// (Every <EPI_SCATTER, ., false, 4> instantiation carries the role branch and the k offset, the non-compact scatter with
+//  tail_cus = 0 included: same registers and LDS as before, not the same code.  The other epilogues compile as they did.)
 // =========================================================================================
 __device__ __forceinline__ void dma16(const void* gsrc, uint32_t lds_dst) {
   uint32_t keep;
@@ -964,13 +972,27 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
   constexpr int NS = dma_ring_stages(STAGE, WM);
   constexpr int SCW = WBN + 4;
   constexpr int AB = DBM * 64;                   // byte offset of the B tile inside a stage
+  // the tiles of the last, partly filled round of the table-gradient scatter are split over K (nr_scatter_tail.h)
+  constexpr bool TAIL_SPLIT = (EPI == EPI_SCATTER) && !PK && WM == 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const bool det = nr_fix_on();          // deterministic mode: fixed-point accumulation of the outputs (nr_common.h)
   float* sC = reinterpret_cast<float*>(smem);
   const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;
 
   const int bid = blockIdx.x, per = 8 * nchunks;
-  const int mt = (bid / per) * 8 + (bid & 7), nch = (bid >> 3) % nchunks;
+  int mt = (bid / per) * 8 + (bid & 7);
+  const int nch = (bid >> 3) % nchunks;
+  // k-steps [kb, kb + nk) of the tile: all of them, except in the tail split of the compact scatter
+  int kb = 0, nk = (K + BK - 1) / BK;
+  if constexpr (TAIL_SPLIT) {
+    if (ep.tail_cus > 0) {                       // (the launcher: compact rows, one column chunk, tail_cus more workgroups)
+      const ScatterTailRole role = nr_scatter_tail_role(bid, *ep.row_count, det ? 0 : ep.tail_cus, nk);
+      if (role.tile < 0) return;
+      mt = role.tile;
+      kb = role.k_begin;
+      nk = role.k_end - role.k_begin;
+    }
+  }
   const int m0 = mt * DBM, nbase = nch * WBN;
   if (m0 >= M) return;
   const int N = min(WBN, Ntot - nbase);
@@ -1032,7 +1054,9 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
       isA[t] = false;
     }
   }
+  const int kofs = TAIL_SPLIT ? kb * BK : 0;      // first column of this workgroup's k range
   auto issue = [&](int stage, int k0) {
+    if (TAIL_SPLIT) k0 += kofs;
 #pragma unroll
     for (int t = 0; t < PB + 1; ++t) {
       if (t < PB || extra) {
@@ -1092,7 +1116,6 @@ __global__ __launch_bounds__(128 * WM) void gemm_nt_dma_kernel(const bf16_t* __r
     }
     if (wid == NW - 1) dma16(ep.rowscale + min(m0 + 4 * lane, M - 4), lds0 + NS * STAGE + GBYTES);   // alpha of rows m0 .. m0+255
   }
-  const int nk = (K + BK - 1) / BK;
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
     if (s < nk) issue(s, s * BK);
@@ -1778,6 +1801,88 @@ int launch_nt_wreg_m(const RowSrc& A, const void* B, int ldb, int M, int N, int 
 }
 
 // =========================================================================================
+// The balanced walk of the two fused pooling kernels.  The flagged sequences of the whole launch form one ordered list of T
+// entries; workgroup b0 of G walks the entries of rank b0, b0 + G, b0 + 2G, ... so every workgroup gets floor(T / G) or
+// ceil(T / G) pipeline steps whatever the pattern of the flags (the strided partition of the SEQUENCES, filtered afterwards,
+// left the unluckiest workgroup 12 .. 21 % above the mean at the news level, and the launch lasts as long as that one).
+// Every workgroup ranks all n flags itself (n ints out of L2), with no LDS beyond the list and the 8 wave counts: wave w takes
+// a contiguous run of 64-flag ballots and counts them; one barrier gives it its starting rank; then it passes over its
+// ballots again, 64 at a time with lane j on ballot j (a scan of the popcounts ranks them), and picks the set bits whose rank
+// is b0 (mod G).  The first 64 ballots of a wave's run stay in a register (all of them up to n = 32 768), the ones beyond are
+// formed again from the flags.  The assignment is a function of the flags alone.  Returns the number of steps; sList is complete after the caller's next barrier.
+// =========================================================================================
+template <int NW>
+__device__ __forceinline__ int pool_balanced_walk(const int32_t* __restrict__ flags, int n, int G, int b0, int* sList, int* sCnt, int wid,
+                                                  int lane) {
+  const int nb = (n + 63) >> 6, per = (nb + NW - 1) / NW;
+  const int i0 = min(wid * per, nb), i1 = min(i0 + per, nb);
+  constexpr int U = 16, KEPT = 64;                         // flag loads in flight per wave | ballots kept in the register
+  static_assert(KEPT % U == 0, "a chunk of U ballots is kept as a whole or not at all");
+  uint64_t mybal = 0;
+  int cnt = 0;
+  // U ballots from index i on (clamped loads: always in bounds; ballots past i1 are never used)
+  auto ballots = [&](int i, uint64_t (&bal)[U]) {
+    int f[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f[u] = flags[min((i + u) * 64 + lane, n - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u) bal[u] = __ballot((i + u) * 64 + lane < n && f[u] != 0);
+  };
+  for (int i = i0; i < i1; i += U) {
+    uint64_t bal[U];
+    ballots(i, bal);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (i + u < i1) {                                    // wave-uniform
+        if (i + u - i0 == lane) mybal = bal[u];            // (lane < KEPT always)
+        cnt += __popcll(bal[u]);
+      }
+    }
+  }
+  if (lane == 0) sCnt[wid] = cnt;
+  __syncthreads();
+  int rank = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const int cw = sCnt[w];
+    rank += w < wid ? cw : 0;
+    total += cw;
+  }
+  // second pass, 64 ballots at a time with lane j on ballot j: a scan of the popcounts gives every ballot the ranks [lo, hi) of
+  // its set bits, the lane looks for the workgroup's ranks b0 + q G in there (at most one when G >= 64) and finds the bit
+  for (int g0 = i0; g0 < i1; g0 += KEPT) {
+    uint64_t gb = mybal;
+    if (g0 != i0) {                                        // wave-uniform: formed again from the flags
+      gb = 0;
+#pragma unroll 1
+      for (int k = 0; k < KEPT; k += U) {
+        uint64_t bal[U];
+        ballots(g0 + k, bal);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (g0 + k + u < i1 && k + u == lane) gb = bal[u];
+      }
+    }
+    const int c = __popcll(gb);
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += t;
+    }
+    const int lo = rank + incl - c, hi = rank + incl;
+    int q = lo <= b0 ? 0 : (lo - b0 + G - 1) / G;
+    for (int t = b0 + q * G; t < hi; t += G, ++q) {
+      uint64_t w = gb;
+      for (int z = t - lo; z > 0; --z) w &= w - 1;         // drop the set bits in front of it
+      sList[q] = (g0 + lane) * 64 + (__ffsll((unsigned long long)w) - 1);
+    }
+    rank += __shfl(incl, 63, 64);
+  }
+  return b0 < total ? (total - b0 + G - 1) / G : 0;
+}
+
+// =========================================================================================
 // Fused additive-attention pooling FORWARD (src/model/model_utils.py:21-30) for sequences of L <= 32 tokens:
 //   e = tanh(x W1^T + b1) -> a = exp(e w2 + b2) (* mask) / (sum + 1e-8) -> out = sum_l a_l x_l
 // in ONE pass over x.  The unfused path ran the weights-in-registers fc1 GEMM (x in, e out) and then pool_core_fwd
@@ -1792,7 +1897,8 @@ int launch_nt_wreg_m(const RowSrc& A, const void* B, int ldb, int M, int N, int 
 //       32 lanes) -> alpha (global) -> this wave's 4 rows of the weighted sum over the x rows STILL IN the ring -> sRed
 //   S3  sequence k    : MFMAs -> tanh -> e (global, bf16: the backward needs it) -> partial dots with w2 -> sPart[k % 2]
 // Vector-memory bookkeeping is static as above: every wave issues PW DMAs + S + 2 stores per step.
-// Sequences nobody needs (flags == 0) get zeros in out / alpha from the prologue and are left out of the walk.
+// Sequences nobody needs (flags == 0) get zeros in out / alpha from the prologue and are left out of the walk; the needed ones
+// are dealt out by RANK (pool_balanced_walk above), so every workgroup runs floor(T / G) or ceil(T / G) steps.
 // =========================================================================================
 struct PoolFusedArgs {
   const bf16_t* x; int ldx;          // [n * L, ldx]
@@ -1837,30 +1943,14 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
   float* sRed = reinterpret_cast<float*>(smem + Cfg::RED);
   int* sList = reinterpret_cast<int*>(smem + Cfg::LIST);
 
-  // ---- the walk: this workgroup's needed sequences, in order; the others get their zeros here
+  // ---- the walk: with flags, the needed sequences of rank b0, b0 + G, ... (pool_balanced_walk), in order; the zeros of the
+  //      sequences left out stay on the strided partition b0, b0 + G, ... of the SEQUENCES.  Without flags: that partition.
   const int G = gridDim.x, b0 = blockIdx.x;
   int nsteps = b0 < a.n ? (a.n - b0 + G - 1) / G : 0;
   if (a.needed != nullptr) {
     __shared__ int sCnt[NW + 1];
     const int cand = nsteps;
-    int run = 0;
-    for (int base = 0; base < cand; base += 512) {
-      const int c = base + tid, sq = b0 + c * G;
-      const bool live = c < cand && a.needed[sq] != 0;
-      const uint64_t bal = __ballot(live);
-      if (lane == 0) sCnt[wid] = __popcll(bal);
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const int cw = sCnt[w];
-        before += w < wid ? cw : 0;
-        total += cw;
-      }
-      if (live) sList[run + before + __popcll(bal & ((1ull << lane) - 1ull))] = sq;
-      run += total;
-      __syncthreads();
-    }
+    const int run = pool_balanced_walk<NW>(a.needed, a.n, G, b0, sList, sCnt, wid, lane);
     // zeros for the sequences left out: a wave per sequence
     for (int c = wid; c < cand; c += NW) {
       const int sq = b0 + c * G;
@@ -2077,6 +2167,7 @@ __global__ __launch_bounds__(512) void pool_fused_fwd_kernel(PoolFusedArgs a, in
 //   C   sequence k - 2: dX = dpre . W1 (W1^T resident in registers, A fragments from the ring) + alpha g    -> global (bf16)
 // Sequences with a zero pooled gradient (flags) are left out of the walk: their dX rows are zero-filled in the prologue, their
 // dpre rows only where a 32-row slab of the weight-gradient GEMM can reach them (within `reach` sequences of a live one).
+// The live ones are dealt out by RANK (pool_balanced_walk above): floor(T / G) or ceil(T / G) steps per workgroup.
 // Vector-memory bookkeeping is static: every wave issues PW DMAs, 5 loads and 6 stores per step, in that order.
 // =========================================================================================
 struct PoolFusedBwdArgs {
@@ -2128,30 +2219,14 @@ __global__ __launch_bounds__(512) void pool_fused_bwd_kernel(PoolFusedBwdArgs a,
   float* sRedW = sW2 + 256;
   int* sList = reinterpret_cast<int*>(smem + Cfg::LIST);
 
-  // ---- the walk: this workgroup's sequences with a non-zero pooled gradient; zeros for the others
+  // ---- the walk: with flags, the sequences with a non-zero pooled gradient of rank b0, b0 + G, ... (pool_balanced_walk); the
+  //      zeros of the others stay on the strided partition b0, b0 + G, ... of the SEQUENCES.  Without flags: that partition.
   const int G = gridDim.x, b0 = blockIdx.x;
   int nsteps = b0 < a.n ? (a.n - b0 + G - 1) / G : 0;
   if (a.nz != nullptr) {
     __shared__ int sCnt[NW + 1];
     const int cand = nsteps;
-    int run = 0;
-    for (int base = 0; base < cand; base += 512) {
-      const int c = base + tid, sq = b0 + c * G;
-      const bool live = c < cand && a.nz[sq] != 0;
-      const uint64_t bal = __ballot(live);
-      if (lane == 0) sCnt[wid] = __popcll(bal);
-      __syncthreads();
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const int cw = sCnt[w];
-        before += w < wid ? cw : 0;
-        total += cw;
-      }
-      if (live) sList[run + before + __popcll(bal & ((1ull << lane) - 1ull))] = sq;
-      run += total;
-      __syncthreads();
-    }
+    const int run = pool_balanced_walk<NW>(a.nz, a.n, G, b0, sList, sCnt, wid, lane);
     for (int c = wid; c < cand; c += NW) {                 // a wave per zero-gradient sequence
       const int sq = b0 + c * G;
       if (a.nz[sq] != 0) continue;                         // wave-uniform
@@ -2437,8 +2512,25 @@ int launch_nt_dma_w(const RowSrc& A, const void* B, int ldb, int M, int N, int K
   auto kern = gemm_nt_dma_kernel<EPI, NT16, PK, WM>;
   NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   const int tilesM = (M + DBM - 1) / DBM, nchunks = (N + NT16 * 16 - 1) / (NT16 * 16);
-  const int grid = ((tilesM + 7) / 8) * 8 * nchunks;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * WM), smem, stream, (const bf16_t*)A.base, A.ld, (const bf16_t*)B, ldb, M, N, K, ep, nchunks);
+  int grid = ((tilesM + 7) / 8) * 8 * nchunks;
+  EpiArgs epl = ep;
+  epl.tail_cus = 0;
+  if constexpr (EPI == EPI_SCATTER && !PK && WM == 4) {
+    // compact rows in one column chunk: the last round's tiles are split over K among the idle CUs (nr_scatter_tail.h);
+    // the workgroups that may be needed for it are launched on top and return at once when they are not
+    if (ep.row_count != nullptr && nchunks == 1) {
+      static int cus = 0;
+      if (cus == 0) {
+        int dev = 0, c = 0;
+        NR_CHECK_HIP(hipGetDevice(&dev));
+        NR_CHECK_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
+        cus = c >= 8 ? c : 256;
+      }
+      epl.tail_cus = cus;
+      grid = nr_scatter_tail_grid(M, cus);
+    }
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * WM), smem, stream, (const bf16_t*)A.base, A.ld, (const bf16_t*)B, ldb, M, N, K, epl, nchunks);
   NR_CHECK_LAUNCH();
   return NR_OK;
 }
