@@ -695,7 +695,17 @@ int nr_prof_collect(char* buf, size_t n);
  * The two MFMA GEMM building blocks on dense operands (used by every op above; exported for unit tests
  * and kernel-level measurement).  A [M, lda], B [N, ldb] of dtype; C [M, ldc] of out_dtype:
  *   nr_gemm_nt:  C = A . B^T (+ bias[N]) (tanh if act_tanh)
- *   nr_gemm_tn:  dW[N, ldw] (fp32) += dC[M, ldc]^T . A[M, lda] ; db[N] += column sums of dC (db may be NULL) */
+ *   nr_gemm_tn:  dW[N, ldw] (fp32) += dC[M, ldc]^T . A[M, lda] ; db[N] += column sums of dC (db may be NULL)
+ * K (and for nr_gemm_tn N), lda, ldb and the ldc of dC are multiples of the 16-byte chunk, ldc of C a multiple of 4; a call
+ * that breaks this, an operand off a 16-byte boundary or an empty problem returns NR_ERR_ARG before anything is launched.
+ * B padding (nr_gemm_nt, NR_BF16): when ldb >= roundup32(K), the columns [K, roundup32(K)) of every row of B MUST BE ZERO.
+ * The LDS-DMA and weights-in-registers kernels, which such a call may take, run whole 32-deep k-steps and do not predicate
+ * the K tail of B.  nr_cast_pad with ld_dst >= roundup32(cols) (ops.pack(..., ld=), and its default ld) produces exactly
+ * this.  With ldb < roundup32(K) (e.g. ldb == K) the call takes kernels that predicate the tail, and whatever follows
+ * column K -- the next row's data -- is not read.  Columns from roundup32(K) on are never read.  A has NO such requirement:
+ * its K tail is clamped to valid columns, so the slack columns [K, lda) of A may hold anything, NaN included.
+ * nr_gemm_tn in deterministic mode (nr_set_deterministic) accumulates dW and db in fixed point like every other weight
+ * gradient; the scratch then needs (N - 1) * ldw + K + N elements. */
 int nr_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, const float* bias, int act_tanh, void* C,
                int ldc, int out_dtype, int M, int N, int K, nr_stream_t stream);
 int nr_gemm_tn(int dtype, const void* dC, int ldc, const void* A, int lda, float* dW, int ldw, float* db, int M, int N,

@@ -627,6 +627,13 @@ int nr_gemm_tn(int dtype, const void* dC, int ldc, const void* A, int lda, float
   NR_CHECK_ARG(dtype_ok(dtype) && dC && A && dW, "gemm_tn: bad dtype / null operand");
   NR_DEVICE_GUARD(stream, dW);
   RowSrc a = dense_rows(A, lda, K);
+  DetScope det((hipStream_t)stream);                 // deterministic mode: dW (slack columns included: they get + 0) and db
+  if (det.on() && M > 0 && N > 0 && K > 0 && ldw >= K) {
+    det.add(dW, (size_t)(N - 1) * ldw + K);
+    det.add(db, (size_t)N);
+    int rc = det.begin(true, false);
+    if (rc) return rc;
+  }
   return nr_launch_gemm_tn(dtype, dC, ldc, a, dW, ldw, db, M, N, K, N, K, (hipStream_t)stream);
 }
 

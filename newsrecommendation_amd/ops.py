@@ -1348,7 +1348,13 @@ def dropout_mask(count: int, p: float, seed: int, device) -> torch.Tensor:
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, bias=None, act_tanh=False, out_dtype=None) -> torch.Tensor:
-    """C = a . b^T (+bias)(tanh): the MFMA GEMM building block on dense operands (unit tests / measurement)."""
+    """C = a . b^T (+bias)(tanh): the MFMA GEMM building block on dense operands (unit tests / measurement).
+
+    `a` and `b` may be row-strided views (their row strides are passed as lda / ldb).  B padding, bf16: when b.stride(0) >=
+    roundup32(K), the columns [K, roundup32(K)) of b's storage must be zero -- the LDS-DMA and weights-in-registers kernels
+    run whole 32-deep k-steps and do not predicate the K tail of B; `pack(w, code)` / `pack(w, code, ld=...)` produce such an
+    operand.  A column slice of a wider non-zero matrix is therefore only valid for K % 32 == 0 (or with a row stride below
+    roundup32(K), which selects the kernels that predicate the tail).  `a` has no such requirement: its K tail is clamped."""
     _need_gpu(a, b)
     code = NR_BF16 if a.dtype == torch.bfloat16 else NR_F32
     M, K = a.shape
