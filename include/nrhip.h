@@ -222,6 +222,28 @@ int nr_sdpa_fwd(const void* qkv, const float* mask, void* y, int n, int L, int h
 int nr_sdpa_bwd(const void* qkv, const float* mask, const void* dy, void* dqkv, int n, int L, int heads, int d_head,
                 int dtype, float p_out, uint32_t seed_out, nr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Sequence lengths, per entry point (L = tokens of one sequence; the clicked history at the user level):
+ *   nr_sdpa_fwd / nr_sdpa_bwd            1 <= L <= 64 ("bad shape" beyond; unchanged)
+ *   nr_sdpa_long_fwd / nr_sdpa_long_bwd  64 < L <= 128 only; any other L is refused before any launch
+ *   nr_mhsa_fwd / nr_mhsa_bwd            1 <= L <= 128 (materialised Q|K|V); proj_table stays L <= 64; padding-token
+ *                                        substitution, sequence lists and compact rows (row_ws paths) stay L <= 32, the fused
+ *                                        title kernel L <= 32
+ *   nr_additive_pool_fwd / _bwd          1 <= L <= 128; the fused pooling kernels and the live-slab weight gradient stay L <= 32
+ * Routes of the attention core at 64 < L <= 128:
+ *   bf16, d_head % 4 == 0, d_head <= 32, qkv / y / dy / dqkv 8-byte aligned: matrix-core kernels, the score matrix as RB x RB
+ *     tiles of 32 x 32, RB = ceil(L / 32) (profiler labels attn_long_fwd[bf16, / attn_long_bwd[bf16,)
+ *   everything else (fp32; bf16 with a misaligned buffer or d_head % 4 != 0): the LDS/VALU kernels (attn_fwd[ / attn_bwd[),
+ *     d_head in {4, 8, 16, 20, 32}
+ * Same softmax, same mask-after-exp, same output dropout counters (element index m*N + c) and the same input domain as
+ * nr_sdpa_*: |s| <= 60, row maximum over all keys at most 45 above the maximum over the valid keys.  An all-masked sequence
+ * gives exact zeros.  No atomics: a repeated call is bit-identical.
+ * The pooling core at 64 < L <= 128 gives each lane of its softmax wave two tokens (lane, lane + 64), summed in a fixed order. */
+int nr_sdpa_long_fwd(const void* qkv, const float* mask, void* y, int n, int L, int heads, int d_head, int dtype, float p_out,
+                     uint32_t seed_out, nr_stream_t stream);
+int nr_sdpa_long_bwd(const void* qkv, const float* mask, const void* dy, void* dqkv, int n, int L, int heads, int d_head,
+                     int dtype, float p_out, uint32_t seed_out, nr_stream_t stream);
+
 /* Index validation (what torch's embedding / cross_entropy raise IndexError for; the kernels themselves trust their
  * indices).  Counts the entries of ids[i*stride], i < count, outside [0, rows) into *bad (DEVICE int32, accumulated:
  * zero it first).  The Python layer calls it when ops.CHECK_INDICES is on and raises IndexError.                */

@@ -123,6 +123,8 @@ SIGNATURES = {
     "nr_linear_workspace_bytes": [C.POINTER(LinearDesc)],
     "nr_sdpa_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u32, _vp],
     "nr_sdpa_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u32, _vp],
+    "nr_sdpa_long_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u32, _vp],
+    "nr_sdpa_long_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _u32, _vp],
     "nr_assemble_batch": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "nr_stack_rows": [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "nr_eval_metrics_workspace_bytes": [_i],

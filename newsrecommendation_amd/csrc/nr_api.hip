@@ -404,7 +404,7 @@ static MhsaPlan mhsa_plan(const nr_mhsa_desc* d) {
 static int mhsa_check(const nr_mhsa_desc* d, MhsaPlan* plan) {
   NR_CHECK_ARG(d != nullptr, "mhsa: null descriptor");
   NR_CHECK_ARG(dtype_ok(d->dtype), "mhsa: bad dtype %d", d->dtype);
-  NR_CHECK_ARG(d->n >= 0 && d->L >= 1 && d->L <= 64 && d->d_model >= 1 && d->heads >= 1 && d->d_head >= 1,
+  NR_CHECK_ARG(d->n >= 0 && d->L >= 1 && d->L <= 128 && d->d_model >= 1 && d->heads >= 1 && d->d_head >= 1,
                "mhsa: bad shape n=%d L=%d d_model=%d heads=%d d_head=%d", d->n, d->L, d->d_model, d->heads, d->d_head);
   const int ch = nr_chunk(d->dtype);
   NR_CHECK_ARG((3 * d->heads * d->d_head) % ch == 0, "mhsa: 3*news_dim=%d must be a multiple of %d for this dtype",
@@ -609,6 +609,37 @@ int nr_sdpa_bwd(const void* qkv, const float* mask, const void* dy, void* dqkv, 
   if (rc) return rc;
   if (n == 0) return NR_OK;
   NR_CHECK_ARG(dy != nullptr && dqkv != nullptr, "sdpa_bwd: null operand");
+  NR_DEVICE_GUARD(stream, dqkv);
+  return nr_launch_attn(true, dtype, qkv, mask, nullptr, dy, dqkv, n, L, heads, d_head, nr_make_drop(p_out, seed_out), (hipStream_t)stream);
+}
+
+// The bare core for long clicked histories (64 < L <= 128); nr_sdpa_* keeps its L <= 64 contract.
+static int sdpa_long_check(const void* qkv, int n, int L, int heads, int d_head, int dtype, float p_out) {
+  NR_CHECK_ARG(L > 64 && L <= 128, "sdpa_long: L=%d must be in [65, 128] (nr_sdpa_fwd / nr_sdpa_bwd serve L <= 64)", L);
+  NR_CHECK_ARG(dtype_ok(dtype), "sdpa_long: bad dtype %d", dtype);
+  NR_CHECK_ARG(n >= 0 && heads >= 1 && d_head >= 1, "sdpa_long: bad shape n=%d L=%d heads=%d d_head=%d", n, L, heads, d_head);
+  NR_CHECK_ARG(n == 0 || qkv != nullptr, "sdpa_long: null operand");
+  NR_CHECK_ARG(p_out >= 0.f && p_out < 1.f, "sdpa_long: dropout p out of range");
+  NR_CHECK_ARG((uint64_t)n * L * (uint64_t)(3 * heads * d_head) < 0xffffffffull, "sdpa_long: problem too large for 32-bit element counters");
+  return NR_OK;
+}
+
+int nr_sdpa_long_fwd(const void* qkv, const float* mask, void* y, int n, int L, int heads, int d_head, int dtype, float p_out,
+                     uint32_t seed_out, nr_stream_t stream) {
+  int rc = sdpa_long_check(qkv, n, L, heads, d_head, dtype, p_out);
+  if (rc) return rc;
+  if (n == 0) return NR_OK;
+  NR_CHECK_ARG(y != nullptr, "sdpa_long_fwd: null output");
+  NR_DEVICE_GUARD(stream, y);
+  return nr_launch_attn(false, dtype, qkv, mask, y, nullptr, nullptr, n, L, heads, d_head, nr_make_drop(p_out, seed_out), (hipStream_t)stream);
+}
+
+int nr_sdpa_long_bwd(const void* qkv, const float* mask, const void* dy, void* dqkv, int n, int L, int heads, int d_head, int dtype,
+                     float p_out, uint32_t seed_out, nr_stream_t stream) {
+  int rc = sdpa_long_check(qkv, n, L, heads, d_head, dtype, p_out);
+  if (rc) return rc;
+  if (n == 0) return NR_OK;
+  NR_CHECK_ARG(dy != nullptr && dqkv != nullptr, "sdpa_long_bwd: null operand");
   NR_DEVICE_GUARD(stream, dqkv);
   return nr_launch_attn(true, dtype, qkv, mask, nullptr, dy, dqkv, n, L, heads, d_head, nr_make_drop(p_out, seed_out), (hipStream_t)stream);
 }
@@ -1040,7 +1071,7 @@ static int pool_check(const nr_pool_desc* d) {
   NR_CHECK_ARG(d != nullptr, "additive_pool: null descriptor");
   NR_CHECK_ARG(dtype_ok(d->dtype), "additive_pool: bad dtype %d", d->dtype);
   const int ch = nr_chunk(d->dtype);
-  NR_CHECK_ARG(d->n >= 0 && d->L >= 1 && d->L <= 64 && d->N >= 1 && d->q >= 1, "additive_pool: bad shape n=%d L=%d N=%d q=%d", d->n, d->L,
+  NR_CHECK_ARG(d->n >= 0 && d->L >= 1 && d->L <= 128 && d->N >= 1 && d->q >= 1, "additive_pool: bad shape n=%d L=%d N=%d q=%d", d->n, d->L,
                d->N, d->q);
   NR_CHECK_ARG(d->N % ch == 0 && d->q % ch == 0, "additive_pool: N=%d and q=%d must be multiples of %d for this dtype", d->N, d->q, ch);
   NR_CHECK_ARG(d->ldw1 >= d->N, "additive_pool: ldw1=%d < N=%d", d->ldw1, d->N);

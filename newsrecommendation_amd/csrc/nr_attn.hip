@@ -4,7 +4,7 @@
 // denominator sum + 1e-8.  We evaluate the algebraically identical stable form
 //     a_ij = exp(s_ij - m_i) mask_j / (sum_j exp(s_ij - m_i) mask_j + 1e-8 exp(-m_i)).
 //
-// One workgroup = one sequence (L <= 64 tokens) x a group of HG heads; K and V of the group
+// One workgroup = one sequence (L <= 128 tokens) x a group of HG heads; K and V of the group
 // are staged in LDS as fp32; thread (i, head) owns query row i.  Backward is two phases
 // (row-wise: dQ + row statistics; column-wise: dK, dV) so no atomics are needed and the
 // result is deterministic.
@@ -92,7 +92,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(AttnArgs a) {
   }
 }
 
-template <typename T, int DH>
+// LCAP: capacity of the per-row statistics (64, or 128 for the long clicked histories: 64 < L <= 128)
+template <typename T, int DH, int LCAP = 64>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int seq = blockIdx.x, h0 = blockIdx.y * a.HG;
@@ -104,9 +105,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_kernel(AttnArgs a) {
   float* sV = sK + LW;
   float* sG = sV + LW;                 // d(ctx) after undoing the output dropout
   float* sMask = sG + LW;              // [L]
-  float* sM = sMask + 64;              // [HG][64] row max
-  float* sInv = sM + 64 * a.HG;        // [HG][64] 1/(sum + eps')
-  float* sRd = sInv + 64 * a.HG;       // [HG][64] sum_j a_ij dA_ij
+  float* sM = sMask + LCAP;            // [HG][LCAP] row max
+  float* sInv = sM + LCAP * a.HG;      // [HG][LCAP] 1/(sum + eps')
+  float* sRd = sInv + LCAP * a.HG;     // [HG][LCAP] sum_j a_ij dA_ij
   const T* qkv = reinterpret_cast<const T*>(a.qkv);
   const T* dy = reinterpret_cast<const T*>(a.dy);
   T* dqkv = reinterpret_cast<T*>(a.dqkv);
@@ -164,9 +165,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_kernel(AttnArgs a) {
     T* op = dqkv + (row0 + i) * 3 * N + (h0 + hh) * DH;
 #pragma unroll
     for (int c = 0; c < DH; ++c) op[c] = (T)(dq[c] * a.scale);
-    sM[hh * 64 + i] = m;
-    sInv[hh * 64 + i] = inv;
-    sRd[hh * 64 + i] = rd;
+    sM[hh * LCAP + i] = m;
+    sInv[hh * LCAP + i] = inv;
+    sRd[hh * LCAP + i] = rd;
   }
   __syncthreads();
 
@@ -186,8 +187,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_kernel(AttnArgs a) {
     for (int i = 0; i < L; ++i) {
       const float* qr = sQ + i * W + hh * DH;
       const float* gr = sG + i * W + hh * DH;
-      const float aij = __expf(dot_lds<DH>(k, qr) * a.scale - sM[hh * 64 + i]) * mj * sInv[hh * 64 + i];
-      const float ds = aij * (dot_lds<DH>(v, gr) - sRd[hh * 64 + i]) * a.scale;
+      const float aij = __expf(dot_lds<DH>(k, qr) * a.scale - sM[hh * LCAP + i]) * mj * sInv[hh * LCAP + i];
+      const float ds = aij * (dot_lds<DH>(v, gr) - sRd[hh * LCAP + i]) * a.scale;
 #pragma unroll
       for (int c = 0; c < DH; ++c) {
         dk[c] = fmaf(ds, qr[c], dk[c]);
@@ -207,6 +208,21 @@ template <typename T, int DH>
 int launch_attn(bool bwd, const AttnArgs& a, hipStream_t stream) {
   const int groups = (a.heads + a.HG - 1) / a.HG;
   const size_t lw = (size_t)a.L * a.HG * DH * sizeof(float);
+  if (a.L > 64) {
+    // long clicked histories: the same kernels, 128 mask slots (forward) / 128-row statistics (backward)
+    const size_t smem = bwd ? 4 * lw + (128 + 3 * 128 * a.HG) * sizeof(float) : 2 * lw + 128 * sizeof(float);
+    if (!bwd) {
+      auto k = attn_fwd_kernel<T, DH>;
+      NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      hipLaunchKernelGGL(k, dim3(a.n, groups), dim3(ATT_THREADS), smem, stream, a);
+    } else {
+      auto k = attn_bwd_kernel<T, DH, 128>;
+      NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      hipLaunchKernelGGL(k, dim3(a.n, groups), dim3(ATT_THREADS), smem, stream, a);
+    }
+    NR_CHECK_LAUNCH();
+    return NR_OK;
+  }
   if (!bwd) {
     const size_t smem = 2 * lw + 64 * sizeof(float);
     auto k = attn_fwd_kernel<T, DH>;
@@ -238,6 +254,8 @@ int launch_attn_d(bool bwd, int DH, const AttnArgs& a, hipStream_t s) {
 }  // namespace
 
 bool nr_attn_mfma_supported(int L, int d_head);
+int nr_launch_attn_long_mfma(bool bwd, int dtype, const void* qkv, const float* mask, void* y, const void* dy, void* dqkv, int n,
+                             int L, int heads, int d_head, const DropCfg& drop, hipStream_t stream);
 int nr_launch_attn_mfma(bool bwd, int dtype, const void* qkv, const float* mask, void* y, const void* dy, void* dqkv, int n,
                         int L, int heads, int d_head, const DropCfg& drop, hipStream_t stream, const uint32_t* tmask,
                         const float* bias, const int32_t* seq_list, const int32_t* seq_count, const int32_t* needed);
@@ -246,8 +264,15 @@ int nr_launch_attn_mfma(bool bwd, int dtype, const void* qkv, const float* mask,
 int nr_launch_attn(bool bwd, int dtype, const void* qkv, const float* mask, void* y, const void* dy, void* dqkv, int n, int L,
                    int heads, int d_head, const DropCfg& drop, hipStream_t stream, const uint32_t* tmask, const float* bias,
                    const int32_t* seq_list, const int32_t* seq_count, const int32_t* needed) {
-  NR_CHECK_ARG(L >= 1 && L <= 64, "attention: L=%d must be in [1, 64]", L);
+  NR_CHECK_ARG(L >= 1 && L <= 128, "attention: L=%d must be in [1, 128]", L);
   NR_CHECK_ARG(n >= 1 && heads >= 1, "attention: empty problem");
+  if (L > 64) {
+    // long clicked histories: bf16 on the matrix cores (RB x RB tiles), everything else on the LDS/VALU kernels below
+    // (`needed` is a hint: as at 33..64, every sequence is computed)
+    NR_CHECK_ARG(tmask == nullptr && seq_list == nullptr, "attention: padding-token substitution and sequence lists stop at L <= 32 (L=%d)", L);
+    const int rc = nr_launch_attn_long_mfma(bwd, dtype, qkv, mask, y, dy, dqkv, n, L, heads, d_head, drop, stream);
+    if (rc >= 0) return rc;
+  }
   // L <= 32: one wave per (sequence, head) on the matrix cores; longer sequences: LDS/VALU kernels below.
   if (nr_attn_mfma_supported(L, d_head)) {
     const int rc = nr_launch_attn_mfma(bwd, dtype, qkv, mask, y, dy, dqkv, n, L, heads, d_head, drop, stream, tmask, bias, seq_list,

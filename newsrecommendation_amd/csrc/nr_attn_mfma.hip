@@ -1570,6 +1570,255 @@ __global__ __launch_bounds__(AW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 
+// ---- 64 < L <= 128 (long clicked histories): the score matrix as RB x RB tiles of 32 x 32, RB = ceil(L / 32) in {3, 4} ----
+// The 64-row kernels above with the block count as a template parameter: every matrix is RB row-block images, a query
+// block meets all RB key blocks at once (softmax statistics stay lane-local plus one cross-half shuffle), and dK / dV of a
+// key block sum over the RB query blocks in a fixed order.  No prefetch across items and no gather source: one wave holds
+// 3 RB + 1 (forward) or 4 RB + 1 (backward) images, so a workgroup of AW waves owns the CU's LDS and a second item in
+// registers would only spill.  No atomics; every output element is written once by one lane.
+template <int RB>
+__global__ __launch_bounds__(AW * 64) void fwd_long_kernel(AttnMArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NI = 3 * RB + 1;
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  bf16_t* base = reinterpret_cast<bf16_t*>(smem) + (size_t)wid * NI * IMG;
+  bf16_t *sQ = base, *sK = base + RB * IMG, *sV = base + 2 * RB * IMG, *sO = base + 3 * RB * IMG;
+  float* sMask = reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(smem) + (size_t)AW * NI * IMG) + wid * 128;
+  const bf16_t* qkv = reinterpret_cast<const bf16_t*>(a.qkv);
+  bf16_t* y = reinterpret_cast<bf16_t*>(a.y);
+  const int L = a.L, d = a.d, heads = a.heads, N = heads * d, h2 = lane >> 5;
+  DropCfg nodrop;
+  nodrop.key = 0; nodrop.thresh = 0; nodrop.scale = 1.f;
+  const int hgroups = (heads + AW - 1) / AW;
+  const float c2 = a.scale * LOG2E;
+  for (long sb = blockIdx.x; sb < a.n; sb += gridDim.x)
+    for (int hgi = 0; hgi < hgroups; ++hgi) {
+      const int hraw = hgi * AW + wid;
+      const bool active = hraw < heads;
+      const int head = active ? hraw : 0, Lw = active ? L : 0;
+      const size_t row0 = (size_t)sb * L;
+      const bf16_t* src = qkv + row0 * 3 * N + head * d;
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        const int Lr = clampL(Lw, rb);
+        Slice t[3];
+#pragma unroll
+        for (int w = 0; w < 3; ++w) slice_load(t[w], src + (size_t)32 * rb * 3 * N + w * N, 3 * N, Lr, d, lane);
+        slice_put<false>(t[0], Lr, d, sQ + rb * IMG, lane, nodrop, 0, 0);
+        slice_put<false>(t[1], Lr, d, sK + rb * IMG, lane, nodrop, 0, 0);
+        slice_put<false>(t[2], Lr, d, sV + rb * IMG, lane, nodrop, 0, 0);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = 64 * u + lane;
+        sMask[j] = (j < Lw) ? (a.mask ? a.mask[row0 + j] : 1.f) : 0.f;   // keys >= L: weight 0
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int qb = 0; qb < RB; ++qb) {
+        f32x16 s[RB];
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
+          mm_rr(s[kb], sK + kb * IMG, sQ + qb * IMG, lane);      // keys of block kb x queries of block qb (lane = query)
+        }
+        // max of the RAW scores over the keys < L (scale > 0); key blocks 0 and 1 are complete (L > 64)
+        float mr = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (kb < 2 || 32 * kb + rowof(r, h2) < L) mr = fmaxf(mr, s[kb][r]);
+        mr = fmaxf(mr, __shfl_xor(mr, 32, 64));
+        const float m = mr * a.scale, mc = -mr * c2;
+        float sum = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float e = __builtin_amdgcn_exp2f(fmaf(s[kb][r], c2, mc)) * sMask[32 * kb + rowof(r, h2)];
+            s[kb][r] = e;
+            sum += e;
+          }
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.f / (sum + 1e-8f * __expf(-m));
+        f32x16 ctx;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ctx[r] = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[kb][r] *= inv;
+          mm_xt(ctx, s[kb], sV + kb * IMG, lane);
+        }
+        __syncthreads();
+        acc_to_img_t(ctx, 1.f, sO, lane);
+        __syncthreads();
+        const size_t r0 = row0 + 32 * qb;
+        img_t_to_global<true>(sO, y + r0 * N + head * d, N, clampL(Lw, qb), d, lane, a.drop, (uint32_t)(r0 * N + head * d), (uint32_t)N);
+      }
+      __syncthreads();
+    }
+}
+
+template <int RB>
+__global__ __launch_bounds__(AW * 64) void bwd_long_kernel(AttnMArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int NI = 4 * RB + 1;
+  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  bf16_t* base = reinterpret_cast<bf16_t*>(smem) + (size_t)wid * NI * IMG;
+  bf16_t *sQ = base, *sK = base + RB * IMG, *sV = base + 2 * RB * IMG, *sG = base + 3 * RB * IMG, *sO = base + 4 * RB * IMG;
+  float* sF = reinterpret_cast<float*>(reinterpret_cast<bf16_t*>(smem) + (size_t)AW * NI * IMG) + wid * 512;
+  float *sMask = sF, *sM = sF + 128, *sInv = sF + 256, *sRd = sF + 384;
+  const bf16_t* qkv = reinterpret_cast<const bf16_t*>(a.qkv);
+  const bf16_t* dy = reinterpret_cast<const bf16_t*>(a.dy);
+  bf16_t* dqkv = reinterpret_cast<bf16_t*>(a.dqkv);
+  const int L = a.L, d = a.d, heads = a.heads, N = heads * d, h2 = lane >> 5, li = lane & 31;
+  DropCfg nodrop;
+  nodrop.key = 0; nodrop.thresh = 0; nodrop.scale = 1.f;
+  const int hgroups = (heads + AW - 1) / AW;
+  for (long sb = blockIdx.x; sb < a.n; sb += gridDim.x)
+    for (int hgi = 0; hgi < hgroups; ++hgi) {
+      const int hraw = hgi * AW + wid;
+      const bool active = hraw < heads;
+      const int head = active ? hraw : 0, Lw = active ? L : 0;
+      const size_t row0 = (size_t)sb * L;
+      const bf16_t* src = qkv + row0 * 3 * N + head * d;
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        const int Lr = clampL(Lw, rb);
+        const size_t ro = (size_t)32 * rb;
+        Slice t[4];
+#pragma unroll
+        for (int w = 0; w < 3; ++w) slice_load(t[w], src + ro * 3 * N + w * N, 3 * N, Lr, d, lane);
+        slice_load(t[3], dy + (row0 + ro) * N + head * d, N, Lr, d, lane);
+        slice_put<false>(t[0], Lr, d, sQ + rb * IMG, lane, nodrop, 0, 0);
+        slice_put<false>(t[1], Lr, d, sK + rb * IMG, lane, nodrop, 0, 0);
+        slice_put<false>(t[2], Lr, d, sV + rb * IMG, lane, nodrop, 0, 0);
+        slice_put<true>(t[3], Lr, d, sG + rb * IMG, lane, a.drop, (uint32_t)((row0 + ro) * N + head * d), (uint32_t)N);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = 64 * u + lane;
+        sMask[j] = (j < Lw) ? (a.mask ? a.mask[row0 + j] : 1.f) : 0.f;
+      }
+      __syncthreads();
+      bf16_t* op = dqkv + row0 * 3 * N + head * d;
+      // phase A: per query block -> row statistics and dQ (lane = query i, registers = keys)
+#pragma unroll 1
+      for (int qb = 0; qb < RB; ++qb) {
+        f32x16 s[RB], p[RB];
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { s[kb][r] = 0.f; p[kb][r] = 0.f; }
+          mm_rr(s[kb], sK + kb * IMG, sQ + qb * IMG, lane);
+          mm_rr(p[kb], sV + kb * IMG, sG + qb * IMG, lane);       // dP^T
+        }
+        float m = -INFINITY;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            s[kb][r] *= a.scale;
+            if (kb < 2 || 32 * kb + rowof(r, h2) < L) m = fmaxf(m, s[kb][r]);
+          }
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        float sum = 0.f, rdu = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float e = __expf(s[kb][r] - m) * sMask[32 * kb + rowof(r, h2)];   // 0 for keys >= L
+            s[kb][r] = e;
+            sum += e;
+            rdu = fmaf(e, p[kb][r], rdu);
+          }
+        sum += __shfl_xor(sum, 32, 64);
+        rdu += __shfl_xor(rdu, 32, 64);
+        const float inv = 1.f / (sum + 1e-8f * __expf(-m));
+        const float rd = rdu * inv;
+        if (lane < 32) {
+          sM[32 * qb + lane] = m;
+          sInv[32 * qb + lane] = inv;
+          sRd[32 * qb + lane] = rd;
+        }
+        f32x16 dq;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq[r] = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < RB; ++kb) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[kb][r] = s[kb][r] * inv * (p[kb][r] - rd);   // dS^T
+          mm_xt(dq, s[kb], sK + kb * IMG, lane);
+        }
+        __syncthreads();
+        acc_to_img_t(dq, a.scale, sO, lane);
+        __syncthreads();
+        img_t_to_global<false>(sO, op + (size_t)32 * qb * 3 * N, 3 * N, clampL(Lw, qb), d, lane, nodrop, 0, 0);
+      }
+      __syncthreads();
+      // phase B: per key block -> dK, dV (lane = key j, registers = query rows), query blocks summed in order
+#pragma unroll 1
+      for (int kb = 0; kb < RB; ++kb) {
+        f32x16 dk, dv;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
+        const float mj = sMask[32 * kb + li];
+#pragma unroll
+        for (int qb = 0; qb < RB; ++qb) {
+          f32x16 s, dp;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+          mm_rr(s, sQ + qb * IMG, sK + kb * IMG, lane);
+          mm_rr(dp, sG + qb * IMG, sV + kb * IMG, lane);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int i = 32 * qb + rowof(r, h2);
+            const float pij = __expf(s[r] * a.scale - sM[i]) * mj * sInv[i];
+            s[r] = pij;
+            dp[r] = pij * (dp[r] - sRd[i]);
+          }
+          mm_xt(dk, dp, sQ + qb * IMG, lane);
+          mm_xt(dv, s, sG + qb * IMG, lane);
+        }
+        const int Lk = clampL(Lw, kb);
+        __syncthreads();
+        acc_to_img_t(dk, a.scale, sO, lane);
+        __syncthreads();
+        img_t_to_global<false>(sO, op + (size_t)32 * kb * 3 * N + N, 3 * N, Lk, d, lane, nodrop, 0, 0);
+        __syncthreads();
+        acc_to_img_t(dv, 1.f, sO, lane);
+        __syncthreads();
+        img_t_to_global<false>(sO, op + (size_t)32 * kb * 3 * N + 2 * N, 3 * N, Lk, d, lane, nodrop, 0, 0);
+      }
+      __syncthreads();
+    }
+}
+
+template <int RB>
+int launch_long_rb(bool bwd, const AttnMArgs& a, hipStream_t stream) {
+  long blocks = a.n;
+  const long cap = 256L * 4;     // one workgroup per CU fits (LDS); grid-stride beyond
+  if (blocks > cap) blocks = cap;
+  const size_t smem = bwd ? AW * ((4 * RB + 1) * IMG * sizeof(bf16_t) + 512 * sizeof(float))
+                          : AW * ((3 * RB + 1) * IMG * sizeof(bf16_t) + 128 * sizeof(float));
+  if (bwd) {
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bwd_long_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(bwd_long_kernel<RB>, dim3((unsigned)blocks), dim3(AW * 64), smem, stream, a);
+  } else {
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_long_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(fwd_long_kernel<RB>, dim3((unsigned)blocks), dim3(AW * 64), smem, stream, a);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+int launch_long(bool bwd, const AttnMArgs& a, hipStream_t stream) {
+  return a.L > 96 ? launch_long_rb<4>(bwd, a, stream) : launch_long_rb<3>(bwd, a, stream);
+}
+
+
 // ==========================================================================================
 // Fused forward of the title level (K1 + K2 + K3): embedding gather -> dropout -> Q|K|V projection ->
 // per-head attention -> dropout, one WAVE per title, the title's [32 x 320] input rows held in registers as
@@ -1899,6 +2148,25 @@ int nr_launch_attn_mfma(bool bwd, int dtype, const void* qkv, const float* mask,
   if (!bwd && fast && L <= 32 && seq_list != nullptr) { a.seq_list = seq_list; a.seq_count = seq_count; }   // forward: needed sequences only
   if (fast) return b16::launch(bwd, a, stream);
   return dtype == NR_BF16 ? launch_t<bf16_t>(bwd, a, stream) : launch_t<float>(bwd, a, stream);
+}
+
+
+// 64 < L <= 128, bf16 fast route (d_head % 4 == 0, <= 32, 8-byte aligned tensors).  Returns -1 when the call is not
+// eligible: the caller then runs the LDS/VALU kernels.
+int nr_launch_attn_long_mfma(bool bwd, int dtype, const void* qkv, const float* mask, void* y, const void* dy, void* dqkv, int n,
+                             int L, int heads, int d_head, const DropCfg& drop, hipStream_t stream) {
+  if (!(dtype == NR_BF16 && L > 64 && L <= 128 && d_head >= 4 && d_head <= 32 && d_head % 4 == 0)) return -1;
+  if ((((uintptr_t)qkv | (uintptr_t)y | (uintptr_t)dy | (uintptr_t)dqkv) & 7) != 0) return -1;
+  AttnMArgs a;
+  a.tmask = nullptr; a.bias = nullptr; a.seq_list = nullptr; a.seq_count = nullptr; a.ids = nullptr; a.needed = nullptr;
+  a.pos = nullptr; a.dump = nullptr; a.db = nullptr; a.nzf = nullptr;
+  a.qkv = qkv; a.mask = mask; a.y = y; a.dy = dy; a.dqkv = dqkv;
+  a.n = n; a.L = L; a.heads = heads; a.d = d_head; a.N = heads * d_head;
+  a.scale = 1.0f / sqrtf((float)d_head);
+  a.drop = drop;
+  a.vec = 1;
+  NrProfScope ps(stream, "attn_long_%s[bf16,n=%d,L=%d,h=%d,d=%d]", bwd ? "bwd" : "fwd", n, L, heads, d_head);
+  return b16::launch_long(bwd, a, stream);
 }
 
 

@@ -50,14 +50,16 @@ __device__ __forceinline__ float wave_row_dot(const T* __restrict__ row, const f
 
 constexpr int POOL_RED_FLOATS = 256 * 8;   // LDS reduction scratch: [row groups][columns] <= 256 chunks of <= 8
 
-template <typename T>
+// TPL: tokens per lane of the one-wave softmax (1: L <= 64; 2: 64 < L <= 128, lane owns tokens lane and lane + 64, its two
+// values combined first and the wave reduction after, a fixed order)
+template <typename T, int TPL = 1>
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ e,
                                                        const float* __restrict__ w2, const float* __restrict__ b2,
                                                        const float* __restrict__ mask, float* __restrict__ alpha,
                                                        float* __restrict__ out, int ld_out, int L, int N, int q,
                                                        const int32_t* __restrict__ needed) {
   constexpr int CH = ChunkOf<T>::CH;
-  __shared__ float sS[64];
+  __shared__ float sS[64 * TPL];
   __shared__ float sRed[POOL_RED_FLOATS];
   const int seq = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const size_t row0 = (size_t)seq * L;
@@ -72,15 +74,44 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const T* __restrict__ x, 
   }
   __syncthreads();
   if (wid == 0) {
-    const float s = lane < L ? sS[lane] : -INFINITY;
-    const float m = wave_max(s);
-    float ex = 0.f;
-    if (lane < L) ex = __expf(s - m) * (mask ? mask[row0 + lane] : 1.f);
-    const float sum = wave_sum(ex);
-    const float a = ex / (sum + 1e-8f * __expf(-m));
-    if (lane < L) {
-      sS[lane] = a;
-      alpha[row0 + lane] = a;
+    if constexpr (TPL == 1) {                              // (kept as it was: the L <= 64 launch compiles to the code it always had)
+      const float s = lane < L ? sS[lane] : -INFINITY;
+      const float m = wave_max(s);
+      float ex = 0.f;
+      if (lane < L) ex = __expf(s - m) * (mask ? mask[row0 + lane] : 1.f);
+      const float sum = wave_sum(ex);
+      const float a = ex / (sum + 1e-8f * __expf(-m));
+      if (lane < L) {
+        sS[lane] = a;
+        alpha[row0 + lane] = a;
+      }
+    } else {
+      float sv[TPL], ex[TPL];
+#pragma unroll
+      for (int u = 0; u < TPL; ++u) sv[u] = lane + 64 * u < L ? sS[lane + 64 * u] : -INFINITY;
+      float sm = sv[0];
+#pragma unroll
+      for (int u = 1; u < TPL; ++u) sm = fmaxf(sm, sv[u]);
+      const float m = wave_max(sm);
+#pragma unroll
+      for (int u = 0; u < TPL; ++u) {
+        const int l = lane + 64 * u;
+        ex[u] = l < L ? __expf(sv[u] - m) * (mask ? mask[row0 + l] : 1.f) : 0.f;
+      }
+      float es = ex[0];
+#pragma unroll
+      for (int u = 1; u < TPL; ++u) es += ex[u];
+      const float sum = wave_sum(es);
+      const float den = sum + 1e-8f * __expf(-m);
+#pragma unroll
+      for (int u = 0; u < TPL; ++u) {
+        const int l = lane + 64 * u;
+        if (l < L) {
+          const float a = ex[u] / den;
+          sS[l] = a;
+          alpha[row0 + l] = a;
+        }
+      }
     }
   }
   __syncthreads();
@@ -128,15 +159,15 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const T* __restrict__ x, 
 // ------------------------------------------------------------------------------------------
 constexpr int POOL_SPB = 8;
 
-template <typename T>
+template <typename T, int TPL = 1>   // TPL: as in pool_fwd_kernel
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ e,
                                                        const float* __restrict__ w2, const float* __restrict__ alpha,
                                                        const float* __restrict__ g, int ld_g, T* __restrict__ dpre,
                                                        float* __restrict__ partial, int n, int L, int N, int q, int spb,
                                                        const int32_t* __restrict__ seq_nz) {
   constexpr int CH = ChunkOf<T>::CH;
-  __shared__ float sDA[64];
-  __shared__ float sDS[64];
+  __shared__ float sDA[64 * TPL];
+  __shared__ float sDS[64 * TPL];
   __shared__ float sRed[POOL_RED_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qc = q / CH;                       // chunks per e row (<= 256: q <= 1024)
@@ -168,10 +199,27 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, 
     }
     __syncthreads();
     if (wid == 0) {
-      const float a = lane < L ? alpha[row0 + lane] : 0.f;
-      const float dA = lane < L ? sDA[lane] : 0.f;
-      const float rd = wave_sum(a * dA);
-      if (lane < L) sDS[lane] = a * (dA - rd);
+      if constexpr (TPL == 1) {
+        const float a = lane < L ? alpha[row0 + lane] : 0.f;
+        const float dA = lane < L ? sDA[lane] : 0.f;
+        const float rd = wave_sum(a * dA);
+        if (lane < L) sDS[lane] = a * (dA - rd);
+      } else {
+        float av[TPL], dv[TPL];
+#pragma unroll
+        for (int u = 0; u < TPL; ++u) {
+          const int l = lane + 64 * u;
+          av[u] = l < L ? alpha[row0 + l] : 0.f;
+          dv[u] = l < L ? sDA[l] : 0.f;
+        }
+        float t = av[0] * dv[0];
+#pragma unroll
+        for (int u = 1; u < TPL; ++u) t = fmaf(av[u], dv[u], t);
+        const float rd = wave_sum(t);
+#pragma unroll
+        for (int u = 0; u < TPL; ++u)
+          if (lane + 64 * u < L) sDS[lane + 64 * u] = av[u] * (dv[u] - rd);
+      }
     }
     __syncthreads();
     float wacc[CH];
@@ -599,10 +647,15 @@ inline int grid_for(size_t total, int block = 256, int cap = 256 * 16) {
 // ---- launchers used by nr_api.hip ---------------------------------------------------------
 int nr_launch_pool_core_fwd(int dtype, const void* x, const void* e, const float* w2, const float* b2, const float* mask,
                             float* alpha, float* out, int ld_out, int n, int L, int N, int q, hipStream_t s, const int32_t* needed) {
-  NR_CHECK_ARG(L >= 1 && L <= 64, "additive_pool: L=%d must be in [1, 64]", L);
+  NR_CHECK_ARG(L >= 1 && L <= 128, "additive_pool: L=%d must be in [1, 128]", L);
   NR_CHECK_ARG((((uintptr_t)x | (uintptr_t)e) & 15) == 0 && q <= 1024, "additive_pool: x / e must be 16-byte aligned, q <= 1024");
   NrProfScope ps(s, "pool_core_fwd[n=%d,L=%d,N=%d,q=%d]", n, L, N, q);
-  if (dtype == NR_BF16)
+  if (L > 64) {   // two tokens per lane
+    if (dtype == NR_BF16)
+      hipLaunchKernelGGL((pool_fwd_kernel<bf16_t, 2>), dim3(n), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)e, w2, b2, mask, alpha, out, ld_out, L, N, q, needed);
+    else
+      hipLaunchKernelGGL((pool_fwd_kernel<float, 2>), dim3(n), dim3(256), 0, s, (const float*)x, (const float*)e, w2, b2, mask, alpha, out, ld_out, L, N, q, needed);
+  } else if (dtype == NR_BF16)
     hipLaunchKernelGGL(pool_fwd_kernel<bf16_t>, dim3(n), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)e, w2, b2, mask, alpha, out, ld_out, L, N, q, needed);
   else
     hipLaunchKernelGGL(pool_fwd_kernel<float>, dim3(n), dim3(256), 0, s, (const float*)x, (const float*)e, w2, b2, mask, alpha, out, ld_out, L, N, q, needed);
@@ -618,13 +671,18 @@ int nr_pool_partial_rows(int n) { const int spb = pool_spb(n); return (n + spb -
 int nr_launch_pool_core_bwd(int dtype, const void* x, const void* e, const float* w2, const float* alpha, const float* g,
                             int ld_g, void* dpre, float* partial, float* dw2, float* db2, int n, int L, int N, int q,
                             hipStream_t s, const int32_t* seq_nz) {
-  NR_CHECK_ARG(L >= 1 && L <= 64, "additive_pool: L=%d must be in [1, 64]", L);
+  NR_CHECK_ARG(L >= 1 && L <= 128, "additive_pool: L=%d must be in [1, 128]", L);
   NR_CHECK_ARG(q <= 1024, "additive_pool: q=%d must be <= 1024", q);
   NR_CHECK_ARG((((uintptr_t)x | (uintptr_t)e | (uintptr_t)dpre | (uintptr_t)g) & 15) == 0 && ld_g % 4 == 0,
                "additive_pool_bwd: x / e / dpre / g must be 16-byte aligned");
   const int nb = nr_pool_partial_rows(n);
   NrProfScope ps(s, "pool_core_bwd[n=%d,L=%d,N=%d,q=%d]", n, L, N, q);
-  if (dtype == NR_BF16)
+  if (L > 64) {   // two tokens per lane
+    if (dtype == NR_BF16)
+      hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, 2>), dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)e, w2, alpha, g, ld_g, (bf16_t*)dpre, partial, n, L, N, q, pool_spb(n), seq_nz);
+    else
+      hipLaunchKernelGGL((pool_bwd_kernel<float, 2>), dim3(nb), dim3(256), 0, s, (const float*)x, (const float*)e, w2, alpha, g, ld_g, (float*)dpre, partial, n, L, N, q, pool_spb(n), seq_nz);
+  } else if (dtype == NR_BF16)
     hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)e, w2, alpha, g, ld_g, (bf16_t*)dpre, partial, n, L, N, q, pool_spb(n), seq_nz);
   else
     hipLaunchKernelGGL(pool_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float*)x, (const float*)e, w2, alpha, g, ld_g, (float*)dpre, partial, n, L, N, q, pool_spb(n), seq_nz);

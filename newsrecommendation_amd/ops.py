@@ -588,6 +588,36 @@ class SDPAFunction(Function):
         return dqkv, None, None, None, None, None, None
 
 
+class LongSDPAFunction(Function):
+    """SDPAFunction for long clicked histories, 64 < L <= 128 (nr_sdpa_long_fwd / nr_sdpa_long_bwd): bf16 with aligned
+    buffers runs on the matrix cores (RB x RB tiles of 32 x 32), everything else on the LDS/VALU kernels."""
+
+    @staticmethod
+    def forward(ctx, qkv, mask, n, L, heads, d_head, code):
+        _need_gpu(qkv, mask)
+        N = heads * d_head
+        mask_c = mask.contiguous().float() if mask is not None else None
+        y = torch.empty(n * L, N, dtype=torch_dtype(code), device=qkv.device)
+        check(_lib.lib().nr_sdpa_long_fwd(ptr(qkv), ptr(mask_c), ptr(y), n, L, heads, d_head, code, 0.0, 0, _stream()),
+              "nr_sdpa_long_fwd")
+        ctx.dims = (n, L, heads, d_head, code)
+        ctx.save_for_backward(qkv, mask_c)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        _enter_backward()
+        qkv, mask_c = ctx.saved_tensors
+        n, L, heads, d_head, code = ctx.dims
+        dy = dy.contiguous()
+        if dy.dtype != torch_dtype(code):
+            dy = dy.to(torch_dtype(code))
+        dqkv = torch.empty_like(qkv)
+        check(_lib.lib().nr_sdpa_long_bwd(ptr(qkv), ptr(mask_c), ptr(dy), ptr(dqkv), n, L, heads, d_head, code, 0.0, 0, _stream()),
+              "nr_sdpa_long_bwd")
+        return dqkv, None, None, None, None, None, None
+
+
 def sdpa(Q, K, V, code: int, mask=None):
     """Q, K, V: [n, h, L, d] (any strides, e.g. the transposed views of src/model/model_utils.py:89-91); mask: [n, L], or the
     reference's per-head expansion [n, h, L] of it (:86-87) -> [n, h, L, d].  The three tensors are packed into the
@@ -604,7 +634,7 @@ def sdpa(Q, K, V, code: int, mask=None):
     td = torch_dtype(code)
     # [n, h, L, d] x 3 -> [n, L, 3, h, d] -> [n*L, 3*h*d]
     qkv = torch.stack([t.to(td).permute(0, 2, 1, 3) for t in (Q, K, V)], dim=2).reshape(n * L, 3 * h * d)
-    y = SDPAFunction.apply(qkv, mask, n, L, h, d, code)
+    y = (LongSDPAFunction if L > 64 else SDPAFunction).apply(qkv, mask, n, L, h, d, code)
     return y.view(n, L, h, d).permute(0, 2, 1, 3)
 
 
