@@ -605,6 +605,56 @@ size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d);
 int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K11  diversified recommendation: Maximal Marginal Relevance (Carbonell & Goldstein 1998) over a pool of the M best.  The
+ * reference has nothing of the kind (it scores the candidate lists of behaviors.tsv only), so, as with K9 / K10, the contract
+ * is this library's own; metrics.mmr_reference states it on the host.  One launch, no workspace, one workgroup per user.
+ *   news_vecs    [V, N] fp32, row stride ld_news; N a multiple of 4, at most NR_TOPK_MAX_N; alignment as in nr_topk_desc
+ *   pool_ids     [U, M] int32, row stride ld_pool_ids;  pool_scores [U, M] fp32, row stride ld_pool_scores: what
+ *                nr_score_topk wrote for k = M, but any arrays are allowed
+ *   M            in [1, NR_TOPK_MAX_K];  k in [1, M]
+ *   penalty      scalar fp32, finite and >= 0;  penalty_u optional [U] fp32: when given it replaces the scalar, user by user
+ *   group        optional [V] int32 with group_cap = c in [1, 128], together as in nr_topk_desc; a negative id = in no group
+ *   out_ids      [U, k] int32;  out_scores [U, k] fp32;  out_place [U, k] int32, all contiguous
+ * Place i of user u's pool is LIVE when pool_ids[u, i] is in [1, V) and pool_scores[u, i] is not NaN.  A place that is not live
+ * is never taken and its id is never used as an index (nr_score_topk's fill, id 0 / -inf, is not live); a repeated id is
+ * simply two places.  With x_i the news vector of place i, r_i its pool score and p_u the user's penalty, all in fp32:
+ *   g(i, j)    = <x_i, x_j> over N: ONE fmaf chain in a fixed order; its bits depend on the two vectors and on N only, not on
+ *                M, the place, the tile variant, U or the user's position in the grid; g(i, j) == g(j, i) bit for bit
+ *   rn_i       = g(i, i) > 0 ? 1 / sqrt(g(i, i)) : 0, square root and division both correctly rounded: an all-zero vector
+ *                has similarity 0 to everything and makes no NaN
+ *   s(i | j)   = fl(fl(g(i, j) * rn_i) * rn_j): the cosine, as seen from candidate i
+ * The walk: S = {} and k times: the candidates are the live places not yet taken (with caps: whose group is negative or has
+ * fewer than c places taken so far); value_i = r_i while S is empty, afterwards fmaf(-p_u, maxsim_i, r_i) with
+ * maxsim_i = max over j in S of s(i | j); the candidate with the largest value is taken, ties to the LOWEST place (for a pool
+ * that nr_score_topk sorted: score descending, then id ascending); no candidate ends the walk.
+ *   out_ids    the ids taken, in the order taken;  out_scores their r_i (the relevance, not the MMR value);  out_place their
+ *              places in the pool, 0-based;  the tail of a short row is id 0, score -inf, place -1
+ * Consequences: with p_u = 0 the row is the pool walked in (score descending, place ascending) order under the cap -- for a
+ * sorted pool without caps its first k places, bit for bit.  A row depends only on that user's pool row, its p_u and the
+ * vectors that row names.
+ * Unspecified: non-finite vector components, or a NaN or negative entry of penalty_u, give an unspecified row for that user
+ * only, never an access outside the arrays (the library cannot check device arrays and does not synchronise).
+ * Refused before any launch (nr_last_error; host arithmetic only): a null descriptor or required pointer; M or k out of range;
+ * N, ld_news or the alignment of news_vecs against K9's rules; a pool row stride below M; a scalar penalty that is negative or
+ * not finite; group without a cap in [1, 128] or a cap without group; U < 0; V < 1.  U == 0 returns 0 without a launch.   */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const int32_t* pool_ids;
+  const float* pool_scores;
+  int ld_pool_ids, ld_pool_scores;
+  int U, N, M, k;
+  float penalty;
+  const float* penalty_u; /* optional [U]: replaces `penalty` user by user */
+  const int32_t* group;   /* optional [V]: group id per news, negative = no group; with group_cap */
+  int group_cap;          /* 1 .. NR_TOPK_MAX_K with group, 0 without */
+  int32_t* out_ids;
+  float* out_scores;
+  int32_t* out_place;
+} nr_mmr_desc;
+int nr_mmr_select(const nr_mmr_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +
  * the DataLoader collate, src/dataset.py:44-49, src/main.py:89-103.  Only news INDICES come from the host (once per
  * epoch); the feature rows are gathered here.

@@ -90,6 +90,13 @@ class RankDesc(C.Structure):
                 ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
 
 
+class MmrDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("pool_ids", C.c_void_p), ("pool_scores", C.c_void_p),
+                ("ld_pool_ids", C.c_int), ("ld_pool_scores", C.c_int), ("U", C.c_int), ("N", C.c_int), ("M", C.c_int), ("k", C.c_int),
+                ("penalty", C.c_float), ("penalty_u", C.c_void_p), ("group", C.c_void_p), ("group_cap", C.c_int),
+                ("out_ids", C.c_void_p), ("out_scores", C.c_void_p), ("out_place", C.c_void_p)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -163,6 +170,7 @@ SIGNATURES = {
     "nr_score_topk": [C.POINTER(TopkDesc), _vp],
     "nr_score_rank_workspace_bytes": [C.POINTER(RankDesc)],
     "nr_score_rank": [C.POINTER(RankDesc), _vp],
+    "nr_mmr_select": [C.POINTER(MmrDesc), _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -210,7 +218,7 @@ def lib():
                     fn = getattr(L, name)          # AttributeError if the .so lacks a declared symbol
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
-                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc)
+                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

@@ -483,6 +483,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 7) out[6] = sizeof(nr_adam_rows_desc);
   if (n >= 8) out[7] = sizeof(nr_topk_desc);
   if (n >= 9) out[8] = sizeof(nr_rank_desc);
+  if (n >= 10) out[9] = sizeof(nr_mmr_desc);
   return NR_OK;
 }
 

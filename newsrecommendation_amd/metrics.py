@@ -172,6 +172,73 @@ def rank_reference(a, b=None, *, targets, exclude=None, prior=None, stamp=None, 
     return ranks, out
 
 
+def mmr_reference(news, pool_ids, pool_scores, *, k, penalty, group=None, group_cap=None):
+    """Host statement of the diversified re-ranking contract (include/nrhip.h, nr_mmr_select); tests check the device against
+    it, no product path calls it.  Float64 arithmetic on the given inputs (fp32 arrays are taken as they are).
+
+    news [V, N]; pool_ids [U, M] and pool_scores [U, M]: every user's pool; place i is live when its id is in [1, V) and its score
+    is not NaN.  g(i, j) = <x_i, x_j>, rn_i = 1 / sqrt(g(i, i)) where g(i, i) > 0, else 0, s(i | j) = g(i, j) rn_i rn_j.  The walk
+    takes k times the live place not yet taken with the largest value, ties to the LOWEST place: value_i = r_i for the first
+    step, r_i - p_u max_{j taken} s(i | j) afterwards; penalty is a scalar or [U].  Group caps: group [V] integer ids (negative =
+    in no group) with group_cap = c, together: a place whose group already has c places in the row is no candidate.  The walk
+    ends when there is no candidate; the tail of the row is id 0, score -inf, place -1.
+    Returns (ids int32 [U, k], scores float64 [U, k] -- the pool scores of the places taken --, places int32 [U, k], margins
+    float64 [U, k]): margins[u, t] = value of the place taken at step t minus the best value among the other candidates of
+    that step (0 for a tie, +inf without another candidate or after the walk ended) -- a row whose margins all exceed the
+    error of a fp32 value cannot come out differently on the device."""
+    if (group is None) != (group_cap is None):
+        raise ValueError("group and group_cap come together")
+    if group is not None and not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
+    news = np.asarray(news, dtype=np.float64)
+    pid = np.asarray(pool_ids, dtype=np.int64)
+    r = np.asarray(pool_scores, dtype=np.float64)
+    V = news.shape[0]
+    U, M = pid.shape
+    if r.shape != (U, M) or not 1 <= k <= M:
+        raise ValueError(f"pool_ids {pid.shape}, pool_scores {r.shape}, k = {k}: shapes must agree and k lie in [1, M]")
+    p = np.broadcast_to(np.asarray(penalty, dtype=np.float64), (U,)) if np.ndim(penalty) else np.full(U, float(penalty))
+    live = (pid >= 1) & (pid < V) & ~np.isnan(r)
+    safe = np.where(live, pid, 0)
+    grp = np.full((U, M), -1, dtype=np.int64) if group is None else np.where(live, np.asarray(group, dtype=np.int64).reshape(V)[safe], -1)
+    cap = 0 if group is None else int(group_cap)
+    ids = np.zeros((U, k), dtype=np.int32)
+    out = np.full((U, k), -np.inf, dtype=np.float64)
+    places = np.full((U, k), -1, dtype=np.int32)
+    margins = np.full((U, k), np.inf, dtype=np.float64)
+    for u0 in range(0, U, 16):                                   # the Gram matrices of 16 users at a time
+        sl = slice(u0, min(u0 + 16, U))
+        n = sl.stop - sl.start
+        rows = np.arange(n)
+        x = news[safe[sl]] * live[sl, :, None]
+        gram = x @ x.transpose(0, 2, 1)
+        diag = np.einsum("uii->ui", gram)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rn = np.where(diag > 0, 1.0 / np.sqrt(diag), 0.0)
+        taken = np.zeros((n, M), dtype=bool)
+        count = np.zeros((n, M), dtype=np.int64)
+        maxsim = np.full((n, M), -np.inf)
+        for t in range(k):
+            cand = live[sl] & ~taken & ((grp[sl] < 0) | (count < cap))
+            with np.errstate(invalid="ignore"):
+                val = r[sl] if t == 0 else r[sl] - p[sl, None] * maxsim
+            has = cand.any(axis=1)
+            best = np.where(cand, val, -np.inf).max(axis=1)
+            j = (cand & (val == best[:, None])).argmax(axis=1)   # the first place that reaches the maximum
+            others = cand.copy()
+            others[rows, j] = False
+            second = np.where(others, val, -np.inf).max(axis=1)
+            with np.errstate(invalid="ignore"):
+                gap = np.where(others.any(axis=1), np.where(best == second, 0.0, best - second), np.inf)
+            hu, hj = rows[has], j[has]
+            ids[u0 + hu, t], out[u0 + hu, t], places[u0 + hu, t], margins[u0 + hu, t] = pid[u0 + hu, hj], r[u0 + hu, hj], hj, gap[has]
+            taken[hu, hj] = True
+            gj = grp[u0 + hu, hj]
+            count[hu] += (grp[u0 + hu] == gj[:, None]) & (gj[:, None] >= 0)
+            maxsim[hu] = np.maximum(maxsim[hu], gram[hu, hj, :] * rn[hu] * rn[hu, hj][:, None])
+    return ids, out, places, margins
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

@@ -1227,6 +1227,58 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
 
 
 @torch.no_grad()
+def mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, group=None, group_cap=None):
+    """Diversified re-ranking of a pool (nr_mmr_select; include/nrhip.h, K11): Maximal Marginal Relevance over the M places of
+    every user's pool -- `pool_ids` int32 [U, M] and `pool_scores` fp32 [U, M], M <= 128, what score_topk(k=M) returns, but any
+    arrays are allowed.  The row is built greedily: the first entry is the best pool score, every later one the live place not
+    yet taken with the largest fmaf(-penalty, max cosine to what is already in the row, pool score); ties go to the lowest
+    place.  The cosines come from `news_vecs` in exact fp32 (one Gram matrix per user on the matrix cores, never in HBM).
+    `penalty`: a float (finite, >= 0) or a fp32 tensor [U], one penalty per user; 0 gives the pool's own order.
+    `group` [V] int32 with `group_cap` = c in [1, 128], together: at most c places of one group in a row (negative = in no
+    group), applied inside the walk.  A place whose id is outside [1, V) or whose score is NaN (score_topk's fill) is never taken.
+    Returns (ids int32 [U, k], scores fp32 [U, k] -- the pool scores of the places taken, not the MMR values -- and place int32
+    [U, k], the 0-based places in the pool); a row with fewer than k places to take ends in id 0, score -inf, place -1."""
+    pen_t = penalty if isinstance(penalty, torch.Tensor) else None
+    _need_gpu(news_vecs, pool_ids, pool_scores, pen_t, group)
+    if news_vecs.dim() != 2 or news_vecs.dtype != torch.float32 or news_vecs.stride(1) != 1 or (news_vecs.shape[0] > 1 and news_vecs.stride(0) < news_vecs.shape[1]):
+        raise RuntimeError(f"mmr_select: news_vecs must be a 2-D fp32 tensor with contiguous rows, got {tuple(news_vecs.shape)} {news_vecs.dtype} "
+                           f"strides {tuple(news_vecs.stride())}")
+    V, N = news_vecs.shape
+    dev = news_vecs.device
+    for name, t, dt in (("pool_ids", pool_ids, torch.int32), ("pool_scores", pool_scores, torch.float32)):
+        if t.dim() != 2 or t.dtype != dt or t.device != dev or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"mmr_select: {name} must be a 2-D {dt} tensor with contiguous rows on {dev}, got {tuple(t.shape)} {t.dtype} "
+                               f"strides {tuple(t.stride())} on {t.device}")
+    U, M = pool_ids.shape
+    if tuple(pool_scores.shape) != (U, M):
+        raise RuntimeError(f"mmr_select: pool_ids is {tuple(pool_ids.shape)}, pool_scores {tuple(pool_scores.shape)}")
+    pen = None
+    if pen_t is not None:
+        if tuple(pen_t.shape) != (U,) or not pen_t.is_floating_point() or pen_t.device != dev:
+            raise RuntimeError(f"mmr_select: a penalty tensor must be floating point of shape ({U},) on {dev}, got {tuple(pen_t.shape)} "
+                               f"{pen_t.dtype} on {pen_t.device}")
+        pen = pen_t.detach().to(torch.float32).contiguous()
+    gr = None
+    if group is not None:
+        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
+            raise RuntimeError(f"mmr_select: group must be an int32 tensor of shape ({V},) on {dev}, got "
+                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
+        gr = group.detach().contiguous()
+    ids = torch.empty(U, int(k), dtype=torch.int32, device=dev)
+    scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
+    place = torch.empty(U, int(k), dtype=torch.int32, device=dev)
+    if U == 0:
+        return ids, scores, place
+    d = _lib.MmrDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, pool_ids=ptr(pool_ids),
+                     pool_scores=ptr(pool_scores), ld_pool_ids=pool_ids.stride(0) if U > 1 else M,
+                     ld_pool_scores=pool_scores.stride(0) if U > 1 else M, U=U, N=N, M=M, k=int(k),
+                     penalty=0.0 if pen is not None else float(penalty), penalty_u=ptr(pen), group=ptr(gr),
+                     group_cap=0 if group_cap is None else int(group_cap), out_ids=ptr(ids), out_scores=ptr(scores), out_place=ptr(place))
+    check(_lib.lib().nr_mmr_select(C.byref(d), _stream()), "nr_mmr_select")
+    return ids, scores, place
+
+
+@torch.no_grad()
 def score_rank(news_vecs, user_vecs, targets, exclude=None, ks=(), splits=0, prior=None, stamp=None, window=None):
     """Full-corpus rank evaluation (nr_score_rank): for every user and each of its targets ([U, T <= 64] news ids, 0 = no entry)
     the exact 1-based position of that news among the user's eligible news of the whole table, in score_topk's order and with

@@ -370,6 +370,14 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     in no group -- with group_cap = c: a row holds at most c news of one group and is otherwise the same walk down the order,
     so it still has k entries wherever k can be taken.  The cap is applied inside the selection, not to a finished row.
     rank_eval_capped takes the same two arguments and ranks the held-out clicks in this capped ranking."""
+    news_vecs, user, exclude, kw, caps = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                         news_group, group_cap, seen)
+    return ops.score_topk(news_vecs, user, k, exclude=exclude, **kw, **caps)
+
+
+def _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window, news_group, group_cap, seen):
+    """What recommend and recommend_diverse share: the fp32 table, the user vectors, the exclusions, the pool keywords and the
+    cap keywords (group / group_cap; what is None is left out) of ops.score_topk."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
@@ -377,11 +385,31 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     user = _user_vectors(model, news_vecs, hist, m, batch_size, device, _Histories(mask))
     exclude = _exclusions(hist, m, exclude_history, seen, device)
     kw = _pool_kwargs(device, prior, news_time, window)
+    caps = {}
     if news_group is not None:
-        kw["group"] = torch.as_tensor(news_group).to(device=device, dtype=torch.int32)
+        caps["group"] = torch.as_tensor(news_group).to(device=device, dtype=torch.int32)
     if group_cap is not None:
-        kw["group_cap"] = group_cap
-    return ops.score_topk(news_vecs, user, k, exclude=exclude, **kw)
+        caps["group_cap"] = group_cap
+    return news_vecs, user, exclude, kw, caps
+
+
+@torch.no_grad()
+def recommend_diverse(model, news_vecs, hist_idx, mask, k, penalty, pool=128, exclude_history=True, batch_size=8192, prior=None, news_time=None,
+                      window=None, news_group=None, group_cap=None, seen=None):
+    """Diversified full-corpus recommendation: Maximal Marginal Relevance over the `pool` best news of every user.  The user
+    vectors, exclusions, prior and window are recommend's; the pool is drawn with ops.score_topk(k=pool) WITHOUT the caps (the
+    best c per group would take away the choice MMR is there to make) and re-ranked by ops.mmr_select (include/nrhip.h, K11)
+    WITH them: each step takes the news with the largest score - penalty * (largest cosine to the news already in the row).
+    penalty: a float >= 0 or a [U] tensor (penalty 0 is recommend's row, bit for bit, for k <= pool <= 128); to scale it by a
+    user's own score spread see INTEGRATION.md.  Returns (ids int32 [U, k], scores fp32 [U, k]): the scores are the relevance
+    scores of the news taken, so a row is no longer sorted by them; a row with fewer than k news to take ends in id 0, -inf."""
+    news_vecs, user, exclude, kw, caps = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                         news_group, group_cap, seen)
+    pool_ids, pool_scores = ops.score_topk(news_vecs, user, pool, exclude=exclude, **kw)
+    if isinstance(penalty, torch.Tensor):
+        penalty = penalty.to(device=news_vecs.device, dtype=torch.float32)
+    ids, scores, _ = ops.mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, **caps)
+    return ids, scores
 
 
 def _retrieval_sums(ranks, ks):
