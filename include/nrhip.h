@@ -655,6 +655,52 @@ typedef struct {
 int nr_mmr_select(const nr_mmr_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K12  sampled recommendation: k news WITHOUT replacement, each draw proportional to exp(score / tau_u) over what is left --
+ * the Plackett-Luce model -- by the Gumbel-max trick: tau_u * g is added to every score, g an independent standard Gumbel
+ * variate per (user, news), and the k largest are taken.  That is nr_score_topk with a per-(user, news) prior made in
+ * registers: no [U, V] noise matrix exists.  The reference has nothing of the kind; metrics.sample_reference states the
+ * contract on the host.  Every field of `topk` means what it means in K9 (pools, caps, dense and CSR lists, splits, ws).
+ * The noise, for user key a (uint32), news id v, seed (uint64) and draw (uint32):
+ *   bits(a, v) = Philox4x32-10(counter = (v >> 2, a, draw, 0), key = (seed & 0xffffffff, seed >> 32))[v & 3]
+ *                (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85)
+ *   u          = ((bits >> 8) + 0.5) * 2^-24, in [2^-25, 1 - 2^-25]
+ *   g          = -log(-log(u)) in fp32, finite: -2.853 < g < 17.329; within 7 * 2^-23 * max(1, |g|) of the real value
+ * The counter holds the GLOBAL user key and news id, so a draw does not depend on the user tile, the place in it, the corpus
+ * slice, `splits`, or which batch or rank the user was put in.  user_keys names the users ([U] int32, taken as uint32; NULL =
+ * the row index u): a caller who shards users over ranks or batches passes the same key for the same user and gets the same
+ * draw.  `draw` gives independent rows under one seed.
+ * The key:  P(u, v) = fl32(prior[v] + fl32(tau_u * g))  (prior[v] = 0 without a prior; a multiply and an add, never one fma),
+ * and the final score of (u, v) is fl32(dot + P(u, v)) under the pool rules of K9.  Consequences:
+ *   - a prior of -inf still switches a news off; a NaN still falls under the NaN rule;
+ *   - tau_u == 0 gives the row of nr_score_topk, bit for bit;
+ *   - ROW u OF A SAMPLED CALL IS ROW 0 OF nr_score_topk given user u alone with prior = P(u, .) and everything else equal:
+ *     identical ids, identical score bits;
+ *   - with caps the law is still the right one: walking down the perturbed order and skipping a saturated group is sequential
+ *     sampling from the softmax renormalised over what may still be taken;
+ *   - an entry of tau_u that is negative, NaN or infinite gives that user an all-fill row (id 0, -inf), nobody else's changes.
+ *   out_scores   topk.out_scores receive the PERTURBED values the row is ordered by
+ *   out_model    optional [U, k] fp32: fl32(perturbed - fl32(tau_u * g)), the model score + prior to within rounding; -inf in fill
+ *   tau          scalar, used when tau_u == NULL; finite and >= 0, else refused
+ * Workspace: nr_score_topk's, U * splits * k * 8 bytes (0 = bad descriptor, see nr_last_error).  The two launches of
+ * nr_score_topk (the SAMPLE instantiations of the selection, the merge kernels as they are), plus a tiny finalize when
+ * out_model is given.  Refused before any launch: whatever nr_score_topk refuses, and a scalar tau as above.
+ * nr_sample_noise is the probe: g and bits of n (user key, news id) pairs, element-wise, DEVICE arrays; either output may be
+ * NULL.  It runs the function the selection runs.                                                                       */
+typedef struct {
+  nr_topk_desc topk;        /* every field as in K9; out_scores receive the PERTURBED values the row is ordered by */
+  uint64_t seed;
+  uint32_t draw;            /* independent draws under one seed */
+  float tau;                /* used when tau_u == NULL; finite, >= 0 */
+  const float* tau_u;       /* optional [U] */
+  const int32_t* user_keys; /* optional [U]: counter word 1; NULL = the row index u */
+  float* out_model;         /* optional [U, k]: fl32(perturbed - fl32(tau_u * g)), the model score + prior to within rounding; -inf in fill */
+} nr_sample_desc;
+size_t nr_score_sample_workspace_bytes(const nr_sample_desc* d);
+int nr_score_sample(const nr_sample_desc* d, nr_stream_t stream);
+int nr_sample_noise(uint64_t seed, uint32_t draw, const int32_t* user_keys, const int32_t* news_ids, int n, float* out_g, uint32_t* out_bits,
+                    nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +
  * the DataLoader collate, src/dataset.py:44-49, src/main.py:89-103.  Only news INDICES come from the host (once per
  * epoch); the feature rows are gathered here.

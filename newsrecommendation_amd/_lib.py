@@ -97,6 +97,11 @@ class MmrDesc(C.Structure):
                 ("out_ids", C.c_void_p), ("out_scores", C.c_void_p), ("out_place", C.c_void_p)]
 
 
+class SampleDesc(C.Structure):
+    _fields_ = [("topk", TopkDesc), ("seed", C.c_uint64), ("draw", C.c_uint32), ("tau", C.c_float), ("tau_u", C.c_void_p),
+                ("user_keys", C.c_void_p), ("out_model", C.c_void_p)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -113,7 +118,8 @@ _vp, _i, _f, _u32 = C.c_void_p, C.c_int, C.c_float, C.c_uint32
 # name -> argtypes ; every entry returns int unless listed in RESTYPES.  Must list exactly the symbols of include/nrhip.h.
 RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": C.c_size_t, "nr_mhsa_workspace_bytes": C.c_size_t, "nr_conv_workspace_bytes": C.c_size_t, "nr_conv_table_workspace_bytes": C.c_size_t, "nr_pool_workspace_bytes": C.c_size_t,
             "nr_linear_workspace_bytes": C.c_size_t, "nr_adam_rows_workspace_bytes": C.c_size_t,
-            "nr_score_topk_workspace_bytes": C.c_size_t, "nr_score_rank_workspace_bytes": C.c_size_t}
+            "nr_score_topk_workspace_bytes": C.c_size_t, "nr_score_rank_workspace_bytes": C.c_size_t,
+            "nr_score_sample_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
     "nr_last_error": [C.c_char_p, C.c_size_t],
@@ -171,6 +177,9 @@ SIGNATURES = {
     "nr_score_rank_workspace_bytes": [C.POINTER(RankDesc)],
     "nr_score_rank": [C.POINTER(RankDesc), _vp],
     "nr_mmr_select": [C.POINTER(MmrDesc), _vp],
+    "nr_score_sample_workspace_bytes": [C.POINTER(SampleDesc)],
+    "nr_score_sample": [C.POINTER(SampleDesc), _vp],
+    "nr_sample_noise": [C.c_uint64, _u32, _vp, _vp, _i, _vp, _vp, _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -218,7 +227,7 @@ def lib():
                     fn = getattr(L, name)          # AttributeError if the .so lacks a declared symbol
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
-                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc)
+                structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc, SampleDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

@@ -484,6 +484,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 8) out[7] = sizeof(nr_topk_desc);
   if (n >= 9) out[8] = sizeof(nr_rank_desc);
   if (n >= 10) out[9] = sizeof(nr_mmr_desc);
+  if (n >= 11) out[10] = sizeof(nr_sample_desc);
   return NR_OK;
 }
 

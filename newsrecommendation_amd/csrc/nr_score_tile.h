@@ -63,6 +63,76 @@ struct PoolArgs {
   bool any() const { return prior != nullptr || stamp != nullptr || window != nullptr; }
 };
 
+// Sampled rows (include/nrhip.h, K12): the Gumbel noise of one (user key a, news id v) pair under (seed, draw), ONE definition
+// for the selection (nr_score_sample), its finalize and the probe (nr_sample_noise).
+//   bits = Philox4x32-10(counter = (v >> 2, a, draw, 0), key = (seed & 0xffffffff, seed >> 32))[v & 3]
+//   u    = ((bits >> 8) + 0.5) * 2^-24, in [2^-25, 1 - 2^-25];   g = -log(-log(u))
+// The counter holds the GLOBAL user key and news id, never a tile-, slice- or batch-local index, so a draw does not depend on
+// where the pair falls.  Four consecutive news share one Philox block; every lane recomputes the block of its own pair.
+// With m = bits >> 8, u = (2 m + 1) 2^-25 is a fp32 number only below 1/2 (2 m + 1 < 2^24); from 1/2 on it is 1 - u =
+// (2^25 - 2 m - 1) 2^-25 that is one.  So -log(u) is logf of the exact u in the lower half and -log1pf of the exact -(1 - u) in
+// the upper half: no rounding before the first logarithm, and u can never round to 1 (g would be +inf).  g is finite:
+// -2.853 < g < 17.329.
+__host__ __device__ inline uint32_t sample_bits(uint32_t a, uint32_t v, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw) {
+  uint32_t c0 = v >> 2, c1 = a, c2 = draw, c3 = 0u, k0 = seed_lo, k1 = seed_hi;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;   // hi and lo word of each product from one multiply
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  const uint32_t w = v & 3u;
+  return w == 0u ? c0 : w == 1u ? c1 : w == 2u ? c2 : c3;
+}
+__host__ __device__ inline float sample_gumbel(uint32_t bits) {
+  const uint32_t m = bits >> 8;
+  const float t = m < (1u << 23) ? -logf((float)(2u * m + 1u) * 0x1p-25f) : -log1pf(-((float)((1u << 25) - 2u * m - 1u) * 0x1p-25f));
+  return -logf(t);
+}
+// No computed g reaches it (the largest, at bits >> 8 = 2^24 - 1, is 17.3287 to within a few ulp): the skip bound of sample_key.
+constexpr float SAMPLE_G_MAX = 17.5f;
+
+// fl32(tau * g) as a product of its own.  This unit is compiled with -ffp-contract=fast, under which __fmul_rn is a plain `*`
+// that the compiler fuses with the add or subtract that follows into one v_fmac_f32; the empty asm makes the product opaque,
+// at no instruction.  tests/test_gpu_sample.py sees a fused one as a 1-ulp score difference.
+__device__ __forceinline__ float sample_scaled(float tau, float g) {
+  float n = __fmul_rn(tau, g);
+  asm volatile("" : "+v"(n));
+  return n;
+}
+
+struct SampleArgs {
+  uint32_t seed_lo, seed_hi, draw;
+  float tau;                  // used when tau_u is null
+  const float* tau_u;         // [U] or null
+  const int32_t* user_keys;   // [U] or null: the row index
+  __device__ __forceinline__ float tau_of(long u) const { return tau_u != nullptr ? tau_u[u] : tau; }
+  __device__ __forceinline__ uint32_t key_of(long u) const { return user_keys != nullptr ? (uint32_t)user_keys[u] : (uint32_t)u; }
+  __device__ __forceinline__ float gumbel(uint32_t a, uint32_t v) const { return sample_gumbel(sample_bits(a, v, seed_lo, seed_hi, draw)); }
+};
+
+// The key of a sampled call: pool_key fed the perturbed prior P(u, v) = fl32(prior + fl32(tau * g)) -- a multiply and an add of
+// their own (sample_scaled, __fadd_rn: never one fma), the dot product chain untouched.  So a prior of -inf still switches a news
+// off and a NaN still falls under the NaN rule; tau == 0 gives the keys of the plain call (prior + 0); and row u of a sampled
+// call is row 0 of nr_score_topk for user u alone with prior = P(u, .), ids and score bits.  tau is finite and >= 0 here: the
+// caller turns a user whose tau is not into an empty window.
+// The skip: rounding is monotone and tau >= 0, so the key is at most kb, the key under g = SAMPLE_G_MAX.  A pair whose kb does
+// not beat `thr` -- any value the user's threshold had, thresholds only rise -- can never be kept, and gets kb in place of its
+// key without Philox or logarithms: no bit of any row changes.  pmax < inf keeps the bound honest where tau * SAMPLE_G_MAX
+// overflows: dot = -inf would make NaN (key 0) of a pair whose true key is -inf's.
+__device__ __forceinline__ uint32_t sample_key(float dot, float prior, int32_t stamp, int32_t lo, int32_t hi, float tau, const SampleArgs& sa,
+                                               uint32_t a, uint32_t v, uint32_t thr) {
+  const float pmax = __fadd_rn(prior, sample_scaled(tau, SAMPLE_G_MAX));
+  const uint32_t kb = pool_key(dot, pmax, stamp, lo, hi);
+  if (tau == 0.f || (kb <= thr && pmax < __builtin_inff())) return kb;
+  return pool_key(dot, __fadd_rn(prior, sample_scaled(tau, sa.gumbel(a, v))), stamp, lo, hi);
+}
+
 // Exclusion lists of any length in CSR form (include/nrhip.h, K9): user u's list is ids[offsets[u] .. offsets[u + 1]), strictly
 // ascending.  Read by the CSR instantiations only.  segment() clamps both bounds into [0, n] and keeps e >= b: whatever the
 // offsets hold, no index formed from them leaves ids[0 .. n).

@@ -126,9 +126,13 @@ struct GroupRegs<false> {};
 // them launches <MT, false, .>, the kernel as it was before pools existed.  GROUP: the call has group caps (the exchange
 // rule at the top of this file); a call without them launches <MT, ., false, .>, the kernel as it was before caps existed.
 // CSR: the call has exclusion lists in CSR form (a kernel argument of its own again, behind GroupArgs) and no dense list; a
-// call without them launches <MT, ., ., false>, the kernel as it was before the lists existed.
-template <int MT, bool POOL, bool GROUP, bool CSR>
-__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, GroupArgs ga, CsrArgs ca) {
+// call without them launches <MT, ., ., false, .>, the kernel as it was before the lists existed.
+// SAMPLE: the sampled call (nr_score_sample, include/nrhip.h K12; its arguments behind CsrArgs once more).  It implies POOL and
+// changes ONE thing: the keys come from sample_key (nr_score_tile.h), pool_key fed a prior perturbed by tau_u * Gumbel noise
+// made in registers.  Caps, lists, slices and the merge see keys as before.  Every other call launches <MT, ., ., ., false>.
+template <int MT, bool POOL, bool GROUP, bool CSR, bool SAMPLE>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, GroupArgs ga, CsrArgs ca, SampleArgs sa) {
+  static_assert(POOL || !SAMPLE, "the sampled keys are pool keys");
   constexpr int TU = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float tk_smem[];
   ScoreTile<MT> t(tk_smem, a.N);                         // scoring tile: nr_score_tile.h
@@ -151,6 +155,23 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, Gro
     if (ul < TU && u0 + ul < a.U) {
       w_lo = a.pool.lo_of(u0 + ul);
       w_hi = a.pool.hi_of(u0 + ul);
+    }
+  }
+
+  // SAMPLE: lane i keeps tau and the counter word of this wave's i-th user; a tau that is negative, NaN or infinite empties
+  // the user's window: every key 0, an all-fill row
+  float tau_l = 0.f;
+  uint32_t key_l = 0u;
+  if constexpr (SAMPLE) {
+    const int ul = wave + TK_WAVES * lane;
+    if (ul < TU && u0 + ul < a.U) {
+      tau_l = sa.tau_of(u0 + ul);
+      key_l = sa.key_of(u0 + ul);
+      if (!(tau_l >= 0.f && tau_l < __builtin_inff())) {
+        tau_l = 0.f;
+        w_lo = 1;
+        w_hi = 0;
+      }
     }
   }
 
@@ -188,7 +209,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(TopkArgs a, Gro
 
     for (int ul = wave, iu = 0; ul < TU && u0 + ul < a.U; ul += TK_WAVES, ++iu) {
       uint32_t k0, k1;
-      if constexpr (POOL) {
+      if constexpr (SAMPLE) {
+        const int32_t lo = __builtin_amdgcn_readlane(w_lo, iu), hi = __builtin_amdgcn_readlane(w_hi, iu);
+        const float tau = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tau_l), iu));
+        const uint32_t ukey = (uint32_t)__builtin_amdgcn_readlane((int)key_l, iu), t0 = sThr[ul];
+        k0 = lane < nvalid ? sample_key(sS[ul * TK_LDS_TILE + lane], p0, s0, lo, hi, tau, sa, ukey, (uint32_t)(vc + lane), t0) : 0u;
+        k1 = lane + 64 < nvalid ? sample_key(sS[ul * TK_LDS_TILE + lane + 64], p1, s1, lo, hi, tau, sa, ukey, (uint32_t)(vc + lane + 64), t0) : 0u;
+      } else if constexpr (POOL) {
         const int32_t lo = __builtin_amdgcn_readlane(w_lo, iu), hi = __builtin_amdgcn_readlane(w_hi, iu);
         k0 = lane < nvalid ? pool_key(sS[ul * TK_LDS_TILE + lane], p0, s0, lo, hi) : 0u;
         k1 = lane + 64 < nvalid ? pool_key(sS[ul * TK_LDS_TILE + lane + 64], p1, s1, lo, hi) : 0u;
@@ -382,6 +409,39 @@ int topk_check(const nr_topk_desc* d) {
   return NR_OK;
 }
 
+// K12: the model part of a sampled row, fl32(perturbed - fl32(tau_u * g)), from the ids and perturbed scores the merge wrote; the
+// noise is made again from (user key, id) -- the same function, the same bits as in the selection.  -inf in fill.
+__global__ __launch_bounds__(256) void sample_model_kernel(const int32_t* __restrict__ ids, const float* __restrict__ perturbed, SampleArgs sa,
+                                                            int k, long n, float* __restrict__ out_model) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long u = i / k;
+  const int32_t id = ids[i];
+  float m = -__builtin_inff();
+  if (id > 0) m = __fsub_rn(perturbed[i], sample_scaled(sa.tau_of(u), sa.gumbel(sa.key_of(u), (uint32_t)id)));
+  out_model[i] = m;
+}
+
+// K12 probe: the noise of n (user key, news id) pairs, element-wise
+__global__ __launch_bounds__(256) void sample_noise_kernel(SampleArgs sa, const int32_t* __restrict__ user_keys, const int32_t* __restrict__ news_ids,
+                                                            int n, float* __restrict__ out_g, uint32_t* __restrict__ out_bits) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t bits = sample_bits((uint32_t)user_keys[i], (uint32_t)news_ids[i], sa.seed_lo, sa.seed_hi, sa.draw);
+  if (out_bits != nullptr) out_bits[i] = bits;
+  if (out_g != nullptr) out_g[i] = sample_gumbel(bits);
+}
+
+// nr_score_topk's checks plus the fields of the sampled call; 0 = fine
+int sample_check(const nr_sample_desc* d) {
+  NR_CHECK_ARG(d != nullptr, "score_sample: null descriptor");
+  const int rc = topk_check(&d->topk);
+  if (rc != NR_OK) return rc;
+  NR_CHECK_ARG(d->tau_u != nullptr || (d->tau >= 0.f && d->tau <= 3.402823466e38f), "score_sample: tau = %g, must be finite and >= 0",
+               (double)d->tau);
+  return NR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,7 +452,8 @@ size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d) {
   return (size_t)d->U * splits * d->k * sizeof(u64);
 }
 
-int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
+// the two launches of nr_score_topk (sa == nullptr) and of nr_score_sample
+static int topk_run(const nr_topk_desc* d, const SampleArgs* sa_in, nr_stream_t stream) {
   const int rc = topk_check(d);
   if (rc != NR_OK) return rc;
   NR_CHECK_ARG(d->news_vecs && d->user && d->out_ids && d->out_scores, "score_topk: null pointer (news_vecs, user, out_ids, out_scores)");
@@ -416,6 +477,8 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
   a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
   const GroupArgs ga = {d->group, d->group_cap};
+  const bool sampled = sa_in != nullptr;
+  const SampleArgs sa = sampled ? *sa_in : SampleArgs{0u, 0u, 0u, 0.f, nullptr, nullptr};
   const bool pool = a.pool.any();
   const bool grouped = d->group != nullptr;
   const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
@@ -424,18 +487,20 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
   const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
   {
     NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
-#define NR_TOPK_LAUNCH(MT, POOL, GROUP, CSR)                                                                                   \
+#define NR_TOPK_LAUNCH(MT, POOL, GROUP, CSR, SAMPLE)                                                                           \
   do {                                                                                                                         \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP, CSR>),                  \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP, CSR, SAMPLE>),          \
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                  \
-    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP, CSR>), grid, dim3(TK_THREADS), smem, s, a, ga, ca);                \
+    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP, CSR, SAMPLE>), grid, dim3(TK_THREADS), smem, s, a, ga, ca, sa);    \
   } while (0)
-#define NR_TOPK_LAUNCH_PG(MT, CSR)                            \
-  do {                                                        \
-    if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR); \
-    else if (pool) NR_TOPK_LAUNCH(MT, true, false, CSR);      \
-    else if (grouped) NR_TOPK_LAUNCH(MT, false, true, CSR);   \
-    else NR_TOPK_LAUNCH(MT, false, false, CSR);               \
+#define NR_TOPK_LAUNCH_PG(MT, CSR)                                          \
+  do {                                                                      \
+    if (sampled && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR, true);      \
+    else if (sampled) NR_TOPK_LAUNCH(MT, true, false, CSR, true);           \
+    else if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR, false);   \
+    else if (pool) NR_TOPK_LAUNCH(MT, true, false, CSR, false);             \
+    else if (grouped) NR_TOPK_LAUNCH(MT, false, true, CSR, false);          \
+    else NR_TOPK_LAUNCH(MT, false, false, CSR, false);                      \
   } while (0)
 #define NR_TOPK_LAUNCH_MT(MT)            \
   do {                                   \
@@ -463,6 +528,47 @@ int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) {
     } else
       hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)d->U), dim3(256), (size_t)P * sizeof(u64), s, (const u64*)a.part, n, P, d->k, d->out_ids,
                          d->out_scores);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_score_topk(const nr_topk_desc* d, nr_stream_t stream) { return topk_run(d, nullptr, stream); }
+
+size_t nr_score_sample_workspace_bytes(const nr_sample_desc* d) {
+  if (sample_check(d) != NR_OK) return 0;
+  return nr_score_topk_workspace_bytes(&d->topk);
+}
+
+int nr_score_sample(const nr_sample_desc* d, nr_stream_t stream) {
+  const int rc = sample_check(d);
+  if (rc != NR_OK) return rc;
+  const SampleArgs sa = {(uint32_t)(d->seed & 0xffffffffull), (uint32_t)(d->seed >> 32), d->draw, d->tau, d->tau_u, d->user_keys};
+  const int rr = topk_run(&d->topk, &sa, stream);
+  if (rr != NR_OK || d->out_model == nullptr) return rr;
+  NR_DEVICE_GUARD(stream, d->topk.news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)d->topk.U * d->topk.k;
+  {
+    NrProfScope ps(s, "sample_model[U=%d,k=%d]", d->topk.U, d->topk.k);
+    hipLaunchKernelGGL(sample_model_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t*)d->topk.out_ids,
+                       (const float*)d->topk.out_scores, sa, d->topk.k, n, d->out_model);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_sample_noise(uint64_t seed, uint32_t draw, const int32_t* user_keys, const int32_t* news_ids, int n, float* out_g, uint32_t* out_bits,
+                    nr_stream_t stream) {
+  NR_CHECK_ARG(n >= 0, "sample_noise: n = %d pairs, must be >= 0", n);
+  if (n == 0) return NR_OK;
+  NR_CHECK_ARG(user_keys != nullptr && news_ids != nullptr, "sample_noise: null pointer (user_keys, news_ids)");
+  NR_DEVICE_GUARD(stream, news_ids);
+  hipStream_t s = (hipStream_t)stream;
+  const SampleArgs sa = {(uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), draw, 0.f, nullptr, nullptr};
+  {
+    NrProfScope ps(s, "sample_noise[n=%d]", n);
+    hipLaunchKernelGGL(sample_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sa, user_keys, news_ids, n, out_g, out_bits);
   }
   NR_CHECK_LAUNCH();
   return NR_OK;

@@ -239,6 +239,67 @@ def mmr_reference(news, pool_ids, pool_scores, *, k, penalty, group=None, group_
     return ids, out, places, margins
 
 
+def philox4x32(counter, key, rounds=10):
+    """Philox4x32 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", 2011) in numpy integers: counter [..., 4] and
+    key [..., 2] of 32-bit words (they broadcast against each other); returns the four output words uint32 [..., 4].
+    Multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85; the key is bumped between rounds."""
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape) for i in range(2))
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(rounds):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2          # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def sample_noise_reference(seed, draw, user_keys, news_ids):
+    """The noise of nr_score_sample (include/nrhip.h, K12) for pairs (user_keys[i], news_ids[i]) -- the two arrays broadcast:
+    bits = Philox4x32-10(counter = (v >> 2, a, draw, 0), key = (seed & 0xffffffff, seed >> 32))[v & 3], integer-exact;
+    u = ((bits >> 8) + 0.5) * 2^-24 and g = -log(-log(u)) in float64.  Returns (g float64, bits uint32)."""
+    a = np.asarray(user_keys, dtype=np.int64) & 0xFFFFFFFF
+    v = np.asarray(news_ids, dtype=np.int64) & 0xFFFFFFFF
+    a, v = np.broadcast_arrays(a, v)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.stack([v >> 2, a, np.full(v.shape, int(draw) & 0xFFFFFFFF, dtype=np.int64), np.zeros(v.shape, dtype=np.int64)], axis=-1)
+    words = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    bits = np.take_along_axis(words, (v & 3)[..., None], axis=-1)[..., 0]
+    u = ((bits >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    return -np.log(-np.log(u)), bits
+
+
+def sample_reference(a, b=None, *, k, temperature, seed, draw=0, user_keys=None, exclude=None, prior=None, stamp=None, window=None, group=None,
+                     group_cap=None):
+    """Host statement of the sampled recommendation contract (include/nrhip.h, nr_score_sample); tests check the device
+    against it, no product path calls it.
+
+    `a`, `b`, `exclude`, the pools and the caps are topk_reference's.  Row u is topk_reference's row for the scores
+    score[u, v] + prior[v] + tau_u * g(user_keys[u], v) in float64, g the Gumbel noise of sample_noise_reference under (seed,
+    draw): k news without replacement, each draw proportional to exp((score + prior) / tau_u) over what is left
+    (Plackett-Luce), under caps renormalised over what may still be taken.  temperature: a scalar or [U], finite and >= 0 --
+    a user whose entry is negative, NaN or infinite gets an all-fill row; 0 is topk_reference itself.  user_keys [U] (None =
+    0 .. U-1) name the users in the noise.
+    Returns (ids int32 [U, k], perturbed float64 [U, k] -- the values the row is ordered by --, model float64 [U, k] -- score +
+    prior of the news taken; -inf in fill)."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    U, V = scores.shape
+    tau = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (U,)) if np.ndim(temperature) else np.full(U, float(temperature))
+    keys = np.arange(U, dtype=np.int64) if user_keys is None else np.asarray(user_keys, dtype=np.int64).reshape(U)
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.isfinite(tau) & (tau >= 0))
+    g, _ = sample_noise_reference(seed, draw, keys[:, None], np.arange(V, dtype=np.int64)[None, :])
+    noise = np.where(bad, 0.0, tau)[:, None] * g
+    ids, perturbed = topk_reference(scores + noise, k=k, exclude=exclude, prior=prior, stamp=stamp, window=window, group=group, group_cap=group_cap)
+    ids[bad], perturbed[bad] = 0, -np.inf
+    with np.errstate(invalid="ignore"):
+        model = np.where(ids > 0, perturbed - np.take_along_axis(noise, ids.astype(np.int64), axis=1), -np.inf)
+    return ids, perturbed, model
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

@@ -1194,36 +1194,108 @@ def score_topk(news_vecs, user_vecs, k, exclude=None, splits=0, prior=None, stam
     news of its group are taken, so at most c per group and still k entries where k can be taken (otherwise the usual fill).
     One without the other is refused by the library.  Without them the call launches the kernels it always launched.
     score_rank_capped takes the same two arguments and gives the place in this capped row."""
+    d, ids, scores, keep = _topk_desc("score_topk", news_vecs, user_vecs, k, exclude, splits, prior, stamp, window, group, group_cap)
+    if d is None:
+        return ids, scores
+    ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), ids.device)      # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_topk(C.byref(d), _stream()), "nr_score_topk")
+    return ids, scores
+
+
+def _topk_desc(what, news_vecs, user_vecs, k, exclude, splits, prior, stamp, window, group, group_cap):
+    """The nr_topk_desc of score_topk / score_sample without its workspace, after the checks the two share.  Returns (descriptor,
+    ids, scores, keepalive); the descriptor is None for U == 0 (nothing to launch)."""
     _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise RuntimeError(f"score_topk: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
+            raise RuntimeError(f"{what}: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
                                f"strides {tuple(t.stride())}")
     V, N = news_vecs.shape
     U = user_vecs.shape[0]
     if user_vecs.shape[1] != N:
-        raise RuntimeError(f"score_topk: vector widths differ ({N} vs {user_vecs.shape[1]})")
+        raise RuntimeError(f"{what}: vector widths differ ({N} vs {user_vecs.shape[1]})")
     dev = news_vecs.device
     ids = torch.empty(U, int(k), dtype=torch.int32, device=dev)
     scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
     if U == 0:
-        return ids, scores
-    ex_fields, ex_keep = _exclude_args("score_topk", exclude, U, dev)
-    pr, st, win = _pool_args("score_topk", V, U, dev, prior, stamp, window)
+        return None, ids, scores, None
+    ex_fields, ex_keep = _exclude_args(what, exclude, U, dev)
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
     gr = None
     if group is not None:
         if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
-            raise RuntimeError(f"score_topk: group must be an int32 tensor of shape ({V},) on {dev}, got "
+            raise RuntimeError(f"{what}: group must be an int32 tensor of shape ({V},) on {dev}, got "
                                f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
         gr = group.detach().contiguous()
     d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), **ex_fields,
                       splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
                       ld_window=2 if win is not None else 0, group=ptr(gr), group_cap=0 if group_cap is None else int(group_cap))
-    ws = _ws(_lib.lib().nr_score_topk_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
-    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
-    check(_lib.lib().nr_score_topk(C.byref(d), _stream()), "nr_score_topk")
-    return ids, scores
+    return d, ids, scores, (ex_keep, pr, st, win, gr)
+
+
+@torch.no_grad()
+def score_sample(news_vecs, user_vecs, k, temperature, seed, draw=0, user_keys=None, exclude=None, splits=0, prior=None, stamp=None, window=None,
+                 group=None, group_cap=None):
+    """Sampled full-corpus recommendation (nr_score_sample; include/nrhip.h, K12): for every user k news drawn WITHOUT
+    replacement, each draw proportional to exp(score / temperature) over what is left (the Plackett-Luce model), by the
+    Gumbel-max trick fused into score_topk's selection: temperature * g is added to every score, g a standard Gumbel variate
+    per (user, news) made in registers from (seed, draw, user key, news id), and the k largest are taken.  No [U, V] matrix of
+    scores or of noise is formed.  Everything else -- `exclude`, `splits`, the pools, the caps -- is score_topk's; with caps
+    the row is sequential sampling from the softmax over what may still be taken.
+    `temperature`: a float (finite, >= 0) or a floating point tensor [U], one per user; 0 gives score_topk's row, bit for bit;
+    a tensor entry that is negative, NaN or infinite gives that user an all-fill row.
+    `seed` (64 bits) and `draw` (32 bits) name the draw; `user_keys` (integer tensor [U], taken as uint32; None = 0 .. U-1) name
+    the users: the row of a user depends on its key, never on its place in the batch, on `splits` or on the rank it is served
+    from, so a caller who shards users passes global user numbers here.
+    Returns (ids int32 [U, k], perturbed fp32 [U, k] -- the values the row is ordered by, descending --, model_scores fp32
+    [U, k] -- fl32(perturbed - fl32(temperature * g)): the score (+ prior) of the news taken, to within two roundings); a row
+    with fewer than k eligible news ends in id 0, -inf, -inf."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(tau_t, user_keys)
+    d, ids, perturbed, keep = _topk_desc("score_sample", news_vecs, user_vecs, k, exclude, splits, prior, stamp, window, group, group_cap)
+    model = torch.empty_like(perturbed)
+    if d is None:
+        return ids, perturbed, model
+    U, dev = ids.shape[0], ids.device
+    tau = None
+    if tau_t is not None:
+        if tuple(tau_t.shape) != (U,) or not tau_t.is_floating_point() or tau_t.device != dev:
+            raise RuntimeError(f"score_sample: a temperature tensor must be floating point of shape ({U},) on {dev}, got {tuple(tau_t.shape)} "
+                               f"{tau_t.dtype} on {tau_t.device}")
+        tau = tau_t.detach().to(torch.float32).contiguous()
+    keys = None
+    if user_keys is not None:
+        if (not isinstance(user_keys, torch.Tensor) or tuple(user_keys.shape) != (U,) or user_keys.is_floating_point() or user_keys.is_complex()
+                or user_keys.dtype == torch.bool or user_keys.device != dev):
+            raise RuntimeError(f"score_sample: user_keys must be an integer tensor of shape ({U},) on {dev}, got "
+                               f"{(tuple(user_keys.shape), user_keys.dtype, user_keys.device) if isinstance(user_keys, torch.Tensor) else type(user_keys)}")
+        keys = user_keys.detach().to(torch.int32).contiguous()
+    sd = _lib.SampleDesc(topk=d, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, draw=int(draw) & 0xFFFFFFFF, tau=0.0 if tau is not None else float(temperature),
+                         tau_u=ptr(tau), user_keys=ptr(keys), out_model=ptr(model))
+    ws = _ws(_lib.lib().nr_score_sample_workspace_bytes(C.byref(sd)), dev)     # 0 for a bad descriptor: the call below says why
+    sd.topk.ws, sd.topk.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_sample(C.byref(sd), _stream()), "nr_score_sample")
+    return ids, perturbed, model
+
+
+@torch.no_grad()
+def sample_noise(seed, draw, user_keys, news_ids):
+    """The noise of score_sample for pairs (user_keys[i], news_ids[i]) (nr_sample_noise, the probe of include/nrhip.h K12): two
+    integer tensors of one shape on the GPU.  Returns (g fp32, bits int64 holding the 32-bit Philox word), of that shape; g is
+    the standard Gumbel variate the selection adds temperature times of -- the same device function."""
+    _need_gpu(user_keys, news_ids)
+    if user_keys.shape != news_ids.shape or user_keys.device != news_ids.device or user_keys.is_floating_point() or news_ids.is_floating_point():
+        raise RuntimeError(f"sample_noise: user_keys and news_ids must be integer tensors of one shape on one device, got "
+                           f"{tuple(user_keys.shape)} {user_keys.dtype} and {tuple(news_ids.shape)} {news_ids.dtype}")
+    a = user_keys.detach().to(torch.int32).contiguous()
+    v = news_ids.detach().to(torch.int32).contiguous()
+    g = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+    bits = torch.empty(a.shape, dtype=torch.int32, device=a.device)
+    check(_lib.lib().nr_sample_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, ptr(a), ptr(v), a.numel(), ptr(g), ptr(bits), _stream()),
+          "nr_sample_noise")
+    return g, bits.to(torch.int64) & 0xFFFFFFFF
 
 
 @torch.no_grad()

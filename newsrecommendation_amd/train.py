@@ -375,6 +375,29 @@ def recommend(model, news_vecs, hist_idx, mask, k, exclude_history=True, batch_s
     return ops.score_topk(news_vecs, user, k, exclude=exclude, **kw, **caps)
 
 
+@torch.no_grad()
+def recommend_sample(model, news_vecs, hist_idx, mask, k, temperature, seed, draw=0, user_keys=None, exclude_history=True, batch_size=8192,
+                     prior=None, news_time=None, window=None, news_group=None, group_cap=None, seen=None):
+    """Sampled full-corpus recommendation: recommend's row drawn instead of maximised -- k news without replacement, each draw
+    proportional to exp(score / temperature) over what is left (ops.score_sample; include/nrhip.h, K12).  A recommender that
+    serves these rows explores (a fresh article gets its share), does not repeat itself on every reload, and logs rows drawn
+    from a known distribution.  The user vectors, exclusions, pools and caps are recommend's.
+    temperature: a float or a [U] tensor (finite, >= 0; 0 is recommend's row, bit for bit); to choose it relative to a user's
+    own score spread see INTEGRATION.md.  seed, draw: the name of the draw.  user_keys [U] integers: global user numbers (None =
+    the row index) -- a user's row depends on its key only, not on batch, rank or place.
+    Returns (ids int32 [U, k], model_scores fp32 [U, k]): the scores (+ prior) of the news taken, to within rounding -- a row is
+    ordered by the perturbed values, not by them; a row with fewer than k eligible news ends in id 0, score -inf."""
+    news_vecs, user, exclude, kw, caps = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                         news_group, group_cap, seen)
+    device = news_vecs.device
+    if isinstance(temperature, torch.Tensor):
+        temperature = temperature.to(device=device, dtype=torch.float32)
+    if user_keys is not None:
+        user_keys = torch.as_tensor(user_keys).to(device=device)
+    ids, _, model_scores = ops.score_sample(news_vecs, user, k, temperature, seed, draw=draw, user_keys=user_keys, exclude=exclude, **kw, **caps)
+    return ids, model_scores
+
+
 def _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window, news_group, group_cap, seen):
     """What recommend and recommend_diverse share: the fp32 table, the user vectors, the exclusions, the pool keywords and the
     cap keywords (group / group_cap; what is None is left out) of ops.score_topk."""
