@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -699,6 +699,115 @@ size_t nr_score_sample_workspace_bytes(const nr_sample_desc* d);
 int nr_score_sample(const nr_sample_desc* d, nr_stream_t stream);
 int nr_sample_noise(uint64_t seed, uint32_t draw, const int32_t* user_keys, const int32_t* news_ids, int n, float* out_g, uint32_t* out_bits,
                     nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K13  full-corpus log-partition.  What a sampled row (K12) is reweighted by is the probability it was drawn with, and that,
+ * like the full-softmax log-likelihood of a held-out click, needs per user
+ *   log Z_u = log sum_v exp(score(u, v) / tau_u)   over exactly the news nr_score_topk / nr_score_sample call eligible for u.
+ * The reference has nothing of the kind; metrics.logz_reference states the contract on the host.  No [U, V] buffer exists.
+ * Score and eligibility are K9's, through the same definition (pool_key, csrc/nr_score_tile.h): score = fl32(dot + prior),
+ * the dot product the same fmaf chain, the same bits; eligible = id in [1, V), the sum not NaN, prior not -inf, stamp inside
+ * the user's window, id not in the user's CSR segment.  Three results per user:
+ *   out_max     [U] fp32: the largest eligible score, the bits nr_score_topk returns for k = 1; -inf when nothing is eligible
+ *   out_count   [U] int32: the number of eligible news, exact
+ *   out_logsum  [U] fp32: log sum_v exp((s(u, v) - out_max[u]) * (1 / tau_u)); >= 0 whenever the maximum is finite
+ * and log Z_u = out_max[u] / tau_u + out_logsum[u].  The parts stay apart so that log p(v) = (s_v - max) / tau - logsum never
+ * forms a large max / tau.
+ *   tau         scalar, used when tau_u == NULL; finite and > 0, else refused.  tau_u: optional [U] fp32.  An entry that is
+ *               <= 0, NaN or infinite gives that user out_logsum = NaN; its max and count stay valid, nobody else's row
+ *               changes.  1 / tau is ONE fp32 division per user (where it overflows, for a tau at the very bottom of the fp32
+ *               range, the weights are those of the limit: 1 for the maxima, 0 below).
+ *   lists       excl_offsets, excl_ids, n_excl: K9's CSR lists with K9's rules (strictly ascending segments; segment bounds
+ *               clamped into [0, n_excl]; an unsorted segment gives that user an unspecified result, never an access outside
+ *               the arrays).  The dense [U, E <= 64] list is not part of this call.  The listed news are left out IN the
+ *               stream, never subtracted afterwards: they are typically the heaviest terms of the sum.
+ *   edge cases  nothing eligible: count 0, max -inf, logsum -inf.  Largest eligible score +-inf: logsum NaN, max and count as
+ *               they are.  A score of -inf under a finite maximum weighs 0 and counts 1.  No NaN and no overflow when
+ *               (s - max) / tau spans thousands: every exponent formed is <= 0.
+ * The bits of all three depend on the inputs of that user only -- not on `splits`, the user tile, the place in it, or the
+ * other users of the call.  [1, V) is cut into nseg <= 256 segments of 128 * ceil((V - 1) / (128 * 256)) ids, a function of V
+ * alone; a slice is a run of whole segments; inside a segment every lane keeps a running (max, sum) over its own news (which
+ * lane sees which id is fixed by the segment start), a fixed-order wave reduction leaves one (max, sum, count) partial per
+ * (user, segment), and a second small kernel merges a user's partials in fp64 in a fixed order.  Two launches, no
+ * float atomics, no host synchronisation.  The derived error bound of out_logsum is in DESIGN.md section 5.
+ *   splits      0: the library chooses (fills the chip for few users); > 0: that many slices, at most nseg
+ *   ws          nr_score_logz_workspace_bytes(d) bytes, 8-byte aligned: U * nseg * 12, rounded; it depends on U and V only
+ *               (0 = bad descriptor, see nr_last_error)
+ * Refused before any launch (nr_last_error): what K9 refuses for N, ld_news / ld_user, alignment, V, U, stamp without window
+ * or the reverse, excl_offsets without excl_ids or the reverse, n_excl < 0; a bad scalar tau; splits outside [0, nseg]; an
+ * undersized workspace.  Group caps are not part of this call: the descriptor has no group fields.
+ * Layout: nr_topk_desc's conventions; the shared tail ws, ws_bytes, prior, stamp, window, ld_window.                       */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  float* out_logsum;
+  float* out_max;
+  int32_t* out_count;
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logz_desc;
+size_t nr_score_logz_workspace_bytes(const nr_logz_desc* d);
+int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K14  log-probabilities of the entries of named rows, on the partition of K13.  metrics.row_logprob_reference states the
+ * contract on the host.  One launch, no workspace: one workgroup per 16 users gathers the k <= 128 table rows a user names
+ * through the same MFMA tile (as the named pass of K10), so an entry has the score bits and the key the stream gives it; one
+ * wave per user then finishes in fp64 and rounds to fp32 once per output.
+ *   row_ids      [U, k] int32, row stride ld_ids, k in [1, NR_TOPK_MAX_K]
+ *   base_max, base_logsum   [U] fp32 each: out_max and out_logsum of a K13 call for these users, pools and temperatures
+ *   tau, tau_u   as in K13; an entry of tau_u that is <= 0, NaN or infinite gives NaN for every real entry of that user's row
+ *   out_logp     [U, k] fp32, contiguous;  out_total optional [U] fp32: the fp64 sum of the row, rounded once
+ * sequential = 1: Plackett-Luce without replacement, the law of nr_score_sample's rows.  The base must have been computed
+ * with the row's ids LEFT OUT of the sum (the caller merges them into the lists of K13).  With s_i the score of entry i, the
+ * mass that is left at step j is the base and the entries j .. k-1:
+ *   M_j = max(base_max, max_{i >= j} s_i)
+ *   L_j = log(exp((base_max - M_j) / tau + base_logsum) + sum_{i >= j} exp((s_i - M_j) / tau))
+ *   out_logp[u, j] = (s_j - M_j) / tau - L_j
+ * formed as a suffix scan of (max, sum) pairs: only positive terms are added, nothing is subtracted.  A row that takes
+ * everything eligible (base count 0: max -inf, logsum -inf) has out_logp == 0 exactly at its last place.
+ * sequential = 0: independent entries against the full partition, out_logp[u, j] = (s_j - base_max) / tau - base_logsum with
+ * the base computed over everything eligible, the entries included: the full-softmax log-probability of a held-out click.
+ * Special entries: an id that is 0 or outside [1, V) is fill -- logp 0, part of no sum.  An entry whose key is 0 (NaN score,
+ * prior -inf, stamp outside the window) gets NaN and is part of no sum either.  Whether an entry is in the user's lists, and
+ * repeats within a row, are the CALLER'S statement and are not checked: a repeated id is simply two entries.
+ * Refused before any launch: a null descriptor or required pointer; k out of range; N, ld_news / ld_user, alignment, V, U,
+ * stamp without window or the reverse against K9's rules; ld_ids < k; a bad scalar tau; sequential outside {0, 1}.
+ * Group caps are not part of this call (under caps the mass that is left needs per-group partitions).                      */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, k;
+  const int32_t* row_ids;
+  int ld_ids;
+  int sequential;           /* 1: Plackett-Luce without replacement; 0: independent entries */
+  float tau;                /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;       /* optional [U] */
+  const float* base_max;    /* [U]: out_max of K13 */
+  const float* base_logsum; /* [U]: out_logsum of K13 */
+  float* out_logp;          /* [U, k] */
+  float* out_total;         /* optional [U] */
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logprob_desc;
+int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

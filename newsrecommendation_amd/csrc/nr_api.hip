@@ -485,6 +485,8 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 9) out[8] = sizeof(nr_rank_desc);
   if (n >= 10) out[9] = sizeof(nr_mmr_desc);
   if (n >= 11) out[10] = sizeof(nr_sample_desc);
+  if (n >= 12) out[11] = sizeof(nr_logz_desc);
+  if (n >= 13) out[12] = sizeof(nr_logprob_desc);
   return NR_OK;
 }
 

@@ -1,0 +1,604 @@
+// Propensities of full-corpus rows: the log-partition of a user's whole score row, and on it the log-probabilities of the
+// entries of named rows -- again without the [U, V] score matrix.  The third consumer of the tile of nr_score_tile.h (after the
+// selection of nr_topk.hip and the counting of nr_rank.hip): summing in place of counting.  Scores and eligibility come from
+// score_key / pool_key, so one (u, v) pair has here the bits and the verdict it has in nr_score_topk and nr_score_rank.
+//
+//   logz_stream_kernel<MT, POOL, LISTS>   the grid, chunking, user tile and LDS budget of rank_count_kernel.  [1, V) is cut into
+//                           nseg <= 256 SEGMENTS of seg = 128 * ceil((V - 1) / (128 * 256)) ids, a function of V alone; a slice
+//                           (blockIdx.y) is a run of whole segments.  A wave owns TU / 8 users; after put_scores lane l holds
+//                           news vc + l and vc + l + 64 of the chunk at vc.  Chunk starts are segment start + 128 q, so which
+//                           lane sees which id is fixed by V.  Per user and lane: a running (max, sum of exp((x - max) / tau),
+//                           count) over the lane's eligible news of the segment, rescaled when the lane's maximum rises -- one
+//                           expf per news.  At the segment end: wave maximum (exact), each lane rescales its sum once, xor
+//                           butterfly sum, and lane 0 stores ONE (max, sum, count) partial per (user, segment).  Nothing in a
+//                           partial depends on the slices, the user tile, the place in it or the other users.
+//                           LISTS: exclusion lists in CSR form (include/nrhip.h, K13).  Exclusion happens HERE, in the stream:
+//                           the listed news (the clicked history, the row already taken) are typically the heaviest terms of the
+//                           sum, and subtracting their weights afterwards would cancel.  Every user of the wave keeps a cursor
+//                           into its strictly ascending segment, set by a 64-ary search to the first entry >= the slice start;
+//                           per chunk the at most 128 entries inside it become two 64-bit "listed" masks in scalar registers.
+//   logz_final_kernel       one wave per user, four partials a lane: maximum of the partials (exact), then their sums rescaled to
+//                           it and added in fp64 in a fixed order (the lane's segments ascending, then an xor butterfly), one
+//                           log, rounded to fp32 once.
+//   logp_rows_kernel<POOL>  the named-row gather of rank_named_kernel: one workgroup per 16 users, chunk c = the k <= 128 rows user
+//                           c names, so the entries get the stream's score bits.  Then one wave per user finishes in fp64: a
+//                           suffix scan of (max, sum) pairs over the row joined with the user's base partition (sequential =
+//                           Plackett-Luce without replacement; only positive terms are added), or each entry against the base
+//                           alone (independent).
+#include <math.h>
+
+#include "nr_score_tile.h"
+
+namespace {
+
+constexpr int LZ_MAX_SEGS = 256;
+constexpr float LZ_INF = __builtin_inff();
+
+// the tile is what the vectors and the staging buffers leave room for, as in the counting pass of nr_rank.hip
+inline size_t lz_lds_bytes(int TU, int N) { return tk_tile_floats(TU, N) * sizeof(float); }
+inline int lz_user_tile(int N) {
+  for (int tu = 64; tu > 16; tu >>= 1)
+    if (lz_lds_bytes(tu, N) <= TK_LDS_MAX) return tu;
+  return 16;
+}
+struct LogzPlan {
+  int TU, seg, nseg, splits, segs_per;
+};
+// seg and nseg depend on V alone; `splits` (0: fill the chip, as rk_auto_splits does) only groups whole segments into slices
+inline LogzPlan lz_plan(int U, int V, int N, int splits) {
+  LogzPlan p;
+  p.TU = lz_user_tile(N);
+  const long per = (long)TK_ROWS * LZ_MAX_SEGS;
+  p.seg = TK_ROWS * (int)(((long)V - 1 + per - 1) / per);
+  p.nseg = (int)(((long)V - 1 + p.seg - 1) / p.seg);
+  long s = splits;
+  if (s <= 0) {
+    const long tiles = ((long)U + p.TU - 1) / p.TU;
+    s = (TK_CUS + tiles - 1) / tiles;
+  }
+  if (s > p.nseg) s = p.nseg;
+  if (s < 1) s = 1;
+  p.segs_per = (int)((p.nseg + s - 1) / s);
+  p.splits = (p.nseg + p.segs_per - 1) / p.segs_per;   // no empty slice
+  return p;
+}
+
+struct LogzArgs {
+  const float* news;
+  const float* user;
+  size_t ld_news, ld_user;
+  int V, U, N, seg, nseg, segs_per;
+  PoolArgs pool;            // read by the POOL instantiations only
+  float tau;                // used when tau_u is null
+  const float* tau_u;       // [U] or null
+  float* pm;                // [U, nseg] partial maxima, -inf = nothing eligible in the segment
+  float* ps;                // [U, nseg] partial sums of exp((x - pm) / tau)
+  int32_t* pc;              // [U, nseg] eligible news of the segment
+  __device__ __forceinline__ float tau_of(long u) const { return tau_u != nullptr ? tau_u[u] : tau; }
+};
+// workspace: the three [U, nseg] arrays, 12 bytes per (user, segment), rounded to 8
+inline size_t lz_carve(void* ws, int U, int nseg, LogzArgs* a) {
+  char* p = reinterpret_cast<char*>(ws);
+  const size_t n = (size_t)U * nseg;
+  if (a) {
+    a->pm = reinterpret_cast<float*>(p);
+    a->ps = reinterpret_cast<float*>(p + n * 4);
+    a->pc = reinterpret_cast<int32_t*>(p + n * 8);
+  }
+  return (n * 12 + 7) & ~(size_t)7;
+}
+
+__device__ __forceinline__ int lz_wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One eligible news x into a lane's running (m, s): s = sum of exp((x_i - m) * it) over what the lane has seen, m their maximum.
+// e = exp(-|x - m| * it) serves both cases: a new maximum rescales the sum by it and adds 1, anything else adds it.  x == m adds
+// exactly 1 without forming inf - inf; -inf under a finite maximum adds exp(-inf) = 0.
+__device__ __forceinline__ void lz_take(float x, float it, float& m, float& s) {
+  const bool up = x > m;
+  const float d = up ? m - x : x - m;
+  const float e = x == m ? 1.f : expf(d * it);
+  s = up ? fmaf(s, e, 1.f) : s + e;
+  m = up ? x : m;
+}
+
+template <int MT, bool POOL, bool LISTS>
+__global__ __launch_bounds__(TK_THREADS) void logz_stream_kernel(LogzArgs a, CsrArgs ca) {
+  constexpr int TU = 16 * MT, PER_WAVE = TU / TK_WAVES;
+  extern __shared__ __attribute__((aligned(16))) float lz_smem[];
+  ScoreTile<MT> t(lz_smem, a.N);
+  const int lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * TU;
+  const int s_lo = (int)blockIdx.y * a.segs_per;
+  const int s_hi = s_lo + a.segs_per < a.nseg ? s_lo + a.segs_per : a.nseg;
+  const long v_lo = 1 + (long)s_lo * a.seg;
+  const long v_hi = 1 + (long)s_hi * a.seg < a.V ? 1 + (long)s_hi * a.seg : a.V;
+  if (v_lo >= v_hi) return;                                   // the whole workgroup
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  // user wave + 8 i of the tile: 1 / tau and this lane's running (max, sum, count) of the segment
+  float it[PER_WAVE], m[PER_WAVE], s[PER_WAVE];
+  int32_t cnt[PER_WAVE];
+#pragma unroll
+  for (int i = 0; i < PER_WAVE; ++i) {
+    const int u = u0 + wave + TK_WAVES * i;
+    it[i] = __fdiv_rn(1.f, u < a.U ? a.tau_of(u) : 1.f);
+    m[i] = -LZ_INF;
+    s[i] = 0.f;
+    cnt[i] = 0;
+  }
+  // LISTS: the cursor of every user of the wave = the first entry of its segment that is >= v_lo.  A 64-ary search, the users of
+  // the wave side by side (their probes are independent loads): answer in [lo, hi], 64 probes lo + lane * step a round; ascending
+  // entries make "probe < v_lo" a prefix of p lanes, which leaves (lo + (p - 1) step, lo + p step].  Every index formed lies in
+  // [lo, hi) within the clamped segment; a round shrinks an open range below its step, so the loop ends whatever the entries hold.
+  int32_t cur[PER_WAVE], end[PER_WAVE];
+  if constexpr (LISTS) {
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int u = u0 + wave + TK_WAVES * i;
+      cur[i] = end[i] = 0;
+      if (u < a.U) ca.segment(u, cur[i], end[i]);
+    }
+    int32_t hi[PER_WAVE];
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) hi[i] = end[i];
+    for (;;) {
+      int32_t val[PER_WAVE], step[PER_WAVE];
+#pragma unroll
+      for (int i = 0; i < PER_WAVE; ++i) {
+        const int32_t n = hi[i] - cur[i];
+        step[i] = (n + 63) >> 6;
+        const long idx = (long)cur[i] + (long)lane * step[i];
+        val[i] = n > 0 && idx < hi[i] ? ca.ids[idx] : 0x7fffffff;
+      }
+      bool open = false;
+#pragma unroll
+      for (int i = 0; i < PER_WAVE; ++i) {
+        const int32_t n = hi[i] - cur[i];
+        if (n <= 0) continue;
+        const long idx = (long)cur[i] + (long)lane * step[i];
+        const int p = __popcll(__ballot(idx < hi[i] && (long)val[i] < v_lo));
+        if (p == 0) hi[i] = cur[i];
+        else if (step[i] == 1) { cur[i] += p; hi[i] = cur[i]; }
+        else {
+          const long nh = (long)cur[i] + (long)p * step[i];
+          cur[i] = (int32_t)((long)cur[i] + (long)(p - 1) * step[i] + 1);
+          hi[i] = nh < hi[i] ? (int32_t)nh : hi[i];
+        }
+        open = open || hi[i] > cur[i];
+      }
+      if (!open) break;
+    }
+  }
+  // POOL: lane i keeps the window of this wave's i-th user; an empty one beyond U
+  int32_t w_lo = 1, w_hi = 0;
+  if constexpr (POOL) {
+    const int u = u0 + wave + TK_WAVES * lane;
+    if (lane < PER_WAVE && u < a.U) {
+      w_lo = a.pool.lo_of(u);
+      w_hi = a.pool.hi_of(u);
+    }
+  }
+
+  ScoreStreamRows rows = {a.news, a.ld_news, v_lo, v_hi};
+  t.load_slab(rows, 0);
+  for (long vc = v_lo; vc < v_hi; vc += TK_ROWS) {
+    f32x4 acc[MT];
+    rows.vc = vc;
+    t.chunk(rows, acc);
+    rows.vc = vc + TK_ROWS;
+    if (rows.vc < v_hi) t.load_slab(rows, 0);                 // in flight while this chunk is summed
+    // POOL: prior and stamp of the chunk's 128 news, two per lane, once per chunk and wave (coalesced; in flight over the barrier)
+    float p0 = 0.f, p1 = 0.f;
+    int32_t s0 = 0, s1 = 0;
+    if constexpr (POOL) {
+      if (vc + lane < v_hi) {
+        p0 = a.pool.prior_of(vc + lane);
+        s0 = a.pool.stamp_of(vc + lane);
+      }
+      if (vc + lane + 64 < v_hi) {
+        p1 = a.pool.prior_of(vc + lane + 64);
+        s1 = a.pool.stamp_of(vc + lane + 64);
+      }
+    }
+    // LISTS: the next 64 entries of every user's segment from its cursor on (in flight over the barrier)
+    int32_t e0[LISTS ? PER_WAVE : 1];
+    if constexpr (LISTS) {
+#pragma unroll
+      for (int i = 0; i < PER_WAVE; ++i) e0[i] = (long)cur[i] + lane < end[i] ? ca.ids[(long)cur[i] + lane] : 0x7fffffff;
+    }
+    t.put_scores(acc);
+    const float* sS = t.scores();
+    const int nvalid = (int)(v_hi - vc < TK_ROWS ? v_hi - vc : TK_ROWS);
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int ul = wave + TK_WAVES * i;
+      // LISTS: the entries inside [vc, vc + 128) are a prefix of what the cursor points at; bit r of (l0, l1) = news vc + r is listed
+      u64 l0 = 0ull, l1 = 0ull;
+      if constexpr (LISTS) {
+        int32_t e = e0[i];
+        for (;;) {
+          const int c = __popcll(__ballot((long)cur[i] + lane < end[i] && (long)e < vc + TK_ROWS));
+          for (int j = 0; j < c; ++j) {
+            const uint32_t r = (uint32_t)((long)__builtin_amdgcn_readlane(e, j) - vc);
+            if (r < 64u) l0 |= 1ull << r;
+            else if (r < 128u) l1 |= 1ull << (r - 64u);
+          }
+          cur[i] += c;
+          if (c < 64) break;                                  // a full probe: the chunk may hold 64 more
+          e = (long)cur[i] + lane < end[i] ? ca.ids[(long)cur[i] + lane] : 0x7fffffff;
+        }
+      }
+      uint32_t k0, k1;
+      if constexpr (POOL) {
+        const int32_t lo = __builtin_amdgcn_readlane(w_lo, i), hi = __builtin_amdgcn_readlane(w_hi, i);
+        k0 = pool_key(sS[ul * TK_LDS_TILE + lane], p0, s0, lo, hi);
+        k1 = pool_key(sS[ul * TK_LDS_TILE + lane + 64], p1, s1, lo, hi);
+      } else {
+        k0 = score_key(sS[ul * TK_LDS_TILE + lane]);
+        k1 = score_key(sS[ul * TK_LDS_TILE + lane + 64]);
+      }
+      // eligible: a row of the slice, key != 0 (not NaN, inside the pool), not listed; the score is key_score of the key
+      const bool el0 = lane < nvalid && k0 != 0u && ((l0 >> lane) & 1ull) == 0ull;
+      const bool el1 = lane + 64 < nvalid && k1 != 0u && ((l1 >> lane) & 1ull) == 0ull;
+      if (el0) {
+        lz_take(key_score(k0), it[i], m[i], s[i]);
+        ++cnt[i];
+      }
+      if (el1) {
+        lz_take(key_score(k1), it[i], m[i], s[i]);
+        ++cnt[i];
+      }
+    }
+    // segment end: one partial per (user, segment), in an order that V alone fixes
+    const long nxt = vc + TK_ROWS;
+    if (nxt >= v_hi || (nxt - 1) % a.seg == 0) {
+      const size_t sg = (size_t)((vc - 1) / a.seg);
+#pragma unroll
+      for (int i = 0; i < PER_WAVE; ++i) {
+        const int u = u0 + wave + TK_WAVES * i;
+        const float M = wave_max(m[i]);
+        const float sc = m[i] == M ? 1.f : expf((m[i] - M) * it[i]);
+        const float S = wave_sum(s[i] * sc);
+        const int C = lz_wave_sum_i(cnt[i]);
+        if (lane == 0 && u < a.U) {
+          a.pm[(size_t)u * a.nseg + sg] = M;
+          a.ps[(size_t)u * a.nseg + sg] = S;
+          a.pc[(size_t)u * a.nseg + sg] = C;
+        }
+        m[i] = -LZ_INF;
+        s[i] = 0.f;
+        cnt[i] = 0;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+}
+
+__device__ __forceinline__ double lz_wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One wave per user; lane l holds the partials of segments l, l + 64, l + 128, l + 192 (nseg <= 256).
+__global__ __launch_bounds__(256) void logz_final_kernel(LogzArgs a, float* __restrict__ out_logsum, float* __restrict__ out_max,
+                                                         int32_t* __restrict__ out_count) {
+  static_assert(LZ_MAX_SEGS == 4 * 64, "four partials per lane");
+  const int lane = threadIdx.x & 63;
+  const size_t u = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (u >= (size_t)a.U) return;                               // the whole wave
+  float mj[4], sj[4], M = -LZ_INF;
+  int32_t n = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = lane + 64 * q;
+    mj[q] = -LZ_INF;
+    sj[q] = 0.f;
+    if (j < a.nseg) {
+      mj[q] = a.pm[u * a.nseg + j];
+      sj[q] = a.ps[u * a.nseg + j];
+      n += a.pc[u * a.nseg + j];
+    }
+    M = fmaxf(M, mj[q]);
+  }
+  M = wave_max(M);
+  n = lz_wave_sum_i(n);
+  const float tau = a.tau_of(u);
+  const bool tau_ok = tau > 0.f && tau < LZ_INF;
+  float ls;
+  if (n == 0) ls = -LZ_INF;
+  else if (!tau_ok || !(fabsf(M) < LZ_INF)) ls = __builtin_nanf("");
+  else {
+    // fp64, in a fixed order: the lane's four segments ascending, then the xor butterfly over the lanes
+    const double it = (double)__fdiv_rn(1.f, tau);
+    double S = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (mj[q] != -LZ_INF) S += (double)sj[q] * (mj[q] == M ? 1.0 : exp(((double)mj[q] - (double)M) * it));
+    ls = (float)log(lz_wave_sum_d(S));
+  }
+  if (lane == 0) {
+    out_logsum[u] = ls;
+    out_max[u] = M;
+    out_count[u] = n;
+  }
+}
+
+// ---- K14 ----------------------------------------------------------------------------------------------------------------
+
+struct LogpArgs {
+  const float* news;
+  const float* user;
+  const int32_t* ids;
+  size_t ld_news, ld_user, ld_ids;
+  int V, U, N, k, sequential;
+  PoolArgs pool;
+  float tau;
+  const float* tau_u;
+  const float* base_max;
+  const float* base_logsum;
+  float* out_logp;
+  float* out_total;         // [U] or null
+};
+
+// chunk row r = table row ids[r]; an id outside [1, V) is a row of zeros (its score is never looked at)
+struct LogpNamedRows {
+  const float* news;
+  size_t ld;
+  const int32_t* ids;   // LDS, [128]
+  int V;
+  __device__ __forceinline__ const float* operator()(int r) const {
+    const int32_t id = ids[r];
+    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
+  }
+};
+
+// (m, s): s = sum of exp((x_i - m) / tau) over a set with maximum m; (-inf, 0) is the empty set
+struct LogpPair {
+  double m, s;
+};
+__device__ __forceinline__ LogpPair lp_join(LogpPair x, LogpPair y, double tau) {
+  const double M = fmax(x.m, y.m);
+  const double ex = x.m == M ? 1.0 : exp((x.m - M) / tau), ey = y.m == M ? 1.0 : exp((y.m - M) / tau);
+  return {M, x.s * ex + y.s * ey};
+}
+__device__ __forceinline__ LogpPair lp_down(LogpPair x, int o) { return {__shfl_down(x.m, o, 64), __shfl_down(x.s, o, 64)}; }
+__device__ __forceinline__ double lp_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <bool POOL>
+__global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lp_smem[];
+  ScoreTile<1> t(lp_smem, a.N);
+  int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [16, 128] the ids the users name
+  uint32_t* sKey = reinterpret_cast<uint32_t*>(sIds + 16 * TK_ROWS);   // [16, 128] their keys, 0 = no score
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * 16;
+  const int users = a.U - u0 < 16 ? a.U - u0 : 16;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  for (int i = tid; i < 16 * TK_ROWS; i += TK_THREADS) {
+    const int ul = i / TK_ROWS, j = i - ul * TK_ROWS;
+    sIds[i] = ul < users && j < a.k ? a.ids[(size_t)(u0 + ul) * a.ld_ids + j] : 0;
+  }
+  __syncthreads();
+
+  LogpNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  t.load_slab(rows, 0);
+  for (int c = 0; c < users; ++c) {
+    f32x4 acc[1];
+    rows.ids = sIds + c * TK_ROWS;
+    t.chunk(rows, acc);
+    if (c + 1 < users) {
+      rows.ids = sIds + (c + 1) * TK_ROWS;
+      t.load_slab(rows, 0);
+    }
+    t.put_scores(acc);
+    if (wave == 0) {
+      // of the [16 x 128] scores only row c is kept, as its keys: prior and stamp gathered by id give the key of the stream
+      const size_t u = (size_t)(u0 + c);
+      int32_t lo = 0, hi = 0;
+      if constexpr (POOL) {
+        lo = a.pool.lo_of(u);
+        hi = a.pool.hi_of(u);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int r = lane + 64 * h;
+        const int32_t id = sIds[c * TK_ROWS + r];
+        uint32_t key = 0u;
+        if (id >= 1 && id < a.V) {
+          const float dot = t.scores()[c * TK_LDS_TILE + r];
+          if constexpr (POOL) key = pool_key(dot, a.pool.prior_of(id), a.pool.stamp_of(id), lo, hi);
+          else key = score_key(dot);
+        }
+        sKey[c * TK_ROWS + r] = key;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+
+  // one wave per user, in fp64; lane l holds entries 2 l and 2 l + 1 of the row
+  const double NaN = __builtin_nan(""), NINF = -(double)LZ_INF;
+  for (int c = wave; c < users; c += TK_WAVES) {
+    const size_t u = (size_t)(u0 + c);
+    const float tau_f = a.tau_u != nullptr ? a.tau_u[u] : a.tau;
+    const bool tau_ok = tau_f > 0.f && tau_f < LZ_INF;
+    const double tau = (double)tau_f;
+    const int j0 = 2 * lane, j1 = j0 + 1;
+    const int32_t id0 = sIds[c * TK_ROWS + j0], id1 = sIds[c * TK_ROWS + j1];
+    const uint32_t key0 = sKey[c * TK_ROWS + j0], key1 = sKey[c * TK_ROWS + j1];
+    const bool real0 = id0 >= 1 && id0 < a.V, real1 = id1 >= 1 && id1 < a.V;   // else fill: logp 0, in no sum
+    const bool live0 = key0 != 0u, live1 = key1 != 0u;                         // key 0: NaN, in no sum
+    const double x0 = (double)key_score(key0), x1 = (double)key_score(key1);
+    const double bm = (double)a.base_max[u], bl = (double)a.base_logsum[u];
+    double lp0, lp1;
+    if (a.sequential) {
+      const LogpPair none = {NINF, 0.0};
+      const LogpPair P0 = live0 ? LogpPair{x0, 1.0} : none, P1 = live1 ? LogpPair{x1, 1.0} : none;
+      // inclusive suffix scan over the lanes: R = entries 2 l .. 127
+      LogpPair R = lp_join(P0, P1, tau);
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const LogpPair other = lp_down(R, o);
+        if (lane + o < 64) R = lp_join(R, other, tau);
+      }
+      LogpPair after = lp_down(R, 1);                         // entries 2 l + 2 .. 127
+      if (lane == 63) after = none;
+      const LogpPair base = {bm, exp(bl)};                    // everything eligible that the row does not name
+      const LogpPair S1 = lp_join(P1, lp_join(after, base, tau), tau);
+      const LogpPair S0 = lp_join(P0, S1, tau);
+      lp0 = (x0 - S0.m) / tau - log(S0.s);
+      lp1 = (x1 - S1.m) / tau - log(S1.s);
+    } else {
+      lp0 = (x0 - bm) / tau - bl;
+      lp1 = (x1 - bm) / tau - bl;
+    }
+    lp0 = !real0 ? 0.0 : (!live0 || !tau_ok) ? NaN : lp0;
+    lp1 = !real1 ? 0.0 : (!live1 || !tau_ok) ? NaN : lp1;
+    if (j0 < a.k) a.out_logp[u * a.k + j0] = (float)lp0;
+    if (j1 < a.k) a.out_logp[u * a.k + j1] = (float)lp1;
+    if (a.out_total != nullptr) {
+      const double tot = lp_wave_sum(lp0 + lp1);              // entries beyond k are fill: 0
+      if (lane == 0) a.out_total[u] = (float)tot;
+    }
+  }
+}
+
+// argument checks shared by the size query and the call; 0 = fine
+int logz_check(const nr_logz_desc* d) {
+  NR_CHECK_ARG(d != nullptr, "score_logz: null descriptor");
+  NR_CHECK_ARG(d->V >= 2, "score_logz: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
+  NR_CHECK_ARG(d->U >= 1, "score_logz: U = %d users", d->U);
+  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_logz: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
+               NR_TOPK_MAX_N);
+  NR_CHECK_ARG(d->n_excl >= 0, "score_logz: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
+               "score_logz: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
+               "score_logz: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LZ_INF), "score_logz: tau = %g, a scalar temperature must be finite and > 0",
+               (double)d->tau);
+  const int nseg = lz_plan(d->U, d->V, d->N, 1).nseg;
+  NR_CHECK_ARG(d->splits >= 0 && d->splits <= nseg, "score_logz: splits = %d, must be 0 (library's choice) or in [1, %d], the segments of V = %d",
+               d->splits, nseg, d->V);
+  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_logz: stamp given without window (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_logz: window given without stamp (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_logz: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  return NR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nr_score_logz_workspace_bytes(const nr_logz_desc* d) {
+  if (logz_check(d) != NR_OK) return 0;
+  return lz_carve(nullptr, d->U, lz_plan(d->U, d->V, d->N, d->splits).nseg, nullptr);
+}
+
+int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream) {
+  const int rc = logz_check(d);
+  if (rc != NR_OK) return rc;
+  NR_CHECK_ARG(d->news_vecs && d->user && d->out_logsum && d->out_max && d->out_count,
+               "score_logz: null pointer (news_vecs, user, out_logsum, out_max, out_count)");
+  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
+                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
+               "score_logz: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  const size_t need = nr_score_logz_workspace_bytes(d);
+  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
+               "score_logz: workspace holds %zu bytes, nr_score_logz_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  const LogzPlan pl = lz_plan(d->U, d->V, d->N, d->splits);
+  LogzArgs a;
+  a.news = d->news_vecs; a.user = d->user;
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.seg = pl.seg; a.nseg = pl.nseg; a.segs_per = pl.segs_per;
+  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.tau = d->tau; a.tau_u = d->tau_u;
+  lz_carve(d->ws, d->U, pl.nseg, &a);
+  const bool pool = a.pool.any();
+  const bool lists = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
+  const CsrArgs ca = {lists ? d->excl_offsets : nullptr, lists ? d->excl_ids : nullptr, lists ? d->n_excl : 0};
+  {
+    const int TU = pl.TU;
+    const size_t smem = lz_lds_bytes(TU, d->N);
+    const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)pl.splits);
+    NrProfScope ps(s, "logz_stream[U=%d,V=%d,N=%d,TU=%d,splits=%d,seg=%d]", d->U, d->V, d->N, TU, pl.splits, pl.seg);
+#define NR_LOGZ_LAUNCH(MT, POOL, LISTS)                                                                                       \
+  do {                                                                                                                        \
+    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logz_stream_kernel<MT, POOL, LISTS>),                      \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                 \
+    hipLaunchKernelGGL((logz_stream_kernel<MT, POOL, LISTS>), grid, dim3(TK_THREADS), smem, s, a, ca);                        \
+  } while (0)
+#define NR_LOGZ_LAUNCH_MT(MT)                       \
+  do {                                              \
+    if (pool && lists) NR_LOGZ_LAUNCH(MT, true, true);   \
+    else if (pool) NR_LOGZ_LAUNCH(MT, true, false);      \
+    else if (lists) NR_LOGZ_LAUNCH(MT, false, true);     \
+    else NR_LOGZ_LAUNCH(MT, false, false);               \
+  } while (0)
+    if (TU == 64) NR_LOGZ_LAUNCH_MT(4);
+    else if (TU == 32) NR_LOGZ_LAUNCH_MT(2);
+    else NR_LOGZ_LAUNCH_MT(1);
+#undef NR_LOGZ_LAUNCH_MT
+#undef NR_LOGZ_LAUNCH
+  }
+  NR_CHECK_LAUNCH();
+  {
+    NrProfScope ps(s, "logz_final[U=%d,nseg=%d]", d->U, pl.nseg);
+    hipLaunchKernelGGL(logz_final_kernel, dim3((unsigned)((d->U + 3) / 4)), dim3(256), 0, s, a, d->out_logsum, d->out_max, d->out_count);
+  }
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream) {
+  NR_CHECK_ARG(d != nullptr, "row_logprob: null descriptor");
+  NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "row_logprob: k = %d entries per row, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
+  NR_CHECK_ARG(d->V >= 2, "row_logprob: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
+  NR_CHECK_ARG(d->U >= 1, "row_logprob: U = %d users", d->U);
+  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "row_logprob: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
+               NR_TOPK_MAX_N);
+  NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LZ_INF), "row_logprob: tau = %g, a scalar temperature must be finite and > 0",
+               (double)d->tau);
+  NR_CHECK_ARG(d->sequential == 0 || d->sequential == 1, "row_logprob: sequential = %d, must be 0 or 1", d->sequential);
+  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "row_logprob: stamp given without window (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "row_logprob: window given without stamp (the two come together)");
+  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "row_logprob: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_ARG(d->news_vecs && d->user && d->row_ids && d->base_max && d->base_logsum && d->out_logp,
+               "row_logprob: null pointer (news_vecs, user, row_ids, base_max, base_logsum, out_logp)");
+  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
+                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
+               "row_logprob: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_ARG(d->ld_ids >= d->k, "row_logprob: id row stride %d < k = %d", d->ld_ids, d->k);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  LogpArgs a;
+  a.news = d->news_vecs; a.user = d->user; a.ids = d->row_ids;
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_ids = (size_t)d->ld_ids;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.sequential = d->sequential;
+  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.tau = d->tau; a.tau_u = d->tau_u;
+  a.base_max = d->base_max; a.base_logsum = d->base_logsum;
+  a.out_logp = d->out_logp; a.out_total = d->out_total;
+  const bool pool = a.pool.any();
+  NrProfScope ps(s, "logp_rows[U=%d,N=%d,k=%d,seq=%d]", d->U, d->N, d->k, d->sequential);
+  const size_t smem = lz_lds_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
+  const void* fn = pool ? reinterpret_cast<const void*>(logp_rows_kernel<true>) : reinterpret_cast<const void*>(logp_rows_kernel<false>);
+  NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  if (pool) hipLaunchKernelGGL(logp_rows_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  else hipLaunchKernelGGL(logp_rows_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+}  // extern "C"

@@ -300,6 +300,93 @@ def sample_reference(a, b=None, *, k, temperature, seed, draw=0, user_keys=None,
     return ids, perturbed, model
 
 
+def _temperatures(temperature, U):
+    """[U] float64 temperatures and the mask of the valid ones (finite and > 0)."""
+    tau = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (U,)) if np.ndim(temperature) else np.full(U, float(temperature))
+    with np.errstate(invalid="ignore"):
+        return tau, np.isfinite(tau) & (tau > 0)
+
+
+def logz_reference(a, b=None, *, temperature, exclude=None, prior=None, stamp=None, window=None):
+    """Host statement of the full-corpus log-partition contract (include/nrhip.h, nr_score_logz); tests check the device against
+    it, no product path calls it.
+
+    `a`, `b`, `exclude` (ragged, any length) and the pools are topk_reference's, and so is what is eligible: ids 1 .. V-1 that
+    are not in exclude[u], whose score (+ prior) is not NaN, whose prior is not -inf and whose stamp lies in the user's window.
+    Per user, over its eligible news, in float64: smax = the largest score, count = how many, and
+    logsum = log sum exp((score - smax) / tau_u), so that log Z = smax / tau + logsum.  temperature: a scalar or [U]; an entry
+    that is not finite and > 0 gives logsum NaN and leaves smax and count.  Nothing eligible: (-inf, -inf, 0); a largest score
+    of +-inf: logsum NaN.  Returns (logsum float64 [U], smax float64 [U], count int64 [U])."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    tau, tau_ok = _temperatures(temperature, U)
+    logsum, smax, count = np.full(U, -np.inf), np.full(U, -np.inf), np.zeros(U, dtype=np.int64)
+    for u in range(U):
+        ok = ~np.isnan(scores[u]) & pool[u]
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        x = scores[u, ok]
+        count[u] = x.size
+        if x.size == 0:
+            continue
+        smax[u] = x.max()
+        if not tau_ok[u] or not np.isfinite(smax[u]):
+            logsum[u] = np.nan
+        else:
+            logsum[u] = np.log(np.sum(np.exp((x - smax[u]) / tau[u])))
+    return logsum, smax, count
+
+
+def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
+    """Host statement of the row log-probability contract (include/nrhip.h, nr_row_logprob); tests check the device against it,
+    no product path calls it.
+
+    `a`, `b` and the pools are topk_reference's.  row_ids [U, k] integers; base = (logsum [U], smax [U]), the first two results
+    of logz_reference (or of the device) for these users.  With s_i the score (+ prior) of entry i, in float64:
+      sequential: out[u, j] = (s_j - M_j) / tau - L_j,  M_j = max(smax, max_{i >= j} s_i),
+                  L_j = log(exp((smax - M_j) / tau + logsum) + sum_{i >= j} exp((s_i - M_j) / tau)) -- Plackett-Luce without
+                  replacement; the base must have been formed WITHOUT the row's ids (pass them in `exclude` of logz_reference)
+      otherwise:  out[u, j] = (s_j - smax) / tau - logsum, the base formed over everything eligible, the entries included.
+    An entry that is 0 or outside [1, V) is fill: 0, part of no sum.  An entry outside the pool or with a NaN score gives NaN and
+    is part of no sum.  A temperature that is not finite and > 0 gives NaN for the real entries of that user.  Membership in an
+    exclusion list and repeats are the caller's statement and are not checked.
+    Returns (logp float64 [U, k], total float64 [U] = the row sums)."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    ids = np.asarray(row_ids, dtype=np.int64).reshape(U, -1)
+    k = ids.shape[1]
+    tau, tau_ok = _temperatures(temperature, U)
+    bl, bm = np.asarray(base[0], dtype=np.float64).reshape(U), np.asarray(base[1], dtype=np.float64).reshape(U)
+    out = np.zeros((U, k), dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for u in range(U):
+            real = (ids[u] >= 1) & (ids[u] < V)
+            at = np.where(real, ids[u], 0)
+            s = scores[u, at]
+            live = real & pool[u, at] & ~np.isnan(s)
+            for j in range(k):
+                if not real[j]:
+                    continue
+                if not live[j] or not tau_ok[u]:
+                    out[u, j] = np.nan
+                elif sequential:
+                    rest = s[j:][live[j:]]
+                    M = max(bm[u], rest.max())
+                    mass = np.sum(np.exp((rest - M) / tau[u]))
+                    if bm[u] > -np.inf or np.isnan(bl[u]):
+                        mass = mass + np.exp((bm[u] - M) / tau[u] + bl[u])
+                    out[u, j] = (s[j] - M) / tau[u] - np.log(mass)
+                else:
+                    out[u, j] = (s[j] - bm[u]) / tau[u] - bl[u]
+    return out, out.sum(axis=1)
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

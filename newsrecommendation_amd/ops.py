@@ -1298,6 +1298,114 @@ def sample_noise(seed, draw, user_keys, news_ids):
     return g, bits.to(torch.int64) & 0xFFFFFFFF
 
 
+def _vector_args(what, news_vecs, user_vecs):
+    """The shape checks score_logz / row_logprob share with score_topk; returns (V, N, U, device)."""
+    for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"{what}: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
+                               f"strides {tuple(t.stride())}")
+    V, N = news_vecs.shape
+    U = user_vecs.shape[0]
+    if user_vecs.shape[1] != N:
+        raise RuntimeError(f"{what}: vector widths differ ({N} vs {user_vecs.shape[1]})")
+    return V, N, U, news_vecs.device
+
+
+def _tau_args(what, temperature, U, dev):
+    """`temperature` as (scalar, [U] fp32 tensor or None) of a descriptor."""
+    if not isinstance(temperature, torch.Tensor):
+        return float(temperature), None
+    if tuple(temperature.shape) != (U,) or not temperature.is_floating_point() or temperature.device != dev:
+        raise RuntimeError(f"{what}: a temperature tensor must be floating point of shape ({U},) on {dev}, got {tuple(temperature.shape)} "
+                           f"{temperature.dtype} on {temperature.device}")
+    return 0.0, temperature.detach().to(torch.float32).contiguous()
+
+
+@torch.no_grad()
+def score_logz(news_vecs, user_vecs, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """Full-corpus log-partition (nr_score_logz; include/nrhip.h, K13): per user log sum_v exp(score(u, v) / temperature) over
+    exactly the news score_topk / score_sample call eligible -- same score bits fl32(dot + prior), same pools, same lists --
+    without the [U, V] score matrix.  Returns (logsum fp32 [U], smax fp32 [U], count int32 [U]): smax is the largest eligible
+    score (score_topk's k = 1 score, bit for bit; -inf when nothing is eligible), count the number of eligible news, and
+    logsum = log sum_v exp((score - smax) / temperature) >= 0, so that log Z = smax / temperature + logsum and
+    log p(v) = (score_v - smax) / temperature - logsum.  Nothing eligible: (-inf, -inf, 0).
+    `temperature`: a float (finite, > 0) or a floating point tensor [U]; a tensor entry that is <= 0, NaN or infinite gives that
+    user logsum = NaN and leaves its smax and count, and everybody else, as they are.
+    `exclude`: None, an ExclusionLists, or an integer tensor [U, E] of any width (converted to an ExclusionLists: this call
+    knows the CSR lists only).  The listed news are left out inside the stream, not subtracted afterwards.
+    `splits`: 0 = the library chooses the number of corpus slices; the three results do not depend on it, bit for bit, nor on
+    which users share the call."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t)
+    V, N, U, dev = _vector_args("score_logz", news_vecs, user_vecs)
+    logsum = torch.empty(U, dtype=torch.float32, device=dev)
+    smax = torch.empty(U, dtype=torch.float32, device=dev)
+    count = torch.empty(U, dtype=torch.int32, device=dev)
+    if U == 0:
+        return logsum, smax, count
+    if isinstance(exclude, torch.Tensor):
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"score_logz: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        exclude = ExclusionLists(exclude)
+    if exclude is not None:
+        if not isinstance(exclude, ExclusionLists):
+            raise RuntimeError(f"score_logz: exclude must be a tensor [U, E] or an ExclusionLists, got {type(exclude)}")
+        if exclude.U != U or exclude.device != dev:
+            raise RuntimeError(f"score_logz: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
+    n_excl = 0 if exclude is None else exclude.ids.numel()
+    pr, st, win = _pool_args("score_logz", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("score_logz", temperature, U, dev)
+    d = _lib.LogzDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits),
+                      excl_offsets=ptr(exclude.offsets) if exclude is not None else None, excl_ids=ptr(exclude.ids) if n_excl else None,
+                      n_excl=n_excl, tau=tau, tau_u=ptr(tau_u), out_logsum=ptr(logsum), out_max=ptr(smax), out_count=ptr(count),
+                      prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_logz_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_logz(C.byref(d), _stream()), "nr_score_logz")
+    return logsum, smax, count
+
+
+@torch.no_grad()
+def row_logprob(news_vecs, user_vecs, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
+    """Log-probabilities of the entries of named rows (nr_row_logprob; include/nrhip.h, K14).  `row_ids`: integer tensor
+    [U, k <= 128], 0 (or anything outside [1, V)) = fill.  `base` = (logsum, smax) -- the first two results of score_logz for
+    these users, pools and temperatures (a third element, the count, is ignored).
+    sequential=True: the row as a draw without replacement (Plackett-Luce, the law of score_sample): entry j against the base
+    and the entries j .. k-1.  The base must then have been computed WITHOUT the row's ids (merge them into `exclude` of
+    score_logz).  sequential=False: every entry on its own against the base, which must then cover everything eligible, the
+    entries included: the full-softmax log-probability of a held-out click.
+    Returns (logp fp32 [U, k], total fp32 [U] = the row's sum, formed in fp64): fill entries give 0; an entry outside the pool
+    or with a NaN score gives NaN; a bad entry of a temperature tensor gives its user's real entries NaN.  Whether an entry is
+    in the user's exclusion lists, and repeats within a row, are the caller's statement and are not checked."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, row_ids, prior, stamp, window, tau_t, base[0], base[1])
+    V, N, U, dev = _vector_args("row_logprob", news_vecs, user_vecs)
+    if row_ids.dim() != 2 or row_ids.shape[0] != U or row_ids.is_floating_point() or row_ids.device != dev:
+        raise RuntimeError(f"row_logprob: row_ids must be an integer tensor [U = {U}, k] on {dev}, got {tuple(row_ids.shape)} {row_ids.dtype} "
+                           f"on {row_ids.device}")
+    k = row_ids.shape[1]
+    logp = torch.empty(U, k, dtype=torch.float32, device=dev)
+    total = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return logp, total
+    bl, bm = base[0], base[1]
+    for name, t in (("base logsum", bl), ("base smax", bm)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
+            raise RuntimeError(f"row_logprob: {name} must be a floating point tensor of shape ({U},) on {dev}")
+    bl, bm = bl.detach().to(torch.float32).contiguous(), bm.detach().to(torch.float32).contiguous()
+    ids = row_ids.detach().to(torch.int32).contiguous()
+    pr, st, win = _pool_args("row_logprob", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("row_logprob", temperature, U, dev)
+    d = _lib.LogprobDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                         ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=k, row_ids=ptr(ids), ld_ids=k,
+                         sequential=1 if sequential else 0, tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl),
+                         out_logp=ptr(logp), out_total=ptr(total), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
+                         ld_window=2 if win is not None else 0)
+    check(_lib.lib().nr_row_logprob(C.byref(d), _stream()), "nr_row_logprob")
+    return logp, total
+
+
 @torch.no_grad()
 def mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, group=None, group_cap=None):
     """Diversified re-ranking of a pool (nr_mmr_select; include/nrhip.h, K11): Maximal Marginal Relevance over the M places of

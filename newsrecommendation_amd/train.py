@@ -398,6 +398,107 @@ def recommend_sample(model, news_vecs, hist_idx, mask, k, temperature, seed, dra
     return ids, model_scores
 
 
+def _device_temperature(temperature, U, device):
+    """A temperature as ops.score_logz / ops.row_logprob take it.  A scalar that is not finite and > 0 (0 above all: a
+    deterministic row) becomes a [U] tensor of it, so that the answer is NaN for everybody instead of a refusal."""
+    if isinstance(temperature, torch.Tensor):
+        return temperature.to(device=device, dtype=torch.float32)
+    t = float(temperature)
+    return t if 0.0 < t < float("inf") else torch.full((U,), t, dtype=torch.float32, device=device)
+
+
+@torch.no_grad()
+def log_partition(model, news_vecs, hist_idx, mask, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None,
+                  seen=None):
+    """The log-partition of every user's full-corpus score row at `temperature` (ops.score_logz; include/nrhip.h, K13), over
+    exactly the news recommend / recommend_sample would consider for that user under the same arguments: the user vectors,
+    exclude_history, seen, prior, news_time and window are recommend's.  No [U, V] score matrix is formed.
+    Returns (logsum fp32 [U], smax fp32 [U], count int32 [U]) on the device: smax is the best eligible score (recommend's first
+    score, bit for bit), count the number of eligible news, logsum = log sum exp((score - smax) / temperature), so that
+    log Z = smax / temperature + logsum and the softmax log-probability of an eligible news is
+    (score - smax) / temperature - logsum.  temperature: a float or a [U] tensor, finite and > 0; a tensor entry that is not
+    gives that user logsum = NaN."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    return ops.score_logz(news_vecs, user, _device_temperature(temperature, user.shape[0], news_vecs.device), exclude=exclude, **kw)
+
+
+@torch.no_grad()
+def sample_propensity(model, news_vecs, hist_idx, mask, ids, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
+                      window=None, news_group=None, group_cap=None, seen=None):
+    """The probability with which recommend_sample drew its rows: for ids [U, k] returned by recommend_sample called with the
+    SAME model, histories, temperature, exclusions and pools, logp[u, j] = log P(entry j is drawn at step j | entries 0 .. j-1
+    are taken) under the Plackett-Luce law the rows follow, and total[u] = their sum = log P(the row, in this order) -- what a
+    click log of served rows is reweighted by (inverse propensity weighting, off-policy evaluation).
+    Two fused passes, no [U, V] matrix: the log-partition over everything eligible EXCEPT the row (ops.score_logz with the row
+    merged into the exclusion lists: the row's entries are usually the heaviest terms, so they are left out of the stream rather
+    than subtracted), then the row itself on top of that base, step by step, in fp64 (ops.row_logprob, sequential).
+    Returns (logp fp32 [U, k], total fp32 [U]) on the device.  Fill entries (id 0, a short row) give 0.  temperature 0 -- as a
+    float or as an entry of a [U] tensor -- gives NaN: such a row is recommend's, deterministic, its propensity is 1 and there
+    is nothing to reweight by.  Seed, draw and user keys do not enter: the law does not depend on them.
+    Group caps are not supported: under caps the mass that is left at a step needs per-group partitions.  Passing news_group or
+    group_cap raises ValueError."""
+    if news_group is not None or group_cap is not None:
+        raise ValueError("sample_propensity: rows drawn under group caps (news_group / group_cap) have no propensity here: "
+                         "the remaining mass under caps needs per-group partitions")
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    device = news_vecs.device
+    U = user.shape[0]
+    rows = torch.as_tensor(ids).to(device=device, dtype=torch.int32)
+    if rows.dim() != 2 or rows.shape[0] != U:
+        raise RuntimeError(f"sample_propensity: ids must be [U = {U}, k], got {tuple(rows.shape)}")
+    taken = ops.ExclusionLists(rows)
+    lists = taken if exclude is None else (exclude if isinstance(exclude, ops.ExclusionLists) else ops.ExclusionLists(exclude)).merged(taken)
+    tau = _device_temperature(temperature, U, device)
+    base = ops.score_logz(news_vecs, user, tau, exclude=lists, **kw)
+    return ops.row_logprob(news_vecs, user, rows, tau, base, True, **kw)
+
+
+def _in_lists(exclude, tg):
+    """[U, T] bool: is tg[u, j] in user u's exclusion list (None, a dense tensor [U, E] or an ops.ExclusionLists)?"""
+    if exclude is None:
+        return torch.zeros_like(tg, dtype=torch.bool)
+    lists = exclude if isinstance(exclude, ops.ExclusionLists) else ops.ExclusionLists(exclude)
+    users, ids = lists._pairs()
+    if ids.numel() == 0:
+        return torch.zeros_like(tg, dtype=torch.bool)
+    keys = (users << 31) + ids                            # ascending: users ascend, each segment ascends
+    q = (torch.arange(tg.shape[0], device=tg.device, dtype=torch.int64)[:, None] << 31) + tg.to(torch.int64).clamp(min=0)
+    at = torch.searchsorted(keys, q.contiguous()).clamp(max=keys.numel() - 1)
+    return keys[at] == q
+
+
+@torch.no_grad()
+def target_logprob(model, news_vecs, hist_idx, mask, targets, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
+                   window=None, seen=None):
+    """The full-softmax log-probability of held-out clicks, the rank-side counterpart of sample_propensity: for targets [U, T]
+    (0 = no entry), logp[u, j] = (score - smax) / temperature - logsum over the user's WHOLE eligible row (log_partition under
+    the same arguments; ops.row_logprob, independent entries, in fp64 on rank_eval's score bits).  The arguments are rank_eval's;
+    the result is NaN exactly where rank_eval gives rank 0: an entry that is 0 or out of range, excluded (history or seen),
+    outside the pool, NaN-scored, or a repeat of an earlier entry of its row.  -nansum of it is the full-corpus negative
+    log-likelihood, next to rank_eval's MRR and nDCG.  Returns logp fp32 [U, T] on the device."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    device = news_vecs.device
+    U, V = user.shape[0], news_vecs.shape[0]
+    tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
+    if tg.dim() != 2 or tg.shape[0] != U:
+        raise RuntimeError(f"target_logprob: targets must be [U = {U}, T], got {tuple(tg.shape)}")
+    tau = _device_temperature(temperature, U, device)
+    base = ops.score_logz(news_vecs, user, tau, exclude=exclude, **kw)
+    W = _lib.NR_TOPK_MAX_K
+    logp = torch.cat([ops.row_logprob(news_vecs, user, tg[:, c:c + W].contiguous(), tau, base, False, **kw)[0] for c in range(0, tg.shape[1], W)],
+                     dim=1) if tg.shape[1] else torch.empty(U, 0, dtype=torch.float32, device=device)
+    # what rank_eval does not rank and the kernel does not look at: fill, a listed news, a later repeat (stable sort by id: the
+    # first of equal ids is the earliest entry)
+    srt, at = torch.sort(tg, dim=1, stable=True)
+    rep = torch.zeros_like(tg, dtype=torch.bool)
+    rep[:, 1:] = srt[:, 1:] == srt[:, :-1]
+    not_ranked = (tg < 1) | (tg >= V) | _in_lists(exclude, tg) | torch.zeros_like(rep).scatter(1, at, rep)
+    return logp.masked_fill(not_ranked, float("nan"))
+
+
 def _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window, news_group, group_cap, seen):
     """What recommend and recommend_diverse share: the fp32 table, the user vectors, the exclusions, the pool keywords and the
     cap keywords (group / group_cap; what is None is left out) of ops.score_topk."""
