@@ -50,12 +50,6 @@ __global__ __launch_bounds__(256) void assemble_kernel(const int32_t* __restrict
 // ------------------------------------------------------------------------------------------ ranking metrics
 constexpr int MET_MAXC = 4096;   // candidates of one impression held in LDS
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One wave per impression.  Descending rank of candidate i with ties broken towards the LATER index first -- the order of
 // np.argsort(score, kind="stable")[::-1]; numpy's default sort (src/metrics.py:6,20) leaves the order of tied scores
 // unspecified, any of them is "the reference's".  AUC is the Mann-Whitney statistic with half credit for ties, which is

@@ -20,7 +20,7 @@
 //   logz_final_kernel       one wave per user, four partials a lane: maximum of the partials (exact), then their sums rescaled to
 //                           it and added in fp64 in a fixed order (the lane's segments ascending, then an xor butterfly), one
 //                           log, rounded to fp32 once.
-//   logp_rows_kernel<POOL>  the named-row gather of rank_named_kernel: one workgroup per 16 users, chunk c = the k <= 128 rows user
+//   logp_rows_kernel<POOL>  the named-row gather of rank_named_kernel (ScoreNamedRows, nr_score_tile.h): one workgroup per 16 users, chunk c = the k <= 128 rows user
 //                           c names, so the entries get the stream's score bits.  Then one wave per user finishes in fp64: a
 //                           suffix scan of (max, sum) pairs over the row joined with the user's base partition (sequential =
 //                           Plackett-Luce without replacement; only positive terms are added), or each entry against the base
@@ -34,28 +34,18 @@ namespace {
 constexpr int LZ_MAX_SEGS = 256;
 constexpr float LZ_INF = __builtin_inff();
 
-// the tile is what the vectors and the staging buffers leave room for, as in the counting pass of nr_rank.hip
-inline size_t lz_lds_bytes(int TU, int N) { return tk_tile_floats(TU, N) * sizeof(float); }
-inline int lz_user_tile(int N) {
-  for (int tu = 64; tu > 16; tu >>= 1)
-    if (lz_lds_bytes(tu, N) <= TK_LDS_MAX) return tu;
-  return 16;
-}
 struct LogzPlan {
   int TU, seg, nseg, splits, segs_per;
 };
-// seg and nseg depend on V alone; `splits` (0: fill the chip, as rk_auto_splits does) only groups whole segments into slices
+// The tile is what the vectors and the staging buffers leave room for, as in the counting pass of nr_rank.hip.  seg and nseg
+// depend on V alone; `splits` (0: fill the chip, score_auto_splits) only groups whole segments into slices
 inline LogzPlan lz_plan(int U, int V, int N, int splits) {
   LogzPlan p;
-  p.TU = lz_user_tile(N);
+  p.TU = score_user_tile(N, 0);
   const long per = (long)TK_ROWS * LZ_MAX_SEGS;
   p.seg = TK_ROWS * (int)(((long)V - 1 + per - 1) / per);
   p.nseg = (int)(((long)V - 1 + p.seg - 1) / p.seg);
-  long s = splits;
-  if (s <= 0) {
-    const long tiles = ((long)U + p.TU - 1) / p.TU;
-    s = (TK_CUS + tiles - 1) / tiles;
-  }
+  long s = splits > 0 ? splits : score_auto_splits(U, V, p.TU, LZ_MAX_SEGS);   // nseg <= chunks, nseg <= LZ_MAX_SEGS
   if (s > p.nseg) s = p.nseg;
   if (s < 1) s = 1;
   p.segs_per = (int)((p.nseg + s - 1) / s);
@@ -86,12 +76,6 @@ inline size_t lz_carve(void* ws, int U, int nseg, LogzArgs* a) {
     a->pc = reinterpret_cast<int32_t*>(p + n * 8);
   }
   return (n * 12 + 7) & ~(size_t)7;
-}
-
-__device__ __forceinline__ int lz_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // One eligible news x into a lane's running (m, s): s = sum of exp((x_i - m) * it) over what the lane has seen, m their maximum.
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(TK_THREADS) void logz_stream_kernel(LogzArgs a, Csr
         const float M = wave_max(m[i]);
         const float sc = m[i] == M ? 1.f : expf((m[i] - M) * it[i]);
         const float S = wave_sum(s[i] * sc);
-        const int C = lz_wave_sum_i(cnt[i]);
+        const int C = wave_sum_i(cnt[i]);
         if (lane == 0 && u < a.U) {
           a.pm[(size_t)u * a.nseg + sg] = M;
           a.ps[(size_t)u * a.nseg + sg] = S;
@@ -276,12 +260,6 @@ __global__ __launch_bounds__(TK_THREADS) void logz_stream_kernel(LogzArgs a, Csr
     }
     __syncthreads();                                          // the score tile is the next chunk's staging buffer
   }
-}
-
-__device__ __forceinline__ double lz_wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // One wave per user; lane l holds the partials of segments l, l + 64, l + 128, l + 192 (nseg <= 256).
@@ -306,7 +284,7 @@ __global__ __launch_bounds__(256) void logz_final_kernel(LogzArgs a, float* __re
     M = fmaxf(M, mj[q]);
   }
   M = wave_max(M);
-  n = lz_wave_sum_i(n);
+  n = wave_sum_i(n);
   const float tau = a.tau_of(u);
   const bool tau_ok = tau > 0.f && tau < LZ_INF;
   float ls;
@@ -319,7 +297,7 @@ __global__ __launch_bounds__(256) void logz_final_kernel(LogzArgs a, float* __re
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (mj[q] != -LZ_INF) S += (double)sj[q] * (mj[q] == M ? 1.0 : exp(((double)mj[q] - (double)M) * it));
-    ls = (float)log(lz_wave_sum_d(S));
+    ls = (float)log(wave_sum_d(S));
   }
   if (lane == 0) {
     out_logsum[u] = ls;
@@ -345,18 +323,6 @@ struct LogpArgs {
   float* out_total;         // [U] or null
 };
 
-// chunk row r = table row ids[r]; an id outside [1, V) is a row of zeros (its score is never looked at)
-struct LogpNamedRows {
-  const float* news;
-  size_t ld;
-  const int32_t* ids;   // LDS, [128]
-  int V;
-  __device__ __forceinline__ const float* operator()(int r) const {
-    const int32_t id = ids[r];
-    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
-  }
-};
-
 // (m, s): s = sum of exp((x_i - m) / tau) over a set with maximum m; (-inf, 0) is the empty set
 struct LogpPair {
   double m, s;
@@ -367,11 +333,6 @@ __device__ __forceinline__ LogpPair lp_join(LogpPair x, LogpPair y, double tau) 
   return {M, x.s * ex + y.s * ey};
 }
 __device__ __forceinline__ LogpPair lp_down(LogpPair x, int o) { return {__shfl_down(x.m, o, 64), __shfl_down(x.s, o, 64)}; }
-__device__ __forceinline__ double lp_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <bool POOL>
 __global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
@@ -390,7 +351,7 @@ __global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
   }
   __syncthreads();
 
-  LogpNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  ScoreNamedRows rows = {a.news, a.ld_news, sIds, a.V};
   t.load_slab(rows, 0);
   for (int c = 0; c < users; ++c) {
     f32x4 acc[1];
@@ -466,7 +427,7 @@ __global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
     if (j0 < a.k) a.out_logp[u * a.k + j0] = (float)lp0;
     if (j1 < a.k) a.out_logp[u * a.k + j1] = (float)lp1;
     if (a.out_total != nullptr) {
-      const double tot = lp_wave_sum(lp0 + lp1);              // entries beyond k are fill: 0
+      const double tot = wave_sum_d(lp0 + lp1);              // entries beyond k are fill: 0
       if (lane == 0) a.out_total[u] = (float)tot;
     }
   }
@@ -475,24 +436,25 @@ __global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
 // argument checks shared by the size query and the call; 0 = fine
 int logz_check(const nr_logz_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_logz: null descriptor");
-  NR_CHECK_ARG(d->V >= 2, "score_logz: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
-  NR_CHECK_ARG(d->U >= 1, "score_logz: U = %d users", d->U);
-  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_logz: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
-               NR_TOPK_MAX_N);
-  NR_CHECK_ARG(d->n_excl >= 0, "score_logz: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
-               "score_logz: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
-               "score_logz: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_RC(check_vectors("score_logz", d->V, d->U, d->N));
+  NR_CHECK_RC(check_lists("score_logz", 0, d->excl_offsets, d->excl_ids, d->n_excl));   // this call has no dense list
   NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LZ_INF), "score_logz: tau = %g, a scalar temperature must be finite and > 0",
                (double)d->tau);
   const int nseg = lz_plan(d->U, d->V, d->N, 1).nseg;
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= nseg, "score_logz: splits = %d, must be 0 (library's choice) or in [1, %d], the segments of V = %d",
                d->splits, nseg, d->V);
-  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_logz: stamp given without window (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_logz: window given without stamp (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_logz: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
-  return NR_OK;
+  return check_pools("score_logz", d->stamp, d->window, d->ld_window);
+}
+
+// the stream's instantiation for the run-time (tile, pool, lists)
+int logz_stream_launch(int TU, bool pool, bool lists, dim3 grid, size_t smem, hipStream_t s, const LogzArgs& a, const CsrArgs& ca) {
+  return with_int<64, 32, 16>(TU, [&](auto tu) {
+    return with_bool(pool, [&](auto p) {
+      return with_bool(lists, [&](auto l) {
+        return launch_lds(logz_stream_kernel<decltype(tu)::value / 16, decltype(p)::value, decltype(l)::value>, grid, dim3(TK_THREADS), smem, s, a, ca);
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -505,16 +467,11 @@ size_t nr_score_logz_workspace_bytes(const nr_logz_desc* d) {
 }
 
 int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream) {
-  const int rc = logz_check(d);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(logz_check(d));
   NR_CHECK_ARG(d->news_vecs && d->user && d->out_logsum && d->out_max && d->out_count,
                "score_logz: null pointer (news_vecs, user, out_logsum, out_max, out_count)");
-  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
-                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
-               "score_logz: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
-  const size_t need = nr_score_logz_workspace_bytes(d);
-  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
-               "score_logz: workspace holds %zu bytes, nr_score_logz_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_CHECK_RC(check_rows("score_logz", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
+  NR_CHECK_RC(check_workspace("score_logz", d->ws, d->ws_bytes, nr_score_logz_workspace_bytes(d)));
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
   const LogzPlan pl = lz_plan(d->U, d->V, d->N, d->splits);
@@ -522,35 +479,16 @@ int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream) {
   a.news = d->news_vecs; a.user = d->user;
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user;
   a.V = d->V; a.U = d->U; a.N = d->N; a.seg = pl.seg; a.nseg = pl.nseg; a.segs_per = pl.segs_per;
-  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
   a.tau = d->tau; a.tau_u = d->tau_u;
   lz_carve(d->ws, d->U, pl.nseg, &a);
-  const bool pool = a.pool.any();
-  const bool lists = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
-  const CsrArgs ca = {lists ? d->excl_offsets : nullptr, lists ? d->excl_ids : nullptr, lists ? d->n_excl : 0};
+  const CsrArgs ca = csr_args(d->excl_offsets, d->excl_ids, d->n_excl);
   {
     const int TU = pl.TU;
-    const size_t smem = lz_lds_bytes(TU, d->N);
+    const size_t smem = tk_tile_bytes(TU, d->N);
     const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)pl.splits);
     NrProfScope ps(s, "logz_stream[U=%d,V=%d,N=%d,TU=%d,splits=%d,seg=%d]", d->U, d->V, d->N, TU, pl.splits, pl.seg);
-#define NR_LOGZ_LAUNCH(MT, POOL, LISTS)                                                                                       \
-  do {                                                                                                                        \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(logz_stream_kernel<MT, POOL, LISTS>),                      \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                 \
-    hipLaunchKernelGGL((logz_stream_kernel<MT, POOL, LISTS>), grid, dim3(TK_THREADS), smem, s, a, ca);                        \
-  } while (0)
-#define NR_LOGZ_LAUNCH_MT(MT)                       \
-  do {                                              \
-    if (pool && lists) NR_LOGZ_LAUNCH(MT, true, true);   \
-    else if (pool) NR_LOGZ_LAUNCH(MT, true, false);      \
-    else if (lists) NR_LOGZ_LAUNCH(MT, false, true);     \
-    else NR_LOGZ_LAUNCH(MT, false, false);               \
-  } while (0)
-    if (TU == 64) NR_LOGZ_LAUNCH_MT(4);
-    else if (TU == 32) NR_LOGZ_LAUNCH_MT(2);
-    else NR_LOGZ_LAUNCH_MT(1);
-#undef NR_LOGZ_LAUNCH_MT
-#undef NR_LOGZ_LAUNCH
+    NR_CHECK_RC(logz_stream_launch(TU, a.pool.any(), ca.offsets != nullptr, grid, smem, s, a, ca));
   }
   NR_CHECK_LAUNCH();
   {
@@ -564,21 +502,14 @@ int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream) {
 int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream) {
   NR_CHECK_ARG(d != nullptr, "row_logprob: null descriptor");
   NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "row_logprob: k = %d entries per row, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
-  NR_CHECK_ARG(d->V >= 2, "row_logprob: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
-  NR_CHECK_ARG(d->U >= 1, "row_logprob: U = %d users", d->U);
-  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "row_logprob: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
-               NR_TOPK_MAX_N);
+  NR_CHECK_RC(check_vectors("row_logprob", d->V, d->U, d->N));
   NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LZ_INF), "row_logprob: tau = %g, a scalar temperature must be finite and > 0",
                (double)d->tau);
   NR_CHECK_ARG(d->sequential == 0 || d->sequential == 1, "row_logprob: sequential = %d, must be 0 or 1", d->sequential);
-  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "row_logprob: stamp given without window (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "row_logprob: window given without stamp (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "row_logprob: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_RC(check_pools("row_logprob", d->stamp, d->window, d->ld_window));
   NR_CHECK_ARG(d->news_vecs && d->user && d->row_ids && d->base_max && d->base_logsum && d->out_logp,
                "row_logprob: null pointer (news_vecs, user, row_ids, base_max, base_logsum, out_logp)");
-  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
-                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
-               "row_logprob: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_RC(check_rows("row_logprob", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
   NR_CHECK_ARG(d->ld_ids >= d->k, "row_logprob: id row stride %d < k = %d", d->ld_ids, d->k);
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
@@ -586,17 +517,15 @@ int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream) {
   a.news = d->news_vecs; a.user = d->user; a.ids = d->row_ids;
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_ids = (size_t)d->ld_ids;
   a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.sequential = d->sequential;
-  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
   a.tau = d->tau; a.tau_u = d->tau_u;
   a.base_max = d->base_max; a.base_logsum = d->base_logsum;
   a.out_logp = d->out_logp; a.out_total = d->out_total;
-  const bool pool = a.pool.any();
   NrProfScope ps(s, "logp_rows[U=%d,N=%d,k=%d,seq=%d]", d->U, d->N, d->k, d->sequential);
-  const size_t smem = lz_lds_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
-  const void* fn = pool ? reinterpret_cast<const void*>(logp_rows_kernel<true>) : reinterpret_cast<const void*>(logp_rows_kernel<false>);
-  NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  if (pool) hipLaunchKernelGGL(logp_rows_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
-  else hipLaunchKernelGGL(logp_rows_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
+  NR_CHECK_RC(with_bool(a.pool.any(), [&](auto p) {
+    return launch_lds(logp_rows_kernel<decltype(p)::value>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  }));
   NR_CHECK_LAUNCH();
   return NR_OK;
 }

@@ -231,8 +231,7 @@ int mmr_check(const nr_mmr_desc* d) {
   NR_CHECK_ARG(d->k >= 1 && d->k <= d->M, "mmr_select: k = %d, must be in [1, M = %d]", d->k, d->M);
   NR_CHECK_ARG(d->U >= 0, "mmr_select: U = %d users", d->U);
   NR_CHECK_ARG(d->V >= 1, "mmr_select: V = %d news rows", d->V);
-  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "mmr_select: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
-               NR_TOPK_MAX_N);
+  NR_CHECK_RC(check_width("mmr_select", d->N));
   NR_CHECK_ARG(d->penalty >= 0.f && d->penalty <= 3.402823466e38f, "mmr_select: penalty = %g, must be finite and >= 0",
                (double)d->penalty);
   NR_CHECK_ARG(d->group == nullptr || (d->group_cap >= 1 && d->group_cap <= NR_TOPK_MAX_K),
@@ -252,8 +251,7 @@ int mmr_check(const nr_mmr_desc* d) {
 extern "C" {
 
 int nr_mmr_select(const nr_mmr_desc* d, nr_stream_t stream) {
-  const int rc = mmr_check(d);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(mmr_check(d));
   if (d->U == 0) return NR_OK;
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
@@ -266,17 +264,9 @@ int nr_mmr_select(const nr_mmr_desc* d, nr_stream_t stream) {
   const size_t smem = mm_lds_bytes(MB);
   {
     NrProfScope ps(s, "mmr_select[U=%d,N=%d,M=%d,k=%d]", d->U, d->N, d->M, d->k);
-#define NR_MMR_LAUNCH(MBV)                                                                                                              \
-  do {                                                                                                                                  \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mmr_select_kernel<MBV>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int)smem));                                                                                       \
-    hipLaunchKernelGGL((mmr_select_kernel<MBV>), dim3((unsigned)d->U), dim3(MM_THREADS), smem, s, a);                                   \
-  } while (0)
-    if (MB == 1) NR_MMR_LAUNCH(1);
-    else if (MB == 2) NR_MMR_LAUNCH(2);
-    else if (MB == 3) NR_MMR_LAUNCH(3);
-    else NR_MMR_LAUNCH(4);
-#undef NR_MMR_LAUNCH
+    NR_CHECK_RC(with_int<1, 2, 3, 4>(MB, [&](auto mb) {
+      return launch_lds(mmr_select_kernel<decltype(mb)::value>, dim3((unsigned)d->U), dim3(MM_THREADS), smem, s, a);
+    }));
   }
   NR_CHECK_LAUNCH();
   return NR_OK;

@@ -46,8 +46,6 @@
 //                           else rank = uncapped - sum_g max(0, n_g - c); the metric terms as in rank_final_kernel.
 #include <math.h>
 
-#include <type_traits>
-
 #include "nr_score_tile.h"
 
 namespace {
@@ -56,13 +54,8 @@ constexpr int RK_SLOTS = NR_RANK_MAX_TARGETS;     // chunk rows 0 .. 63: targets
 constexpr int RK_MAX_SPLITS = 256;
 static_assert(NR_RANK_MAX_TARGETS == 64 && NR_TOPK_MAX_EXCLUDE == 64 && TK_ROWS == 128, "one lane per target and per excluded id");
 
-inline size_t rk_lds_bytes(int TU, int N) { return tk_tile_floats(TU, N) * sizeof(float); }
 // keys and counters of the counting pass live in registers: the tile is what the vectors and the staging buffers leave room for
-inline int rk_user_tile(int N) {
-  for (int tu = 64; tu > 16; tu >>= 1)
-    if (rk_lds_bytes(tu, N) <= TK_LDS_MAX) return tu;
-  return 16;
-}
+inline int rk_user_tile(int N) { return score_user_tile(N, 0); }
 // group caps: blocks of 64 groups as the counting pass instantiates them (1, 2, 4, 8), and the user tile whose per-wave counters
 // (TU / 8 users x 4 targets x blocks) are 64 registers or fewer
 inline int rk_group_blocks(int G) {
@@ -72,22 +65,6 @@ inline int rk_group_blocks(int G) {
 inline int rk_group_user_tile(int N, int G) {
   const int tu = rk_user_tile(N), gb = rk_group_blocks(G), most = gb <= 2 ? 64 : gb == 4 ? 32 : 16;
   return tu < most ? tu : most;
-}
-inline int rk_auto_splits(int U, int V, int N, int tile = 0) {
-  if (tile > 0) {
-    const long tiles = ((long)U + tile - 1) / tile;
-    long s = (TK_CUS + tiles - 1) / tiles;
-    const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
-    if (s > chunks) s = chunks;
-    if (s > RK_MAX_SPLITS) s = RK_MAX_SPLITS;
-    return s < 1 ? 1 : (int)s;
-  }
-  const long tiles = ((long)U + rk_user_tile(N) - 1) / rk_user_tile(N);
-  long s = (TK_CUS + tiles - 1) / tiles;
-  const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
-  if (s > chunks) s = chunks;
-  if (s > RK_MAX_SPLITS) s = RK_MAX_SPLITS;
-  return s < 1 ? 1 : (int)s;
 }
 
 // workspace: 8-byte arrays first
@@ -132,6 +109,11 @@ struct GroupArgs {
 struct NoGroupArgs {};
 template <bool GROUP>
 using GroupArgsIf = typename std::conditional<GROUP, GroupArgs, NoGroupArgs>::type;
+template <bool GROUP>
+GroupArgsIf<GROUP> group_args_if(const GroupArgs& ga) {
+  if constexpr (GROUP) return ga;
+  else return {};
+}
 inline GroupArgs rk_group_carve(void* ws, size_t at, int U, int T, int G, int splits, int cps, size_t* end) {
   GroupArgs g = {};
   char* p = reinterpret_cast<char*>(ws) + ((at + 7) & ~(size_t)7);
@@ -153,35 +135,6 @@ struct RankArgs {
   size_t ld_news, ld_user, ld_tgt, ld_excl;
   int V, U, N, T, E, splits, per;
   PoolArgs pool;        // read by the POOL instantiations only
-};
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// lane j's 64-bit value, j the same in every lane
-__device__ __forceinline__ u64 lane_u64(u64 v, int j) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 news_key(float score, uint32_t id) { return ((u64)score_key(score) << 32) | (uint32_t)~id; }
-
-// chunk row r = table row ids[r]; an id outside [1, V) is a row of zeros (its score is never looked at)
-struct RankNamedRows {
-  const float* news;
-  size_t ld;
-  const int32_t* ids;   // LDS, [128]
-  int V;
-  __device__ __forceinline__ const float* operator()(int r) const {
-    const int32_t id = ids[r];
-    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
-  }
 };
 
 // POOL (both kernels): the call has a prior and / or stamps + windows; every key then comes from pool_key (nr_score_tile.h), as
@@ -208,7 +161,7 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a, Grou
   }
   __syncthreads();
 
-  RankNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  ScoreNamedRows rows = {a.news, a.ld_news, sIds, a.V};
   t.load_slab(rows, 0);
   for (int c = 0; c < users; ++c) {
     f32x4 acc[1];
@@ -247,22 +200,20 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_kernel(RankArgs a, Grou
       const u64 mask = __ballot(ranked);
       const int p = __popcll(mask & ((1ull << lane) - 1ull)), n = __popcll(mask);
       int beaten_by = 0;
-      if constexpr (GROUP) {
-        // lane = excluded news: what the total takes back, its group takes back as well, per target slot
-        const int32_t gx = x_counts ? ga.of(ex) : -1;
-        for (int j = 0; j < a.T; ++j) {
-          const bool beats = x_counts && kx > lane_u64(kt, j);
-          const int cnt = __popcll(__ballot(beats));
-          if (lane == j) beaten_by = cnt;
+      // GROUP: lane = excluded news: what the total takes back, its group takes back as well, per target slot
+      int32_t gx = -1;
+      if constexpr (GROUP) gx = x_counts ? ga.of(ex) : -1;
+      for (int j = 0; j < a.T; ++j) {
+        const bool beats = x_counts && kx > lane_u64(kt, j);
+        const int cnt = __popcll(__ballot(beats));
+        if (lane == j) beaten_by = cnt;
+        if constexpr (GROUP) {
           if (beats && gx >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + gx], -1);
         }
+      }
+      if constexpr (GROUP) {
         if (lane < a.T) ga.tgrp[u * a.T + lane] = t_in ? ga.of(tg) : -1;
         if (ranked) ga.slot[u * a.T + p] = lane;
-      } else {
-        for (int j = 0; j < a.T; ++j) {
-          const int cnt = __popcll(__ballot(x_counts && kx > lane_u64(kt, j)));
-          if (lane == j) beaten_by = cnt;
-        }
       }
       if (ranked) {
         a.w.keys[u * a.T + p] = kt;
@@ -307,7 +258,7 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, 
   rank_csr_stage(sIds, a, ca, (size_t)u0, 0, seg_b, L, tid);
   __syncthreads();
 
-  RankNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  ScoreNamedRows rows = {a.news, a.ld_news, sIds, a.V};
   t.load_slab(rows, 0);
   // wave 0, across the chunks of one user: lane j = target j
   int32_t tg = 0;
@@ -374,32 +325,25 @@ __global__ __launch_bounds__(TK_THREADS) void rank_named_csr_kernel(RankArgs a, 
         kb = news_key(sS[lane + RK_SLOTS], (uint32_t)xb);
       }
       const bool a_counts = a_in && (ka >> 32) != 0, b_counts = b_in && (kb >> 32) != 0;   // a NaN news: nothing to take back
+      // GROUP: what the total takes back, the listed news' group takes back as well, per target slot
+      int32_t grp_a = -1, grp_b = -1;
       if constexpr (GROUP) {
-        // what the total takes back, the listed news' group takes back as well, per target slot
-        const int32_t grp_a = a_counts ? ga.of(xa) : -1, grp_b = b_counts ? ga.of(xb) : -1;
-        for (int j = 0; j < a.T; ++j) {
-          const int32_t tj = __builtin_amdgcn_readlane(tg, j);
-          const u64 ktj = lane_u64(kt, j);
-          const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
-          const bool a_beats = a_counts && ka > ktj, b_beats = b_counts && kb > ktj;
-          const int cnt = __popcll(__ballot(a_beats)) + __popcll(__ballot(b_beats));
-          if (lane == j) {
-            if (listed) ranked = false;
-            beaten_by += cnt;
-          }
+        grp_a = a_counts ? ga.of(xa) : -1;
+        grp_b = b_counts ? ga.of(xb) : -1;
+      }
+      for (int j = 0; j < a.T; ++j) {
+        const int32_t tj = __builtin_amdgcn_readlane(tg, j);
+        const u64 ktj = lane_u64(kt, j);
+        const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
+        const bool a_beats = a_counts && ka > ktj, b_beats = b_counts && kb > ktj;
+        const int cnt = __popcll(__ballot(a_beats)) + __popcll(__ballot(b_beats));
+        if (lane == j) {
+          if (listed) ranked = false;
+          beaten_by += cnt;
+        }
+        if constexpr (GROUP) {
           if (a_beats && grp_a >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + grp_a], -1);
           if (b_beats && grp_b >= 0) atomicAdd(&ga.cnt[(u * a.T + j) * ga.G + grp_b], -1);
-        }
-      } else {
-        for (int j = 0; j < a.T; ++j) {
-          const int32_t tj = __builtin_amdgcn_readlane(tg, j);
-          const u64 ktj = lane_u64(kt, j);
-          const bool listed = __ballot((a_in && xa == tj) || (b_in && xb == tj)) != 0ull;
-          const int cnt = __popcll(__ballot(a_counts && ka > ktj)) + __popcll(__ballot(b_counts && kb > ktj));
-          if (lane == j) {
-            if (listed) ranked = false;
-            beaten_by += cnt;
-          }
         }
       }
       if (q + 1 >= nq) {                                      // the user's last chunk: compact and store
@@ -640,23 +584,7 @@ __global__ __launch_bounds__(256) void rank_final_kernel(RankWs w, int U, int T,
     out_scores[u * T + lane] = score;
   }
   if (!want_terms) return;
-  // the text of rank_terms, kept in place so that this kernel stays instruction for instruction what it was before group caps
-  double* o = w.terms + u * (2 + 2 * ks.n);
-  const double gain = rank > 0 ? 1.0 / log2((double)rank + 1.0) : 0.0, ideal = 1.0 / log2((double)lane + 2.0);
-  const double rr = wave_sum_d(rank > 0 ? 1.0 / (double)rank : 0.0);
-  if (lane == 0) {
-    o[0] = n > 0 ? 1.0 : 0.0;
-    o[1] = n > 0 ? rr / n : 0.0;
-  }
-  for (int i = 0; i < ks.n; ++i) {
-    const bool hit = rank > 0 && rank <= ks.k[i];
-    const int hits = __popcll(__ballot(hit));
-    const double dcg = wave_sum_d(hit ? gain : 0.0), idcg = wave_sum_d(lane < n && lane < ks.k[i] ? ideal : 0.0);
-    if (lane == 0) {
-      o[2 + 2 * i] = n > 0 ? (double)hits / n : 0.0;
-      o[3 + 2 * i] = n > 0 ? dcg / idcg : 0.0;
-    }
-  }
+  rank_terms(w, u, lane, n, rank, ks);
 }
 
 // The finalize pass of a call with group caps.  counters[u, j, g] = n_g of target slot j (stream count minus what the named
@@ -721,26 +649,14 @@ __global__ __launch_bounds__(1024) void rank_reduce_kernel(const double* __restr
 int rank_check(const nr_rank_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_rank: null descriptor");
   NR_CHECK_ARG(d->T >= 1 && d->T <= NR_RANK_MAX_TARGETS, "score_rank: T = %d targets per user, must be in [1, %d]", d->T, NR_RANK_MAX_TARGETS);
-  NR_CHECK_ARG(d->V >= 2, "score_rank: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
-  NR_CHECK_ARG(d->U >= 1, "score_rank: U = %d users", d->U);
-  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_rank: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
-               NR_TOPK_MAX_N);
-  NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_rank: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
-  NR_CHECK_ARG(d->n_excl >= 0, "score_rank: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
-  NR_CHECK_ARG(d->E == 0 || d->excl_offsets == nullptr,
-               "score_rank: the dense list (E = %d) and the CSR lists (excl_offsets) are not combined: one list form per call", d->E);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
-               "score_rank: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
-               "score_rank: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_RC(check_vectors("score_rank", d->V, d->U, d->N));
+  NR_CHECK_RC(check_lists("score_rank", d->E, d->excl_offsets, d->excl_ids, d->n_excl));
   NR_CHECK_ARG(d->n_ks >= 0 && d->n_ks <= NR_RANK_MAX_KS, "score_rank: n_ks = %d cut-offs, at most %d", d->n_ks, NR_RANK_MAX_KS);
   NR_CHECK_ARG(d->n_ks == 0 || d->ks != nullptr, "score_rank: null pointer (ks) with n_ks = %d", d->n_ks);
   for (int i = 0; i < d->n_ks; ++i) NR_CHECK_ARG(d->ks[i] >= 1, "score_rank: cut-off k = %d at position %d, must be >= 1", d->ks[i], i);
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= RK_MAX_SPLITS, "score_rank: splits = %d, must be 0 (library's choice) or in [1, %d]", d->splits,
                RK_MAX_SPLITS);
-  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_rank: stamp given without window (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_rank: window given without stamp (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_rank: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_RC(check_pools("score_rank", d->stamp, d->window, d->ld_window));
   NR_CHECK_ARG(d->group == nullptr || (d->group_cap >= 1 && d->group_cap <= NR_TOPK_MAX_K),
                "score_rank: group given with group_cap = %d, the cap must be in [1, %d]", d->group_cap, NR_TOPK_MAX_K);
   NR_CHECK_ARG(d->group != nullptr || d->group_cap == 0, "score_rank: group_cap = %d given without group (the two come together)", d->group_cap);
@@ -762,10 +678,30 @@ inline RankPlan rk_plan(const nr_rank_desc* d) {
   RankPlan p;
   const bool grp = d->group != nullptr;
   p.TU = grp ? rk_group_user_tile(d->N, d->n_groups) : rk_user_tile(d->N);
-  p.splits = d->splits > 0 ? d->splits : grp ? rk_auto_splits(d->U, d->V, d->N, p.TU) : rk_auto_splits(d->U, d->V, d->N);
+  p.splits = d->splits > 0 ? d->splits : score_auto_splits(d->U, d->V, p.TU, RK_MAX_SPLITS);
   p.per = (int)(((long)d->V - 1 + p.splits - 1) / p.splits);
   p.cps = (p.per + TK_ROWS - 1) / TK_ROWS;
   return p;
+}
+
+// the named passes: f(POOL, GROUP) launches its kernel's instantiation
+template <class F>
+int rank_named_launch(bool pool, bool grp, F&& f) {
+  return with_bool(pool, [&](auto p) { return with_bool(grp, [&](auto g) { return f(p, g); }); });
+}
+// The counting pass for the run-time (tile, pool, blocks of 64 groups; 0 = no caps).  With caps the per-wave counters (TU / 8
+// users x 4 targets x blocks) stay within 64 registers, so MT * GB <= 8 (rk_group_user_tile picks the tile accordingly): the
+// capped kernel exists for (TU, GB) in {64, 32, 16} x {1, 2}, {32, 16} x {4} and {16} x {8}.
+int rank_count_launch(int TU, bool pool, int gb, dim3 grid, size_t smem, hipStream_t s, const RankArgs& a, const GroupArgs& ga) {
+  return with_int<64, 32, 16>(TU, [&](auto tu) {
+    return with_bool(pool, [&](auto p) {
+      return with_int<0, 1, 2, 4, 8>(gb, [&](auto b) {
+        constexpr int MT = decltype(tu)::value / 16, GB = decltype(b)::value;
+        if constexpr (MT * GB > 8) return (int)NR_ERR_ARG;   // not reached
+        else return launch_lds(rank_count_kernel<MT, decltype(p)::value, GB>, grid, dim3(TK_THREADS), smem, s, a, group_args_if<(GB > 0)>(ga));
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -781,18 +717,13 @@ size_t nr_score_rank_workspace_bytes(const nr_rank_desc* d) {
 }
 
 int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
-  const int rc = rank_check(d);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(rank_check(d));
   NR_CHECK_ARG(d->news_vecs && d->user && d->targets && d->out_ranks && d->out_scores,
                "score_rank: null pointer (news_vecs, user, targets, out_ranks, out_scores)");
-  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
-                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
-               "score_rank: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_RC(check_rows("score_rank", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
   NR_CHECK_ARG(d->ld_targets >= d->T, "score_rank: target row stride %d < T = %d", d->ld_targets, d->T);
   NR_CHECK_ARG(d->E == 0 || d->exclude == nullptr || d->ld_exclude >= d->E, "score_rank: exclusion row stride %d < E = %d", d->ld_exclude, d->E);
-  const size_t need = nr_score_rank_workspace_bytes(d);
-  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
-               "score_rank: workspace holds %zu bytes, nr_score_rank_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_CHECK_RC(check_workspace("score_rank", d->ws, d->ws_bytes, nr_score_rank_workspace_bytes(d)));
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
   const RankPlan pl = rk_plan(d);
@@ -817,84 +748,29 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream) {
                        const_cast<u64*>(ga.masks), d->V, d->n_groups, pl.per, pl.cps, n_chunks);
     NR_CHECK_LAUNCH();
   }
-  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
   const bool pool = a.pool.any();
-  const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
-  if (csr) {
-    const CsrArgs ca = {d->excl_offsets, d->excl_ids, d->n_excl};
+  const CsrArgs ca = csr_args(d->excl_offsets, d->excl_ids, d->n_excl);
+  const dim3 named_grid((unsigned)((d->U + 15) / 16));
+  if (ca.offsets != nullptr) {
     NrProfScope ps(s, "rank_named_csr[U=%d,N=%d,T=%d,n_excl=%d]", d->U, d->N, d->T, d->n_excl);
-    const size_t smem = rk_lds_bytes(16, d->N) + (size_t)2 * TK_ROWS * sizeof(int32_t);
-    if (grp) {
-      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true, true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false, true>);
-      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (pool) hipLaunchKernelGGL((rank_named_csr_kernel<true, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, ga);
-      else hipLaunchKernelGGL((rank_named_csr_kernel<false, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, ga);
-    } else {
-      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_csr_kernel<true>) : reinterpret_cast<const void*>(rank_named_csr_kernel<false>);
-      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (pool) hipLaunchKernelGGL(rank_named_csr_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, NoGroupArgs{});
-      else hipLaunchKernelGGL(rank_named_csr_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ca, NoGroupArgs{});
-    }
+    const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * TK_ROWS * sizeof(int32_t);
+    NR_CHECK_RC(rank_named_launch(pool, grp, [&](auto p, auto g) {
+      return launch_lds(rank_named_csr_kernel<p.value, g.value>, named_grid, dim3(TK_THREADS), smem, s, a, ca, group_args_if<g.value>(ga));
+    }));
   } else {
     NrProfScope ps(s, "rank_named[U=%d,N=%d,T=%d,E=%d]", d->U, d->N, d->T, a.E);
-    const size_t smem = rk_lds_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
-    if (grp) {
-      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true, true>) : reinterpret_cast<const void*>(rank_named_kernel<false, true>);
-      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (pool) hipLaunchKernelGGL((rank_named_kernel<true, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ga);
-      else hipLaunchKernelGGL((rank_named_kernel<false, true>), dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, ga);
-    } else {
-      const void* fn = pool ? reinterpret_cast<const void*>(rank_named_kernel<true>) : reinterpret_cast<const void*>(rank_named_kernel<false>);
-      NR_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      if (pool) hipLaunchKernelGGL(rank_named_kernel<true>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, NoGroupArgs{});
-      else hipLaunchKernelGGL(rank_named_kernel<false>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a, NoGroupArgs{});
-    }
+    const size_t smem = tk_tile_bytes(16, d->N) + (size_t)16 * TK_ROWS * sizeof(int32_t);
+    NR_CHECK_RC(rank_named_launch(pool, grp, [&](auto p, auto g) {
+      return launch_lds(rank_named_kernel<p.value, g.value>, named_grid, dim3(TK_THREADS), smem, s, a, group_args_if<g.value>(ga));
+    }));
   }
   NR_CHECK_LAUNCH();
   {
-    const size_t smem = rk_lds_bytes(TU, d->N);
+    const size_t smem = tk_tile_bytes(TU, d->N);
     const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
     NrProfScope ps(s, "rank_count[U=%d,V=%d,N=%d,T=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->T, TU, splits);
-#define NR_RANK_LAUNCH(MT, POOL)                                                                                                           \
-  do {                                                                                                                                     \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                     (int)smem));                                                                                          \
-    hipLaunchKernelGGL((rank_count_kernel<MT, POOL>), grid, dim3(TK_THREADS), smem, s, a, NoGroupArgs{});                                               \
-  } while (0)
-#define NR_RANK_LAUNCH_GROUP(MT, POOL, GB)                                                                                                 \
-  do {                                                                                                                                     \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rank_count_kernel<MT, POOL, GB>),                                 \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                              \
-    hipLaunchKernelGGL((rank_count_kernel<MT, POOL, GB>), grid, dim3(TK_THREADS), smem, s, a, ga);                                   \
-  } while (0)
-#define NR_RANK_LAUNCH_MT(MT, GB)                                  \
-  do {                                                             \
-    if constexpr (GB == 0) {                                       \
-      if (pool) NR_RANK_LAUNCH(MT, true);                          \
-      else NR_RANK_LAUNCH(MT, false);                              \
-    } else {                                                       \
-      if (pool) NR_RANK_LAUNCH_GROUP(MT, true, (GB > 0 ? GB : 1)); \
-      else NR_RANK_LAUNCH_GROUP(MT, false, (GB > 0 ? GB : 1));     \
-    }                                                              \
-  } while (0)
-#define NR_RANK_LAUNCH_TU(GB)                    \
-  do {                                           \
-    if (TU == 64) NR_RANK_LAUNCH_MT(4, GB);      \
-    else if (TU == 32) NR_RANK_LAUNCH_MT(2, GB); \
-    else NR_RANK_LAUNCH_MT(1, GB);               \
-  } while (0)
-    const int gb = grp ? rk_group_blocks(d->n_groups) : 0;    // rk_group_user_tile: TU <= 32 with 4 blocks, 16 with 8
-    if (gb == 0) NR_RANK_LAUNCH_TU(0);
-    else if (gb == 1) NR_RANK_LAUNCH_TU(1);
-    else if (gb == 2) NR_RANK_LAUNCH_TU(2);
-    else if (gb == 4) {
-      if (TU == 32) NR_RANK_LAUNCH_MT(2, 4);
-      else NR_RANK_LAUNCH_MT(1, 4);
-    } else NR_RANK_LAUNCH_MT(1, 8);
-#undef NR_RANK_LAUNCH_TU
-#undef NR_RANK_LAUNCH_MT
-#undef NR_RANK_LAUNCH_GROUP
-#undef NR_RANK_LAUNCH
+    NR_CHECK_RC(rank_count_launch(TU, pool, grp ? rk_group_blocks(d->n_groups) : 0, grid, smem, s, a, ga));
   }
   NR_CHECK_LAUNCH();
   RankKs ks;

@@ -1,13 +1,19 @@
-// The exact-fp32 scoring tile of the full-corpus passes, shared by the top-k selection (nr_topk.hip) and the rank counting
-// (nr_rank.hip).  Both must give one (u, v) pair the SAME bits -- "rank <= k" and "is in the top-k row" are then one
-// statement -- so there is ONE definition of the tile.
+// The exact-fp32 scoring tile of the full-corpus passes and what every pass builds around it.  Its consumers: the top-k
+// selection and the sampled selection (nr_topk.hip), the rank counting and its named passes (nr_rank.hip), the log-partition
+// stream and the named rows of nr_row_logprob (nr_logz.hip); nr_mmr.hip takes score_key and the width check only.  All of them
+// must give one (u, v) pair the SAME bits -- "rank <= k", "is in the top-k row" and "is a term of the partition sum" are then
+// one statement -- so there is ONE definition of the tile, of the keys, and of the rows a chunk is made of.
 //
 // A workgroup of 8 waves keeps TU = 16 * MT user vectors in LDS and takes news rows in chunks of 128 (k-slabs of 32 columns,
 // double buffered through registers).  Wave w forms the [TU x 16] scores of chunk rows 16w .. 16w + 15 on
 // v_mfma_f32_16x16x4_f32; one (u, v) score is ONE fmaf chain over the vector width in a fixed order (k-slab, sub-step e, MFMA
 // k-group), whatever the tile, the place of the user in it, or the place of the news row in the chunk.  Where a chunk's rows
-// come from is the caller's: a slice of the table (ScoreStreamRows) or rows gathered by id.
+// come from is the caller's: a slice of the table (ScoreStreamRows) or rows gathered by id (ScoreNamedRows).
+//
+// The last section is host code: the argument checks, descriptor fills, plans and the launch helper the units share.
 #pragma once
+#include <type_traits>
+
 #include "nr_common.h"
 
 namespace {   // per including unit, as when the tile was nr_topk.hip's own: no name of it reaches other units
@@ -38,6 +44,13 @@ __device__ __forceinline__ uint32_t score_key(float s) {
 }
 __device__ __forceinline__ float key_score(uint32_t key) {
   return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+// A news as one 64-bit key: (score key) << 32 | ~id.  Larger = better; equal scores order by ascending id.
+__device__ __forceinline__ u64 news_key(float score, uint32_t id) { return ((u64)score_key(score) << 32) | (uint32_t)~id; }
+// lane j's 64-bit value, j the same in every lane
+__device__ __forceinline__ u64 lane_u64(u64 v, int j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+  return ((u64)hi << 32) | lo;
 }
 
 // Pools (per-news prior, per-news stamp against a per-user window): the ONE place where a finished dot product becomes the
@@ -155,6 +168,18 @@ struct ScoreStreamRows {
   __device__ __forceinline__ const float* operator()(int r) const { return vc + r < v_hi ? news + (size_t)(vc + r) * ld : nullptr; }
 };
 
+// chunk row r = table row ids[r]; an id outside [1, V) is a row of zeros (its score is never looked at)
+struct ScoreNamedRows {
+  const float* news;
+  size_t ld;
+  const int32_t* ids;   // LDS, [128]
+  int V;
+  __device__ __forceinline__ const float* operator()(int r) const {
+    const int32_t id = ids[r];
+    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
+  }
+};
+
 template <int MT>
 struct ScoreTile {
   static constexpr int TU = 16 * MT;
@@ -244,5 +269,102 @@ struct ScoreTile {
   }
   __device__ __forceinline__ const float* scores() const { return sB; }
 };
+
+// ---- host side: what the entry points of the units share ------------------------------------------------------------------
+
+#define NR_CHECK_RC(...)               \
+  do {                                 \
+    const int rc__ = (__VA_ARGS__);    \
+    if (rc__ != NR_OK) return rc__;    \
+  } while (0)
+
+// The argument rules every full-corpus call states the same way; `what` is the call's name in front of the message.  A call
+// runs them in the order its refusals have always come in, between its own checks.
+inline int check_width(const char* what, int N) {
+  NR_CHECK_ARG(N >= 4 && N % 4 == 0 && N <= NR_TOPK_MAX_N, "%s: vector width N = %d must be a multiple of 4 in [4, %d]", what, N, NR_TOPK_MAX_N);
+  return NR_OK;
+}
+inline int check_vectors(const char* what, int V, int U, int N) {
+  NR_CHECK_ARG(V >= 2, "%s: V = %d news rows; row 0 is the padding news, so at least 2 are needed", what, V);
+  NR_CHECK_ARG(U >= 1, "%s: U = %d users", what, U);
+  return check_width(what, N);
+}
+// the dense list (E ids per user; 0 for a call that has none) and the CSR lists: one form per call, offsets and ids together
+inline int check_lists(const char* what, int E, const int32_t* offsets, const int32_t* ids, int n_excl) {
+  NR_CHECK_ARG(E >= 0 && E <= NR_TOPK_MAX_EXCLUDE, "%s: E = %d excluded ids per user, at most %d", what, E, NR_TOPK_MAX_EXCLUDE);
+  NR_CHECK_ARG(n_excl >= 0, "%s: n_excl = %d entries of excl_ids, must be >= 0", what, n_excl);
+  NR_CHECK_ARG(E == 0 || offsets == nullptr, "%s: the dense list (E = %d) and the CSR lists (excl_offsets) are not combined: one list form per call",
+               what, E);
+  NR_CHECK_ARG(n_excl == 0 || ids == nullptr || offsets != nullptr, "%s: excl_ids given without excl_offsets (n_excl = %d; the two come together)",
+               what, n_excl);
+  NR_CHECK_ARG(n_excl == 0 || offsets == nullptr || ids != nullptr, "%s: excl_offsets given without excl_ids (n_excl = %d; the two come together)",
+               what, n_excl);
+  return NR_OK;
+}
+inline int check_pools(const char* what, const int32_t* stamp, const int32_t* window, int ld_window) {
+  NR_CHECK_ARG(stamp == nullptr || window != nullptr, "%s: stamp given without window (the two come together)", what);
+  NR_CHECK_ARG(window == nullptr || stamp != nullptr, "%s: window given without stamp (the two come together)", what);
+  NR_CHECK_ARG(window == nullptr || ld_window >= 2, "%s: ld_window = %d, a window row is (lo, hi): at least 2", what, ld_window);
+  return NR_OK;
+}
+inline int check_rows(const char* what, const float* news, int ld_news, const float* user, int ld_user, int N) {
+  NR_CHECK_ARG(ld_news >= N && ld_news % 4 == 0 && ld_user >= N && ld_user % 4 == 0 && (((uintptr_t)news | (uintptr_t)user) & 15) == 0,
+               "%s: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", what, ld_news, ld_user, N);
+  return NR_OK;
+}
+// `need` = what nr_<what>_workspace_bytes answers for the descriptor
+inline int check_workspace(const char* what, const void* ws, size_t ws_bytes, size_t need) {
+  NR_CHECK_ARG(ws != nullptr && ws_bytes >= need && (((uintptr_t)ws) & 7) == 0,
+               "%s: workspace holds %zu bytes, nr_%s_workspace_bytes asks for %zu (8-byte aligned)", what, ws_bytes, what, need);
+  return NR_OK;
+}
+
+inline PoolArgs pool_args(const float* prior, const int32_t* stamp, const int32_t* window, int ld_window) {
+  return {prior, stamp, window, (size_t)ld_window};
+}
+// offsets == nullptr in the result = the call has no CSR lists.  n == 0: every segment is empty, so that is no CSR call either.
+inline CsrArgs csr_args(const int32_t* offsets, const int32_t* ids, int n) {
+  const bool csr = offsets != nullptr && ids != nullptr && n > 0;
+  return {csr ? offsets : nullptr, csr ? ids : nullptr, csr ? n : 0};
+}
+
+// LDS bytes of the tile itself, and the widest user tile that fits with the `per_user` bytes a pass keeps per user beside it (the
+// candidates and threshold of the selection; nothing where keys and counters live in registers)
+inline size_t tk_tile_bytes(int TU, int N) { return tk_tile_floats(TU, N) * sizeof(float); }
+inline int score_user_tile(int N, size_t per_user) {
+  for (int tu = 64; tu > 16; tu >>= 1)
+    if (tk_tile_bytes(tu, N) + tu * per_user <= TK_LDS_MAX) return tu;
+  return 16;
+}
+// slices: enough workgroups to fill the chip when there are few user tiles, 1-2 when there are many; never more slices than
+// chunks, nor than `most`
+inline int score_auto_splits(int U, int V, int tile, int most) {
+  const long tiles = ((long)U + tile - 1) / tile;
+  long s = (TK_CUS + tiles - 1) / tiles;
+  const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
+  if (s > chunks) s = chunks;
+  if (s > most) s = most;
+  return s < 1 ? 1 : (int)s;
+}
+
+// A run-time choice as a template argument: f gets std::integral_constant<.., the value>.  with_int knows the values it is
+// given and no others, so a call site instantiates exactly the kernels it lists.
+template <class F>
+int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int... Vs, class F>
+int with_int(int v, F&& f) {
+  int rc = NR_ERR_ARG;
+  (void)((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return rc;
+}
+// One launch of a kernel with dynamic LDS above the default limit: the attribute, then the launch
+template <class... A>
+int launch_lds(void (*kernel)(A...), dim3 grid, dim3 block, size_t smem, hipStream_t s, std::common_type_t<A>... args) {
+  NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(kernel, grid, block, smem, s, args...);
+  return NR_OK;
+}
 
 }  // namespace

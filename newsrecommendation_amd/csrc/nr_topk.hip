@@ -1,7 +1,8 @@
 // Full-corpus top-k recommendation: score[u, v] = <news_vecs[v], user[u]> over the WHOLE news table and, per user, the k best
 // news under the total order (score descending, news id ascending) -- without the [U, V] score matrix ever existing.
 //
-// The scoring tile (ScoreTile<MT>) is nr_score_tile.h, shared with the rank counting of nr_rank.hip: one definition, one set of bits.
+// The scoring tile (ScoreTile<MT>), the keys, the shared argument checks and the plan helpers are nr_score_tile.h: one definition,
+// one set of bits for this unit, nr_rank.hip and nr_logz.hip.
 //
 //   topk_select_kernel<MT>  grid = user tiles x corpus slices, 8 waves.  A workgroup keeps its TU = 16 * MT users' vectors in
 //                           LDS and streams its slice of the table through LDS in chunks of 128 news rows (k-slabs of 32
@@ -51,23 +52,19 @@ namespace {
 
 constexpr int TK_MERGE_MAX = 8192;  // candidates one merge workgroup sorts in LDS (64 KiB)
 
-inline size_t tk_lds_bytes(int TU, int N, int k) {
-  return tk_tile_floats(TU, N) * sizeof(float) + (size_t)TU * k * sizeof(u64) + (size_t)TU * sizeof(uint32_t);
-}
-inline int tk_user_tile(int N, int k) {
-  for (int tu = 64; tu > 16; tu >>= 1)
-    if (tk_lds_bytes(tu, N, k) <= TK_LDS_MAX) return tu;
-  return 16;
-}
+// beside the tile a user keeps its k candidates and its threshold in LDS
+inline size_t tk_user_bytes(int k) { return (size_t)k * sizeof(u64) + sizeof(uint32_t); }
+inline size_t tk_lds_bytes(int TU, int N, int k) { return tk_tile_bytes(TU, N) + TU * tk_user_bytes(k); }
 inline int tk_max_splits(int k) { return TK_MERGE_MAX / k < 256 ? TK_MERGE_MAX / k : 256; }
-// slices: enough workgroups to fill the chip when there are few user tiles, 1-2 when there are many; never more slices than chunks
-inline int tk_auto_splits(int U, int V, int N, int k) {
-  const long tiles = ((long)U + tk_user_tile(N, k) - 1) / tk_user_tile(N, k);
-  long s = (TK_CUS + tiles - 1) / tiles;
-  const long chunks = ((long)V - 1 + TK_ROWS - 1) / TK_ROWS;
-  if (s > chunks) s = chunks;
-  if (s > tk_max_splits(k)) s = tk_max_splits(k);
-  return s < 1 ? 1 : (int)s;
+// user tile and slices of a call: the caller's `splits`, or enough to fill the chip within what one merge workgroup sorts
+struct TopkPlan {
+  int TU, splits;
+};
+inline TopkPlan tk_plan(const nr_topk_desc* d) {
+  TopkPlan p;
+  p.TU = score_user_tile(d->N, tk_user_bytes(d->k));
+  p.splits = d->splits > 0 ? d->splits : score_auto_splits(d->U, d->V, p.TU, tk_max_splits(d->k));
+  return p;
 }
 
 __device__ __forceinline__ u64 wave_min_u64(u64 v) {
@@ -386,23 +383,11 @@ __global__ __launch_bounds__(256) void topk_merge_group_kernel(const u64* __rest
 int topk_check(const nr_topk_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_topk: null descriptor");
   NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "score_topk: k = %d, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
-  NR_CHECK_ARG(d->V >= 2, "score_topk: V = %d news rows; row 0 is the padding news, so at least 2 are needed", d->V);
-  NR_CHECK_ARG(d->U >= 1, "score_topk: U = %d users", d->U);
-  NR_CHECK_ARG(d->N >= 4 && d->N % 4 == 0 && d->N <= NR_TOPK_MAX_N, "score_topk: vector width N = %d must be a multiple of 4 in [4, %d]", d->N,
-               NR_TOPK_MAX_N);
-  NR_CHECK_ARG(d->E >= 0 && d->E <= NR_TOPK_MAX_EXCLUDE, "score_topk: E = %d excluded ids per user, at most %d", d->E, NR_TOPK_MAX_EXCLUDE);
-  NR_CHECK_ARG(d->n_excl >= 0, "score_topk: n_excl = %d entries of excl_ids, must be >= 0", d->n_excl);
-  NR_CHECK_ARG(d->E == 0 || d->excl_offsets == nullptr,
-               "score_topk: the dense list (E = %d) and the CSR lists (excl_offsets) are not combined: one list form per call", d->E);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_ids == nullptr || d->excl_offsets != nullptr,
-               "score_topk: excl_ids given without excl_offsets (n_excl = %d; the two come together)", d->n_excl);
-  NR_CHECK_ARG(d->n_excl == 0 || d->excl_offsets == nullptr || d->excl_ids != nullptr,
-               "score_topk: excl_offsets given without excl_ids (n_excl = %d; the two come together)", d->n_excl);
+  NR_CHECK_RC(check_vectors("score_topk", d->V, d->U, d->N));
+  NR_CHECK_RC(check_lists("score_topk", d->E, d->excl_offsets, d->excl_ids, d->n_excl));
   NR_CHECK_ARG(d->splits >= 0 && d->splits <= tk_max_splits(d->k), "score_topk: splits = %d, must be 0 (library's choice) or in [1, %d] for k = %d",
                d->splits, tk_max_splits(d->k), d->k);
-  NR_CHECK_ARG(d->stamp == nullptr || d->window != nullptr, "score_topk: stamp given without window (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->stamp != nullptr, "score_topk: window given without stamp (the two come together)");
-  NR_CHECK_ARG(d->window == nullptr || d->ld_window >= 2, "score_topk: ld_window = %d, a window row is (lo, hi): at least 2", d->ld_window);
+  NR_CHECK_RC(check_pools("score_topk", d->stamp, d->window, d->ld_window));
   NR_CHECK_ARG(d->group == nullptr || (d->group_cap >= 1 && d->group_cap <= NR_TOPK_MAX_K),
                "score_topk: group given with group_cap = %d, the cap must be in [1, %d]", d->group_cap, NR_TOPK_MAX_K);
   NR_CHECK_ARG(d->group != nullptr || d->group_cap == 0, "score_topk: group_cap = %d given without group (the two come together)", d->group_cap);
@@ -435,11 +420,30 @@ __global__ __launch_bounds__(256) void sample_noise_kernel(SampleArgs sa, const 
 // nr_score_topk's checks plus the fields of the sampled call; 0 = fine
 int sample_check(const nr_sample_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_sample: null descriptor");
-  const int rc = topk_check(&d->topk);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(topk_check(&d->topk));
   NR_CHECK_ARG(d->tau_u != nullptr || (d->tau >= 0.f && d->tau <= 3.402823466e38f), "score_sample: tau = %g, must be finite and >= 0",
                (double)d->tau);
   return NR_OK;
+}
+
+// The selection's instantiation for the run-time (tile, pool, caps, CSR lists, sampled): the 36 that exist, a sampled call
+// being a pooled one.
+int topk_select_launch(int TU, bool pool, bool grouped, bool csr, bool sampled, dim3 grid, size_t smem, hipStream_t s, const TopkArgs& a,
+                              const GroupArgs& ga, const CsrArgs& ca, const SampleArgs& sa) {
+  return with_int<64, 32, 16>(TU, [&](auto tu) {
+    return with_bool(pool || sampled, [&](auto p) {
+      return with_bool(grouped, [&](auto g) {
+        return with_bool(csr, [&](auto c) {
+          return with_bool(sampled, [&](auto sm) {
+            constexpr int MT = decltype(tu)::value / 16;
+            constexpr bool POOL = decltype(p)::value, GROUP = decltype(g)::value, CSR = decltype(c)::value, SAMPLE = decltype(sm)::value;
+            if constexpr (SAMPLE && !POOL) return (int)NR_ERR_ARG;   // not reached: pool || sampled
+            else return launch_lds(topk_select_kernel<MT, POOL, GROUP, CSR, SAMPLE>, grid, dim3(TK_THREADS), smem, s, a, ga, ca, sa);
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -448,26 +452,20 @@ extern "C" {
 
 size_t nr_score_topk_workspace_bytes(const nr_topk_desc* d) {
   if (topk_check(d) != NR_OK) return 0;
-  const int splits = d->splits > 0 ? d->splits : tk_auto_splits(d->U, d->V, d->N, d->k);
-  return (size_t)d->U * splits * d->k * sizeof(u64);
+  return (size_t)d->U * tk_plan(d).splits * d->k * sizeof(u64);
 }
 
 // the two launches of nr_score_topk (sa == nullptr) and of nr_score_sample
 static int topk_run(const nr_topk_desc* d, const SampleArgs* sa_in, nr_stream_t stream) {
-  const int rc = topk_check(d);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(topk_check(d));
   NR_CHECK_ARG(d->news_vecs && d->user && d->out_ids && d->out_scores, "score_topk: null pointer (news_vecs, user, out_ids, out_scores)");
-  NR_CHECK_ARG(d->ld_news >= d->N && d->ld_news % 4 == 0 && d->ld_user >= d->N && d->ld_user % 4 == 0 &&
-                   (((uintptr_t)d->news_vecs | (uintptr_t)d->user) & 15) == 0,
-               "score_topk: rows must be 16-byte aligned (ld_news = %d, ld_user = %d: multiples of 4, >= N = %d)", d->ld_news, d->ld_user, d->N);
+  NR_CHECK_RC(check_rows("score_topk", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
   NR_CHECK_ARG(d->E == 0 || d->exclude == nullptr || d->ld_exclude >= d->E, "score_topk: exclusion row stride %d < E = %d", d->ld_exclude, d->E);
-  const size_t need = nr_score_topk_workspace_bytes(d);
-  NR_CHECK_ARG(d->ws != nullptr && d->ws_bytes >= need && (((uintptr_t)d->ws) & 7) == 0,
-               "score_topk: workspace holds %zu bytes, nr_score_topk_workspace_bytes asks for %zu (8-byte aligned)", d->ws_bytes, need);
+  NR_CHECK_RC(check_workspace("score_topk", d->ws, d->ws_bytes, nr_score_topk_workspace_bytes(d)));
   NR_DEVICE_GUARD(stream, d->news_vecs);
   hipStream_t s = (hipStream_t)stream;
-  const int splits = d->splits > 0 ? d->splits : tk_auto_splits(d->U, d->V, d->N, d->k);
-  const int TU = tk_user_tile(d->N, d->k);
+  const TopkPlan pl = tk_plan(d);
+  const int splits = pl.splits, TU = pl.TU;
   TopkArgs a;
   a.news = d->news_vecs; a.user = d->user;
   a.exclude = d->E > 0 ? d->exclude : nullptr;
@@ -475,44 +473,17 @@ static int topk_run(const nr_topk_desc* d, const SampleArgs* sa_in, nr_stream_t 
   a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_excl = (size_t)d->ld_exclude;
   a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.E = d->E; a.splits = splits;
   a.per = (int)(((long)d->V - 1 + splits - 1) / splits);
-  a.pool.prior = d->prior; a.pool.stamp = d->stamp; a.pool.window = d->window; a.pool.ld_win = (size_t)d->ld_window;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
   const GroupArgs ga = {d->group, d->group_cap};
   const bool sampled = sa_in != nullptr;
   const SampleArgs sa = sampled ? *sa_in : SampleArgs{0u, 0u, 0u, 0.f, nullptr, nullptr};
-  const bool pool = a.pool.any();
   const bool grouped = d->group != nullptr;
-  const bool csr = d->excl_offsets != nullptr && d->excl_ids != nullptr && d->n_excl > 0;   // n_excl == 0: every segment is empty
-  const CsrArgs ca = {csr ? d->excl_offsets : nullptr, csr ? d->excl_ids : nullptr, csr ? d->n_excl : 0};
+  const CsrArgs ca = csr_args(d->excl_offsets, d->excl_ids, d->n_excl);
   const size_t smem = tk_lds_bytes(TU, d->N, d->k);
   const dim3 grid((unsigned)((d->U + TU - 1) / TU), (unsigned)splits);
   {
     NrProfScope ps(s, "topk_select[U=%d,V=%d,N=%d,k=%d,TU=%d,splits=%d]", d->U, d->V, d->N, d->k, TU, splits);
-#define NR_TOPK_LAUNCH(MT, POOL, GROUP, CSR, SAMPLE)                                                                           \
-  do {                                                                                                                         \
-    NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_select_kernel<MT, POOL, GROUP, CSR, SAMPLE>),          \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                                  \
-    hipLaunchKernelGGL((topk_select_kernel<MT, POOL, GROUP, CSR, SAMPLE>), grid, dim3(TK_THREADS), smem, s, a, ga, ca, sa);    \
-  } while (0)
-#define NR_TOPK_LAUNCH_PG(MT, CSR)                                          \
-  do {                                                                      \
-    if (sampled && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR, true);      \
-    else if (sampled) NR_TOPK_LAUNCH(MT, true, false, CSR, true);           \
-    else if (pool && grouped) NR_TOPK_LAUNCH(MT, true, true, CSR, false);   \
-    else if (pool) NR_TOPK_LAUNCH(MT, true, false, CSR, false);             \
-    else if (grouped) NR_TOPK_LAUNCH(MT, false, true, CSR, false);          \
-    else NR_TOPK_LAUNCH(MT, false, false, CSR, false);                      \
-  } while (0)
-#define NR_TOPK_LAUNCH_MT(MT)            \
-  do {                                   \
-    if (csr) NR_TOPK_LAUNCH_PG(MT, true); \
-    else NR_TOPK_LAUNCH_PG(MT, false);   \
-  } while (0)
-    if (TU == 64) NR_TOPK_LAUNCH_MT(4);
-    else if (TU == 32) NR_TOPK_LAUNCH_MT(2);
-    else NR_TOPK_LAUNCH_MT(1);
-#undef NR_TOPK_LAUNCH_MT
-#undef NR_TOPK_LAUNCH_PG
-#undef NR_TOPK_LAUNCH
+    NR_CHECK_RC(topk_select_launch(TU, a.pool.any(), grouped, ca.offsets != nullptr, sampled, grid, smem, s, a, ga, ca, sa));
   }
   NR_CHECK_LAUNCH();
   const int n = splits * d->k;
@@ -522,9 +493,8 @@ static int topk_run(const nr_topk_desc* d, const SampleArgs* sa_in, nr_stream_t 
     NrProfScope ps(s, "topk_merge[U=%d,n=%d,k=%d]", d->U, n, d->k);
     if (grouped) {
       const size_t msmem = (size_t)P * sizeof(u64) + NR_TOPK_MAX_K * sizeof(int32_t);   // up to 64.5 KiB: above the default limit
-      NR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(topk_merge_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)msmem));
-      hipLaunchKernelGGL(topk_merge_group_kernel, dim3((unsigned)d->U), dim3(256), msmem, s, (const u64*)a.part, n, P, d->k, d->group,
-                         d->group_cap, d->out_ids, d->out_scores);
+      NR_CHECK_RC(launch_lds(topk_merge_group_kernel, dim3((unsigned)d->U), dim3(256), msmem, s, a.part, n, P, d->k, d->group, d->group_cap, d->out_ids,
+                             d->out_scores));
     } else
       hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)d->U), dim3(256), (size_t)P * sizeof(u64), s, (const u64*)a.part, n, P, d->k, d->out_ids,
                          d->out_scores);
@@ -541,8 +511,7 @@ size_t nr_score_sample_workspace_bytes(const nr_sample_desc* d) {
 }
 
 int nr_score_sample(const nr_sample_desc* d, nr_stream_t stream) {
-  const int rc = sample_check(d);
-  if (rc != NR_OK) return rc;
+  NR_CHECK_RC(sample_check(d));
   const SampleArgs sa = {(uint32_t)(d->seed & 0xffffffffull), (uint32_t)(d->seed >> 32), d->draw, d->tau, d->tau_u, d->user_keys};
   const int rr = topk_run(&d->topk, &sa, stream);
   if (rr != NR_OK || d->out_model == nullptr) return rr;

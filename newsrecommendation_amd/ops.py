@@ -1154,16 +1154,18 @@ class ExclusionLists:
         return out
 
 
-def _exclude_args(what, exclude, U, dev):
+def _exclude_args(what, exclude, U, dev, dense=True):
     """`exclude` of score_topk / score_rank as descriptor fields: the dense list (a tensor [U, E <= 64]: exclude, ld_exclude, E, as
-    always) or the CSR lists (a wider tensor or an ExclusionLists: excl_offsets, excl_ids, n_excl).  Returns (fields, keepalive)."""
+    always) or the CSR lists (a wider tensor or an ExclusionLists: excl_offsets, excl_ids, n_excl).  dense=False (score_logz, whose
+    descriptor has the CSR fields only): a tensor of any width becomes CSR lists.  Returns (fields, keepalive)."""
+    none = {"exclude": None, "ld_exclude": 0, "E": 0} if dense else {}
     if exclude is None:
-        return {"exclude": None, "ld_exclude": 0, "E": 0}, None
+        return none, None
     if isinstance(exclude, torch.Tensor):
         if exclude.dim() != 2 or exclude.shape[0] != U:
             raise RuntimeError(f"{what}: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
         E = exclude.shape[1]
-        if E <= _lib.NR_TOPK_MAX_EXCLUDE:
+        if dense and E <= _lib.NR_TOPK_MAX_EXCLUDE:
             ex = exclude.detach().to(torch.int32).contiguous() if E else None
             return {"exclude": ptr(ex), "ld_exclude": E, "E": E}, ex
         exclude = ExclusionLists(exclude)
@@ -1172,8 +1174,17 @@ def _exclude_args(what, exclude, U, dev):
     if exclude.U != U or exclude.device != dev:
         raise RuntimeError(f"{what}: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
     n = exclude.ids.numel()
-    return {"exclude": None, "ld_exclude": 0, "E": 0, "excl_offsets": ptr(exclude.offsets), "excl_ids": ptr(exclude.ids) if n else None,
-            "n_excl": n}, exclude
+    return dict(none, excl_offsets=ptr(exclude.offsets), excl_ids=ptr(exclude.ids) if n else None, n_excl=n), exclude
+
+
+def _group_args(what, group, V, dev):
+    """`group` of a capped call as the tensor the descriptor points at: int32 [V] on `dev`, contiguous; None stays None."""
+    if group is None:
+        return None
+    if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
+        raise RuntimeError(f"{what}: group must be an int32 tensor of shape ({V},) on {dev}, got "
+                           f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
+    return group.detach().contiguous()
 
 
 @torch.no_grad()
@@ -1207,27 +1218,14 @@ def _topk_desc(what, news_vecs, user_vecs, k, exclude, splits, prior, stamp, win
     """The nr_topk_desc of score_topk / score_sample without its workspace, after the checks the two share.  Returns (descriptor,
     ids, scores, keepalive); the descriptor is None for U == 0 (nothing to launch)."""
     _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
-    for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
-        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise RuntimeError(f"{what}: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
-                               f"strides {tuple(t.stride())}")
-    V, N = news_vecs.shape
-    U = user_vecs.shape[0]
-    if user_vecs.shape[1] != N:
-        raise RuntimeError(f"{what}: vector widths differ ({N} vs {user_vecs.shape[1]})")
-    dev = news_vecs.device
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
     ids = torch.empty(U, int(k), dtype=torch.int32, device=dev)
     scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
     if U == 0:
         return None, ids, scores, None
     ex_fields, ex_keep = _exclude_args(what, exclude, U, dev)
     pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
-    gr = None
-    if group is not None:
-        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
-            raise RuntimeError(f"{what}: group must be an int32 tensor of shape ({V},) on {dev}, got "
-                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
-        gr = group.detach().contiguous()
+    gr = _group_args(what, group, V, dev)
     d = _lib.TopkDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=int(k), **ex_fields,
                       splits=int(splits), out_ids=ptr(ids), out_scores=ptr(scores), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
@@ -1259,12 +1257,7 @@ def score_sample(news_vecs, user_vecs, k, temperature, seed, draw=0, user_keys=N
     if d is None:
         return ids, perturbed, model
     U, dev = ids.shape[0], ids.device
-    tau = None
-    if tau_t is not None:
-        if tuple(tau_t.shape) != (U,) or not tau_t.is_floating_point() or tau_t.device != dev:
-            raise RuntimeError(f"score_sample: a temperature tensor must be floating point of shape ({U},) on {dev}, got {tuple(tau_t.shape)} "
-                               f"{tau_t.dtype} on {tau_t.device}")
-        tau = tau_t.detach().to(torch.float32).contiguous()
+    tau, tau_u = _tau_args("score_sample", temperature, U, dev)
     keys = None
     if user_keys is not None:
         if (not isinstance(user_keys, torch.Tensor) or tuple(user_keys.shape) != (U,) or user_keys.is_floating_point() or user_keys.is_complex()
@@ -1272,8 +1265,7 @@ def score_sample(news_vecs, user_vecs, k, temperature, seed, draw=0, user_keys=N
             raise RuntimeError(f"score_sample: user_keys must be an integer tensor of shape ({U},) on {dev}, got "
                                f"{(tuple(user_keys.shape), user_keys.dtype, user_keys.device) if isinstance(user_keys, torch.Tensor) else type(user_keys)}")
         keys = user_keys.detach().to(torch.int32).contiguous()
-    sd = _lib.SampleDesc(topk=d, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, draw=int(draw) & 0xFFFFFFFF, tau=0.0 if tau is not None else float(temperature),
-                         tau_u=ptr(tau), user_keys=ptr(keys), out_model=ptr(model))
+    sd = _lib.SampleDesc(topk=d, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, draw=int(draw) & 0xFFFFFFFF, tau=tau, tau_u=ptr(tau_u), user_keys=ptr(keys), out_model=ptr(model))
     ws = _ws(_lib.lib().nr_score_sample_workspace_bytes(C.byref(sd)), dev)     # 0 for a bad descriptor: the call below says why
     sd.topk.ws, sd.topk.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
     check(_lib.lib().nr_score_sample(C.byref(sd), _stream()), "nr_score_sample")
@@ -1299,7 +1291,7 @@ def sample_noise(seed, draw, user_keys, news_ids):
 
 
 def _vector_args(what, news_vecs, user_vecs):
-    """The shape checks score_logz / row_logprob share with score_topk; returns (V, N, U, device)."""
+    """The shape checks of the news and user vectors of every full-corpus call; returns (V, N, U, device)."""
     for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
         if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
             raise RuntimeError(f"{what}: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
@@ -1343,22 +1335,11 @@ def score_logz(news_vecs, user_vecs, temperature, exclude=None, splits=0, prior=
     count = torch.empty(U, dtype=torch.int32, device=dev)
     if U == 0:
         return logsum, smax, count
-    if isinstance(exclude, torch.Tensor):
-        if exclude.dim() != 2 or exclude.shape[0] != U:
-            raise RuntimeError(f"score_logz: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
-        exclude = ExclusionLists(exclude)
-    if exclude is not None:
-        if not isinstance(exclude, ExclusionLists):
-            raise RuntimeError(f"score_logz: exclude must be a tensor [U, E] or an ExclusionLists, got {type(exclude)}")
-        if exclude.U != U or exclude.device != dev:
-            raise RuntimeError(f"score_logz: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
-    n_excl = 0 if exclude is None else exclude.ids.numel()
+    ex_fields, ex_keep = _exclude_args("score_logz", exclude, U, dev, dense=False)
     pr, st, win = _pool_args("score_logz", V, U, dev, prior, stamp, window)
     tau, tau_u = _tau_args("score_logz", temperature, U, dev)
     d = _lib.LogzDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
-                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits),
-                      excl_offsets=ptr(exclude.offsets) if exclude is not None else None, excl_ids=ptr(exclude.ids) if n_excl else None,
-                      n_excl=n_excl, tau=tau, tau_u=ptr(tau_u), out_logsum=ptr(logsum), out_max=ptr(smax), out_count=ptr(count),
+                      ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u), out_logsum=ptr(logsum), out_max=ptr(smax), out_count=ptr(count),
                       prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
     ws = _ws(_lib.lib().nr_score_logz_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
     d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
@@ -1438,12 +1419,7 @@ def mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, group=None, group_c
             raise RuntimeError(f"mmr_select: a penalty tensor must be floating point of shape ({U},) on {dev}, got {tuple(pen_t.shape)} "
                                f"{pen_t.dtype} on {pen_t.device}")
         pen = pen_t.detach().to(torch.float32).contiguous()
-    gr = None
-    if group is not None:
-        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
-            raise RuntimeError(f"mmr_select: group must be an int32 tensor of shape ({V},) on {dev}, got "
-                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
-        gr = group.detach().contiguous()
+    gr = _group_args("mmr_select", group, V, dev)
     ids = torch.empty(U, int(k), dtype=torch.int32, device=dev)
     scores = torch.empty(U, int(k), dtype=torch.float32, device=dev)
     place = torch.empty(U, int(k), dtype=torch.int32, device=dev)
@@ -1495,18 +1471,10 @@ def score_rank_capped(news_vecs, user_vecs, targets, group, group_cap, n_groups=
 def _score_rank(news_vecs, user_vecs, targets, exclude, ks, splits, prior, stamp, window, group, group_cap, n_groups):
     """score_rank (group None) and score_rank_capped: one descriptor, one library call."""
     _need_gpu(news_vecs, user_vecs, targets, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, group)
-    for name, t in (("news_vecs", news_vecs), ("user_vecs", user_vecs)):
-        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-            raise RuntimeError(f"score_rank: {name} must be a 2-D fp32 tensor with contiguous rows, got {tuple(t.shape)} {t.dtype} "
-                               f"strides {tuple(t.stride())}")
-    V, N = news_vecs.shape
-    U = user_vecs.shape[0]
-    if user_vecs.shape[1] != N:
-        raise RuntimeError(f"score_rank: vector widths differ ({N} vs {user_vecs.shape[1]})")
+    V, N, U, dev = _vector_args("score_rank", news_vecs, user_vecs)
     if targets.dim() != 2 or targets.shape[0] != U:
         raise RuntimeError(f"score_rank: targets must be [U = {U}, T], got {tuple(targets.shape)}")
     T = targets.shape[1]
-    dev = news_vecs.device
     want_sums = ks is not None
     ks = [int(k) for k in (ks or ())]
     ranks = torch.empty(U, T, dtype=torch.int32, device=dev)
@@ -1518,14 +1486,9 @@ def _score_rank(news_vecs, user_vecs, targets, exclude, ks, splits, prior, stamp
     ex_fields, ex_keep = _exclude_args("score_rank", exclude, U, dev)
     ks_host = (C.c_int * max(len(ks), 1))(*ks)
     pr, st, win = _pool_args("score_rank", V, U, dev, prior, stamp, window)
-    gr = None
-    if group is not None:
-        if not isinstance(group, torch.Tensor) or tuple(group.shape) != (V,) or group.dtype != torch.int32 or group.device != dev:
-            raise RuntimeError(f"score_rank: group must be an int32 tensor of shape ({V},) on {dev}, got "
-                               f"{(tuple(group.shape), group.dtype, group.device) if isinstance(group, torch.Tensor) else type(group)}")
-        gr = group.detach().contiguous()
-        if n_groups is None:
-            n_groups = max(int(gr.max().item()) + 1, 1)                  # the one synchronisation; all ids negative: one empty group
+    gr = _group_args("score_rank", group, V, dev)
+    if gr is not None and n_groups is None:
+        n_groups = max(int(gr.max().item()) + 1, 1)                      # the one synchronisation; all ids negative: one empty group
     d = _lib.RankDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
                       ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, T=T, targets=ptr(tg), ld_targets=T, **ex_fields,
                       splits=int(splits), ks=ks_host, n_ks=len(ks), out_ranks=ptr(ranks), out_scores=ptr(scores),
