@@ -703,7 +703,11 @@ def additive_pool(x, w1, b1, w2, b2, code: int, mask=None, needed=None, lazy_dx=
     """needed: optional [n] int32 flags (needed_flags): flag 0 = the pooled vector is not used: zeros, nothing computed.
     lazy_dx: the gradient wrt x may keep UNWRITTEN rows for sequences with a zero pooled gradient that lie far from every
     sequence with one -- only when x is the output of ops.mhsa (gather source) whose `_nr_takes_lazy_dy` is set and nothing
-    else consumes x; the MHSA backward then never reads those rows (and raises if the flags did not reach it)."""
+    else consumes x; the MHSA backward then never reads those rows (and raises if the flags did not reach it).
+    Scores: the fused title-level forward (bf16, 24 <= L <= 32, 384 < N <= 416, q <= 256, n * L >= 4096, no mask) takes
+    exp(s) / (sum + 1e-8) as the model writes it, without subtracting the maximum, so scores beyond the fp32 range of exp
+    (s > 88.7; |s| <= |w2|_1 + |b2|) are outside its contract and give NaN there, as they do in the fp32 reference; every
+    other shape subtracts the maximum and returns a number (DESIGN.md "Additive pooling: routes as verified and the sweep")."""
     return PoolFunction.apply(x, w1, b1, w2, b2, mask, code, needed, bool(lazy_dx) and x.requires_grad)
 
 
