@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -735,7 +735,7 @@ int nr_sample_noise(uint64_t seed, uint32_t draw, const int32_t* user_keys, cons
  *               (0 = bad descriptor, see nr_last_error)
  * Refused before any launch (nr_last_error): what K9 refuses for N, ld_news / ld_user, alignment, V, U, stamp without window
  * or the reverse, excl_offsets without excl_ids or the reverse, n_excl < 0; a bad scalar tau; splits outside [0, nseg]; an
- * undersized workspace.  Group caps are not part of this call: the descriptor has no group fields.
+ * undersized workspace.  Group caps are not part of this call (the descriptor has no group fields): K15 is the per-group pass.
  * Layout: nr_topk_desc's conventions; the shared tail ws, ws_bytes, prior, stamp, window, ld_window.                       */
 typedef struct {
   const float* news_vecs;
@@ -786,7 +786,7 @@ int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream);
  * repeats within a row, are the CALLER'S statement and are not checked: a repeated id is simply two entries.
  * Refused before any launch: a null descriptor or required pointer; k out of range; N, ld_news / ld_user, alignment, V, U,
  * stamp without window or the reverse against K9's rules; ld_ids < k; a bad scalar tau; sequential outside {0, 1}.
- * Group caps are not part of this call (under caps the mass that is left needs per-group partitions).                      */
+ * Group caps are not part of this call: under caps the mass that is left needs per-group partitions, K15 / K16.           */
 typedef struct {
   const float* news_vecs;
   int ld_news, V;
@@ -808,6 +808,118 @@ typedef struct {
   int ld_window;
 } nr_logprob_desc;
 int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K15  per-group log-partition: K13 per (user, bin) instead of per user.  Under group caps (K9) a sampled row is sequential
+ * sampling from the softmax over what may still be taken, so the mass that is left at a step is a sum over the groups that are
+ * still open: the propensity of a capped row (K16) needs the partition of every group apart.  metrics.logz_groups_reference
+ * states the contract on the host.  Bins: b = 0 .. n_groups - 1 are the groups, bin n_groups holds the news of no group
+ * (negative group id).  Three results per (user, bin), each [U, n_groups + 1] with row stride n_groups + 1, with K13's
+ * meaning restricted to the bin's news:
+ *   out_max     the largest eligible score of the bin (the bits of K9 / K13); -inf for an empty bin
+ *   out_count   the number of eligible news of the bin, exact
+ *   out_logsum  log sum exp((s - out_max) * (1 / tau_u)) over the bin, >= 0; -inf for an empty bin; NaN for every non-empty bin
+ *               of a user whose tau_u entry is <= 0, NaN or infinite (max and count stay valid), and where out_max is +-inf
+ * Score and eligibility are K13's, bit for bit (pool_key, csrc/nr_score_tile.h).
+ * The stream runs over the GROUP-MAJOR ORDER of the corpus, which the caller builds once per corpus (ops.GroupOrder):
+ *   order      [n_pos] int32: news 1 .. V-1 sorted by (bin, id), every bin's run padded with id 0 up to a multiple of 128
+ *              positions (one chunk of the scoring tile); id 0 is never eligible.  n_pos is a multiple of 128.
+ *   seg_start  [nseg + 1] int32, ascending positions (multiples of 128), seg_start[0] = 0, seg_start[nseg] = n_pos: with
+ *              S = ceil((n_pos / 128) / 256), every bin's run is cut into segments of at most S chunks; a segment never
+ *              straddles two bins; nseg <= 256 + n_groups + 1
+ *   bin_seg    [n_groups + 2] int32: bin b owns segments bin_seg[b] .. bin_seg[b + 1] - 1
+ *   lists      K13's CSR lists IN POSITION SPACE: every id mapped through id -> position and each user's segment re-sorted
+ *              (strictly ascending positions).  In position space the stream is ascending again, so K13's cursor and masks apply.
+ * A chunk's rows are gathered by order[] (ScoreOrderedRows) into the same MFMA chain; prior and stamp are those of the news id.
+ * One (max, sum, count) partial per (user, segment) exactly as in K13 (per-lane chain over the lane's news of the segment,
+ * fixed-order wave reduction); a slice is a run of whole segments (slice y of s: the segments that start in [y n_pos / s,
+ * (y + 1) n_pos / s), so slices carry about equal numbers of chunks whatever the bin sizes); a second kernel merges, per (user, bin), the bin's partials in
+ * fp64 in ascending segment order, takes one log and rounds to fp32 once.  The bits of all three results depend on the user's
+ * own inputs and on the order only -- not on `splits`, the batch, the user tile or the place in it.
+ * What the arrays hold is the caller's statement: ids of order[] outside [1, V) are rows of zeros that are never eligible, and
+ * every position and segment index read from the tables is clamped into its array, so wrong tables give unspecified results,
+ * never an access outside the arrays.
+ *   ws         nr_score_logz_groups_workspace_bytes(d): U * nseg * 12 bytes rounded to 8 (0 = bad descriptor)
+ * Refused before any launch: what K13 refuses; n_groups outside [1, NR_RANK_MAX_GROUPS]; n_pos that is not a positive multiple
+ * of 128; nseg outside [1, 256 + n_groups + 1] or above n_pos / 128; splits outside [0, nseg]; a null order, seg_start, bin_seg. */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1] */
+  const int32_t* excl_ids;     /* optional [n_excl]: POSITIONS, per user strictly ascending */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const int32_t* order;        /* [n_pos] */
+  int n_pos;
+  const int32_t* seg_start;    /* [nseg + 1] */
+  int nseg;
+  const int32_t* bin_seg;      /* [n_groups + 2] */
+  int n_groups;
+  float* out_logsum;           /* [U, n_groups + 1] */
+  float* out_max;              /* [U, n_groups + 1] */
+  int32_t* out_count;          /* [U, n_groups + 1] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V], indexed by news id */
+  const int32_t* stamp;  /* optional [V], indexed by news id; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logz_groups_desc;
+size_t nr_score_logz_groups_workspace_bytes(const nr_logz_groups_desc* d);
+int nr_score_logz_groups(const nr_logz_groups_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K16  log-probabilities of the entries of rows drawn under group caps (nr_score_sample with group / group_cap), on the
+ * per-group partitions of K15 computed with the row's ids LEFT OUT (merged into the lists).  metrics.capped_row_logprob_reference
+ * states the contract on the host.  The law: at step j the candidates are the eligible news not yet taken whose group has
+ * fewer than c = group_cap entries in the row so far; news of no group are never capped.  With w_v = exp(s_v / tau), B_b the
+ * mass of bin b in the bases, and t_b the step at which the row takes its c-th entry of bin b (infinite for bin n_groups and
+ * for bins the row never fills):
+ *   D_j = sum_{b : t_b >= j} (B_b + sum_{i >= j, bin(i) = b} w_i),   out_logp[u, j] = s_j / tau - log D_j
+ * D_j is formed as a sum over the bins still open -- every term positive -- never as "total minus closed bins".
+ * One launch, no workspace: the named-row gather of K14 (the stream's score bits), then one wave per user in fp64 on (max, sum)
+ * pairs: t_b for the row's bins; the never-closing bins joined in a fixed order (each lane its bins ascending, then an xor
+ * butterfly); a walk over the row from the last place to the first that adds w_j at each step and, on reaching t_b, B_b with
+ * the stashed weights of the later entries of b.  One rounding to fp32 per output.
+ *   row_ids     [U, k] int32, row stride ld_ids, k in [1, NR_TOPK_MAX_K]
+ *   base_max, base_logsum   [U, n_groups + 1] fp32, row stride ld_base: out_max and out_logsum of K15
+ *   group       [V] int32 as in K9; an id >= n_groups counts as no group.  group_cap in [1, 128]
+ *   out_logp    [U, k] fp32 contiguous; out_total optional [U]: the fp64 sum of the row, rounded once
+ * Entries: an id that is 0 or outside [1, V) is fill: 0, part of no sum.  A key-0 entry (NaN score, prior -inf, stamp outside the
+ * window) gives NaN, is part of no sum and uses up nothing of a cap.  A bad tau_u entry gives NaN for the real entries of the
+ * user.  A live entry whose group already has c live entries before it gives -inf (the capped sampler never draws it): it uses up
+ * nothing of a cap, its weight still counts in D_j of every earlier step at which its group was open (the caller left it out of
+ * the bases), and out_total is then -inf.  Repeats and membership in the lists are the caller's statement, as in K14.
+ * Refused before any launch: what K14 refuses; group_cap outside [1, 128]; n_groups outside [1, NR_RANK_MAX_GROUPS];
+ * ld_base < n_groups + 1; a null group.                                                                                   */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, k;
+  const int32_t* row_ids;
+  int ld_ids;
+  const int32_t* group;     /* [V] */
+  int group_cap, n_groups;
+  float tau;                /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;       /* optional [U] */
+  const float* base_max;    /* [U, ld_base]: out_max of K15 */
+  const float* base_logsum; /* [U, ld_base]: out_logsum of K15 */
+  int ld_base;
+  float* out_logp;          /* [U, k] */
+  float* out_total;         /* optional [U] */
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logprob_capped_desc;
+int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

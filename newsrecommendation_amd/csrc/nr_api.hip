@@ -487,6 +487,8 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 11) out[10] = sizeof(nr_sample_desc);
   if (n >= 12) out[11] = sizeof(nr_logz_desc);
   if (n >= 13) out[12] = sizeof(nr_logprob_desc);
+  if (n >= 14) out[13] = sizeof(nr_logz_groups_desc);
+  if (n >= 15) out[14] = sizeof(nr_logprob_capped_desc);
   return NR_OK;
 }
 

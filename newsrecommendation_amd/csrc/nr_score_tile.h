@@ -180,6 +180,26 @@ struct ScoreNamedRows {
   }
 };
 
+// chunk row r = table row order[p + r] of a permuted ("virtual") corpus of n positions that ends at v_hi; id 0 is padding, and
+// like any id outside [1, V) a row of zeros.  The tile asks a thread for two rows of a chunk only, r = srow < 64 and srow + 64
+// (load_slab), once per k-slab: seek() reads their two ids once per chunk, so the slabs of a chunk cost no further index loads.
+struct ScoreOrderedRows {
+  const float* news;
+  size_t ld;
+  const int32_t* order;   // [n] news id of every position
+  int V;
+  long v_hi;
+  int32_t id_lo, id_hi;   // this thread's rows srow and srow + 64 of the chunk seek() was given
+  __device__ __forceinline__ void seek(long vc, int srow) {
+    id_lo = vc + srow < v_hi ? order[vc + srow] : 0;
+    id_hi = vc + srow + 64 < v_hi ? order[vc + srow + 64] : 0;
+  }
+  __device__ __forceinline__ const float* operator()(int r) const {
+    const int32_t id = r < 64 ? id_lo : id_hi;
+    return id >= 1 && id < V ? news + (size_t)id * ld : nullptr;
+  }
+};
+
 template <int MT>
 struct ScoreTile {
   static constexpr int TU = 16 * MT;

@@ -387,6 +387,116 @@ def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, 
     return out, out.sum(axis=1)
 
 
+def _bins(group, n_groups, V):
+    """[V] int64 bins of the news under `group`: the group id, or n_groups for a negative one ("no group"); and n_groups
+    (None = max id + 1, at least 1).  An id >= n_groups is an error."""
+    grp = np.asarray(group, dtype=np.int64).reshape(V)
+    G = max(int(grp.max()) + 1, 1) if n_groups is None else int(n_groups)
+    if not 1 <= G <= 512:
+        raise ValueError(f"n_groups = {G}, must be in [1, 512]")
+    if grp.max() >= G:
+        raise ValueError(f"group id {int(grp.max())} >= n_groups = {G}")
+    return np.where(grp < 0, G, grp), G
+
+
+def logz_groups_reference(a, b=None, *, temperature, group, n_groups=None, exclude=None, prior=None, stamp=None, window=None):
+    """Host statement of the per-group log-partition contract (include/nrhip.h, nr_score_logz_groups); tests check the device
+    against it, no product path calls it.
+
+    `a`, `b`, `exclude`, the pools and what is eligible are logz_reference's.  group [V] integer ids in [0, n_groups) (negative =
+    in no group), n_groups <= 512 (None = max id + 1).  Bins b = 0 .. n_groups - 1 are the groups, bin n_groups is "no group".
+    Per (user, bin), over the eligible news of the bin, in float64, with logz_reference's meaning: gmax = the largest score,
+    count = how many, logsum = log sum exp((score - gmax) / tau_u) >= 0.  An empty bin gives (-inf, -inf, 0), whatever the
+    temperature; an entry of temperature that is not finite and > 0 gives that user logsum NaN in every non-empty bin and leaves
+    gmax and count; a largest score of +-inf gives logsum NaN.
+    Returns (logsum float64 [U, n_groups + 1], gmax float64 [U, n_groups + 1], count int64 [U, n_groups + 1])."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    bins, G = _bins(group, n_groups, V)
+    tau, tau_ok = _temperatures(temperature, U)
+    logsum, gmax, count = np.full((U, G + 1), -np.inf), np.full((U, G + 1), -np.inf), np.zeros((U, G + 1), dtype=np.int64)
+    for u in range(U):
+        ok = ~np.isnan(scores[u]) & pool[u]
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        for bb in np.unique(bins[ok]):
+            x = scores[u, ok & (bins == bb)]
+            count[u, bb] = x.size
+            gmax[u, bb] = x.max()
+            if not tau_ok[u] or not np.isfinite(gmax[u, bb]):
+                logsum[u, bb] = np.nan
+            else:
+                logsum[u, bb] = np.log(np.sum(np.exp((x - gmax[u, bb]) / tau[u])))
+    return logsum, gmax, count
+
+
+def capped_row_logprob_reference(a, b=None, *, row_ids, temperature, bases, group, group_cap, n_groups=None, prior=None, stamp=None,
+                                 window=None):
+    """Host statement of the capped row log-probability contract (include/nrhip.h, nr_row_logprob_capped); tests check the
+    device against it, no product path calls it.
+
+    The law of sample_reference's rows under caps: at step j the candidates are the eligible news not yet taken whose group has
+    fewer than c = group_cap entries in the row so far; news of no group (negative id) are never capped.  `a`, `b` and the pools
+    are topk_reference's; row_ids [U, k]; bases = (logsum, gmax), each [U, n_groups + 1]: the first two results of
+    logz_groups_reference (or of the device) computed with the row's ids in `exclude`.  With s_i the score (+ prior) of entry i,
+    w = exp(s / tau), B_b = exp(gmax_b / tau + logsum_b) the mass of bin b in the bases, and t_b the step at which the row takes
+    its c-th live entry of bin b (infinite for bin n_groups and for bins the row never fills), in float64:
+      D_j = sum_{b : t_b >= j} (B_b + sum_{i >= j, bin(i) = b} w_i),   out[u, j] = s_j / tau - log D_j
+    a sum of positive terms over the bins still open (formed around the largest score among them), never a difference.
+    Entries: 0 or outside [1, V) is fill: 0, part of no sum.  Outside the pool or a NaN score: NaN, part of no sum, uses up
+    nothing of a cap.  A temperature that is not finite and > 0: NaN for the real entries of that user.  A live entry whose
+    group already has c live entries before it: -inf (the capped sampler never draws it); it uses up nothing of a cap, and its
+    weight still counts in D_j of every earlier step at which its group was open -- the caller left it out of the bases.  The
+    total of such a row is -inf.  Membership in an exclusion list and repeats are the caller's statement and are not checked.
+    Returns (logp float64 [U, k], total float64 [U] = the row sums)."""
+    if not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    bins, G = _bins(group, n_groups, V)
+    ids = np.asarray(row_ids, dtype=np.int64).reshape(U, -1)
+    k, c = ids.shape[1], int(group_cap)
+    tau, tau_ok = _temperatures(temperature, U)
+    bl, bm = np.asarray(bases[0], dtype=np.float64).reshape(U, G + 1), np.asarray(bases[1], dtype=np.float64).reshape(U, G + 1)
+    out = np.zeros((U, k), dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for u in range(U):
+            real = (ids[u] >= 1) & (ids[u] < V)
+            at = np.where(real, ids[u], 0)
+            s = scores[u, at]
+            live = real & pool[u, at] & ~np.isnan(s)
+            bn = bins[at]
+            t_close = np.full(G + 1, k, dtype=np.int64)                # k stands for "never"
+            seen, capped = np.zeros(G + 1, dtype=np.int64), np.zeros(k, dtype=bool)
+            for j in np.flatnonzero(live):
+                if bn[j] < G:
+                    capped[j] = seen[bn[j]] >= c
+                    seen[bn[j]] += 1
+                    if seen[bn[j]] == c:
+                        t_close[bn[j]] = j
+            for j in range(k):
+                if not real[j]:
+                    continue
+                if not live[j] or not tau_ok[u]:
+                    out[u, j] = np.nan
+                elif capped[j]:
+                    out[u, j] = -np.inf
+                else:
+                    open_bins = t_close >= j
+                    rest = s[j:][live[j:] & open_bins[bn[j:]]]
+                    has = open_bins & ((bm[u] > -np.inf) | np.isnan(bl[u]))
+                    M = max(rest.max(), bm[u][has].max()) if has.any() else rest.max()
+                    mass = np.sum(np.exp((rest - M) / tau[u])) + np.sum(np.exp((bm[u][has] - M) / tau[u] + bl[u][has]))
+                    out[u, j] = (s[j] - M) / tau[u] - np.log(mass)
+    return out, out.sum(axis=1)
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

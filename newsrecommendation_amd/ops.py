@@ -1391,6 +1391,177 @@ def row_logprob(news_vecs, user_vecs, row_ids, temperature, base, sequential, pr
     return logp, total
 
 
+class GroupOrder:
+    """The group-major order of a corpus, which score_logz_groups streams over (include/nrhip.h, K15).  Build it once per corpus
+    -- as an ExclusionLists is built once per batch of users -- and hand it to as many calls as needed; everything in it is a
+    function of `group` alone.  It lives on the device of `group`; CPU tensors work as well (nothing here launches a kernel).
+      group     int32 [V]: one group id per news in [0, n_groups), negative = in no group; n_groups <= 512
+      n_groups  None takes max id + 1 (at least 1).  An id >= n_groups raises ValueError.
+    Bins b = 0 .. n_groups - 1 are the groups, bin n_groups is "no group".  What it holds:
+      order      int32 [n_pos]: news 1 .. V-1 sorted by (bin, id); every bin's run is padded with id 0 up to a multiple of 128
+                 positions (one chunk of the scoring tile).  Id 0 is never eligible.
+      pos        int32 [V]: the inverse map id -> position (-1 for id 0)
+      bin_start  int32 [n_groups + 2]: bin b owns positions bin_start[b] .. bin_start[b + 1] - 1
+      seg_start  int32 [nseg + 1], bin_seg int32 [n_groups + 2]: with S = chunks_per_segment = ceil((n_pos / 128) / 256), every
+                 bin's run is cut into segments of at most S chunks; a segment never straddles two bins; bin b owns segments
+                 bin_seg[b] .. bin_seg[b + 1] - 1; nseg <= 256 + n_groups + 1.
+    Two host synchronisations (the largest id, the bin sizes); the tables are host arithmetic on the bin sizes."""
+
+    CHUNK, MAX_SEGS = 128, 256
+
+    def __init__(self, group, n_groups=None):
+        if not isinstance(group, torch.Tensor) or group.dim() != 1 or group.dtype != torch.int32 or group.numel() < 2:
+            raise RuntimeError(f"GroupOrder: group must be an int32 tensor [V >= 2], got "
+                               f"{(tuple(group.shape), group.dtype) if isinstance(group, torch.Tensor) else type(group)}")
+        g = group.detach().to(torch.int64)
+        dev, V = g.device, g.numel()
+        top = int(g.max())
+        G = max(top + 1, 1) if n_groups is None else int(n_groups)
+        if not 1 <= G <= _lib.NR_RANK_MAX_GROUPS:
+            raise ValueError(f"GroupOrder: n_groups = {G}, must be in [1, {_lib.NR_RANK_MAX_GROUPS}]")
+        if top >= G:
+            raise ValueError(f"GroupOrder: group id {top} >= n_groups = {G}")
+        bins = torch.where(g < 0, torch.full_like(g, G), g)[1:]
+        ids = torch.arange(1, V, dtype=torch.int64, device=dev)
+        srt = torch.sort(bins * V + ids).values                          # (bin, id) ascending
+        sb, sid = srt // V, srt % V
+        counts = torch.bincount(bins, minlength=G + 1)
+        cnt = [int(x) for x in counts.tolist()]
+        C = self.CHUNK
+        padded = [(c + C - 1) // C * C for c in cnt]
+        bin_start = [0]
+        for p in padded:
+            bin_start.append(bin_start[-1] + p)
+        n_pos = bin_start[-1]
+        S = max(1, (n_pos // C + self.MAX_SEGS - 1) // self.MAX_SEGS)
+        seg_start, bin_seg = [], [0]
+        for b in range(G + 1):
+            seg_start.extend(range(bin_start[b], bin_start[b + 1], S * C))
+            bin_seg.append(len(seg_start))
+        seg_start.append(n_pos)
+        first = torch.zeros(G + 1, dtype=torch.int64, device=dev)        # of a bin: its first place in the sorted run
+        first[1:] = torch.cumsum(counts, 0)[:-1]
+        at = torch.tensor(bin_start[:-1], dtype=torch.int64, device=dev)[sb] + (torch.arange(V - 1, dtype=torch.int64, device=dev) - first[sb])
+        order = torch.zeros(n_pos, dtype=torch.int32, device=dev)
+        order[at] = sid.to(torch.int32)
+        pos = torch.full((V,), -1, dtype=torch.int32, device=dev)
+        pos[sid] = at.to(torch.int32)
+        self.V, self.n_groups, self.n_pos, self.nseg, self.chunks_per_segment = V, G, n_pos, len(seg_start) - 1, S
+        self.order, self.pos = order, pos
+        self.bin_start = torch.tensor(bin_start, dtype=torch.int32, device=dev)
+        self.seg_start = torch.tensor(seg_start, dtype=torch.int32, device=dev)
+        self.bin_seg = torch.tensor(bin_seg, dtype=torch.int32, device=dev)
+
+    @property
+    def device(self):
+        return self.order.device
+
+    def positions(self, lists):
+        """An ExclusionLists in position space: every id in [1, V) mapped through id -> position, each user's list re-sorted
+        (strictly ascending positions, which is what the stream over `order` meets in ascending order); other ids are dropped."""
+        users, ids = lists._pairs()
+        keep = (ids >= 1) & (ids < self.V)
+        users, ids = users[keep], ids[keep]
+        keys = torch.unique_consecutive(torch.sort((users << 31) + self.pos.to(torch.int64)[ids]).values)
+        offsets = torch.zeros(lists.U + 1, dtype=torch.int64, device=keys.device)
+        offsets[1:] = torch.cumsum(torch.bincount(keys >> 31, minlength=lists.U), 0)
+        return ExclusionLists.from_sorted(offsets, keys & ((1 << 31) - 1))
+
+
+def _groups_arg(what, groups, V, dev):
+    if not isinstance(groups, GroupOrder):
+        raise RuntimeError(f"{what}: groups must be an ops.GroupOrder, got {type(groups)}")
+    if groups.V != V or groups.device != dev:
+        raise RuntimeError(f"{what}: the GroupOrder was built for V = {groups.V} news on {groups.device}, the call has V = {V} on {dev}")
+    return groups
+
+
+@torch.no_grad()
+def score_logz_groups(news_vecs, user_vecs, temperature, groups, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """Per-group log-partition (nr_score_logz_groups; include/nrhip.h, K15): score_logz per (user, bin) -- bins 0 .. n_groups - 1
+    are the groups of `groups` (an ops.GroupOrder, built once per corpus), bin n_groups is "no group".  Same score bits, pools and
+    lists as score_topk / score_sample / score_logz; no [U, V] score matrix.  Returns (logsum fp32, gmax fp32, count int32), each
+    [U, n_groups + 1]: gmax is the bin's largest eligible score, count its eligible news, logsum = log sum exp((score - gmax) /
+    temperature) >= 0 over the bin; an empty bin gives (-inf, -inf, 0).  exp(gmax / temperature + logsum - log Z) is the bin's
+    share of the user's exposure under score_sample; ops.row_logprob_capped builds the propensity of a capped row on these.
+    `temperature`, `exclude` (ids; mapped to positions here), `splits` (at most groups.nseg) and the pools are score_logz's; a bad
+    entry of a temperature tensor gives that user NaN logsums only.  The three results do not depend, bit for bit, on `splits` or
+    on which users share the call."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    V, N, U, dev = _vector_args("score_logz_groups", news_vecs, user_vecs)
+    gr = _groups_arg("score_logz_groups", groups, V, dev)                   # shapes first: these refusals need no GPU
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, gr.order)
+    B = gr.n_groups + 1
+    logsum = torch.empty(U, B, dtype=torch.float32, device=dev)
+    gmax = torch.empty(U, B, dtype=torch.float32, device=dev)
+    count = torch.empty(U, B, dtype=torch.int32, device=dev)
+    if U == 0:
+        return logsum, gmax, count
+    if isinstance(exclude, torch.Tensor):
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"score_logz_groups: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        exclude = ExclusionLists(exclude)
+    if isinstance(exclude, ExclusionLists) and exclude.U == U and exclude.device == dev:
+        exclude = gr.positions(exclude)
+    ex_fields, ex_keep = _exclude_args("score_logz_groups", exclude, U, dev, dense=False)
+    pr, st, win = _pool_args("score_logz_groups", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("score_logz_groups", temperature, U, dev)
+    d = _lib.LogzGroupsDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                            ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u),
+                            order=ptr(gr.order), n_pos=gr.n_pos, seg_start=ptr(gr.seg_start), nseg=gr.nseg, bin_seg=ptr(gr.bin_seg),
+                            n_groups=gr.n_groups, out_logsum=ptr(logsum), out_max=ptr(gmax), out_count=ptr(count),
+                            prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_logz_groups_workspace_bytes(C.byref(d)), dev)      # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_logz_groups(C.byref(d), _stream()), "nr_score_logz_groups")
+    return logsum, gmax, count
+
+
+@torch.no_grad()
+def row_logprob_capped(news_vecs, user_vecs, row_ids, temperature, bases, group, group_cap, n_groups=None, prior=None, stamp=None,
+                       window=None):
+    """Log-probabilities of the entries of rows drawn under group caps (nr_row_logprob_capped; include/nrhip.h, K16): the law of
+    score_sample(..., group, group_cap) -- at step j the candidates are the eligible news not yet taken whose group has fewer
+    than group_cap entries in the row so far.  `row_ids`: integer tensor [U, k <= 128], 0 (or anything outside [1, V)) = fill.
+    `bases` = (logsum, gmax), each [U, n_groups + 1] -- the first two results of score_logz_groups computed with the row merged
+    into `exclude` (a third element, the count, is ignored).  `group` int32 [V] on the device, `group_cap` in [1, 128]; n_groups
+    None = the width of the bases - 1.
+    Returns (logp fp32 [U, k], total fp32 [U] = the row's sum, formed in fp64).  Fill entries give 0; an entry outside the pool
+    or with a NaN score gives NaN, is part of no sum and uses up nothing of a cap; a bad entry of a temperature tensor gives its
+    user's real entries NaN.  A live entry whose group already has group_cap live entries before it gives -inf -- the capped
+    sampler never draws it; it uses up nothing of a cap, its weight still counts at every earlier step at which its group was
+    open, and the total is -inf.  Repeats and membership in the lists are the caller's statement."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    V, N, U, dev = _vector_args("row_logprob_capped", news_vecs, user_vecs)
+    if row_ids.dim() != 2 or row_ids.shape[0] != U or row_ids.is_floating_point() or row_ids.device != dev:
+        raise RuntimeError(f"row_logprob_capped: row_ids must be an integer tensor [U = {U}, k] on {dev}, got {tuple(row_ids.shape)} "
+                           f"{row_ids.dtype} on {row_ids.device}")
+    k = row_ids.shape[1]
+    bl, bm = bases[0], bases[1]
+    G = int(n_groups) if n_groups is not None else (bl.shape[1] - 1 if isinstance(bl, torch.Tensor) and bl.dim() == 2 else 0)
+    for name, t in (("base logsum", bl), ("base gmax", bm)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U, G + 1) or not t.is_floating_point() or t.device != dev:
+            raise RuntimeError(f"row_logprob_capped: {name} must be a floating point tensor of shape ({U}, n_groups + 1 = {G + 1}) on {dev}, "
+                               f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    gr = _group_args("row_logprob_capped", group, V, dev)
+    _need_gpu(news_vecs, user_vecs, row_ids, prior, stamp, window, tau_t, bl, bm, gr)      # after the shapes: those refusals need no GPU
+    logp = torch.empty(U, k, dtype=torch.float32, device=dev)
+    total = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return logp, total
+    bl, bm = bl.detach().to(torch.float32).contiguous(), bm.detach().to(torch.float32).contiguous()
+    ids = row_ids.detach().to(torch.int32).contiguous()
+    pr, st, win = _pool_args("row_logprob_capped", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("row_logprob_capped", temperature, U, dev)
+    d = _lib.LogprobCappedDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                               ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=k, row_ids=ptr(ids), ld_ids=k, group=ptr(gr),
+                               group_cap=int(group_cap), n_groups=G, tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl),
+                               ld_base=G + 1, out_logp=ptr(logp), out_total=ptr(total), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
+                               ld_window=2 if win is not None else 0)
+    check(_lib.lib().nr_row_logprob_capped(C.byref(d), _stream()), "nr_row_logprob_capped")
+    return logp, total
+
+
 @torch.no_grad()
 def mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, group=None, group_cap=None):
     """Diversified re-ranking of a pool (nr_mmr_select; include/nrhip.h, K11): Maximal Marginal Relevance over the M places of

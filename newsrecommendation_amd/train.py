@@ -436,8 +436,8 @@ def sample_propensity(model, news_vecs, hist_idx, mask, ids, temperature, exclud
     Returns (logp fp32 [U, k], total fp32 [U]) on the device.  Fill entries (id 0, a short row) give 0.  temperature 0 -- as a
     float or as an entry of a [U] tensor -- gives NaN: such a row is recommend's, deterministic, its propensity is 1 and there
     is nothing to reweight by.  Seed, draw and user keys do not enter: the law does not depend on them.
-    Group caps are not supported: under caps the mass that is left at a step needs per-group partitions.  Passing news_group or
-    group_cap raises ValueError."""
+    Group caps are not part of this function: under caps the mass that is left at a step needs per-group partitions, which is
+    what sample_propensity_capped computes.  Passing news_group or group_cap here raises ValueError."""
     if news_group is not None or group_cap is not None:
         raise ValueError("sample_propensity: rows drawn under group caps (news_group / group_cap) have no propensity here: "
                          "the remaining mass under caps needs per-group partitions")
@@ -453,6 +453,56 @@ def sample_propensity(model, news_vecs, hist_idx, mask, ids, temperature, exclud
     tau = _device_temperature(temperature, U, device)
     base = ops.score_logz(news_vecs, user, tau, exclude=lists, **kw)
     return ops.row_logprob(news_vecs, user, rows, tau, base, True, **kw)
+
+
+def _group_order(news_group, groups, device):
+    """news_group as the int32 tensor on `device` and its ops.GroupOrder (`groups` if the caller built one already)."""
+    group = torch.as_tensor(news_group).to(device=device, dtype=torch.int32)
+    return group, (groups if groups is not None else ops.GroupOrder(group))
+
+
+@torch.no_grad()
+def log_partition_groups(model, news_vecs, hist_idx, mask, temperature, news_group, exclude_history=True, batch_size=8192, prior=None,
+                         news_time=None, window=None, seen=None, groups=None):
+    """log_partition per group (ops.score_logz_groups; include/nrhip.h, K15): for every user and every bin -- the groups
+    0 .. G-1 of news_group [N+1] (MIND's category column, say) and bin G for the news of no group (negative id) -- over the
+    news recommend would consider for that user under the same arguments.  Returns (logsum fp32, gmax fp32, count int32), each
+    [U, G + 1] on the device: gmax the bin's best eligible score, count its eligible news, logsum = log sum exp((score - gmax) /
+    temperature); an empty bin gives (-inf, -inf, 0).  With log_partition's log Z = smax / temperature + logsum,
+    exp(gmax / temperature + logsum - log Z) is the category's share of the user's exposure under recommend_sample at this
+    temperature.  groups: an ops.GroupOrder of news_group built beforehand (once per corpus); None builds it here."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    _, order = _group_order(news_group, groups, news_vecs.device)
+    return ops.score_logz_groups(news_vecs, user, _device_temperature(temperature, user.shape[0], news_vecs.device), order, exclude=exclude, **kw)
+
+
+@torch.no_grad()
+def sample_propensity_capped(model, news_vecs, hist_idx, mask, ids, temperature, news_group, group_cap, exclude_history=True, batch_size=8192,
+                             prior=None, news_time=None, window=None, seen=None, groups=None):
+    """sample_propensity for rows drawn under group caps: for ids [U, k] returned by recommend_sample called with the SAME model,
+    histories, temperature, exclusions, pools, news_group and group_cap, logp[u, j] = log P(entry j is drawn at step j | entries
+    0 .. j-1 are taken) under the law those rows follow -- at every step the softmax over the eligible news not yet taken whose
+    group has fewer than group_cap entries in the row so far -- and total[u] = their sum = log P(the row, in this order).
+    Two fused passes, no [U, V] matrix: the log-partition PER GROUP over everything eligible except the row (ops.score_logz_groups
+    with the row merged into the exclusion lists), then the row on top of these bases in fp64 (ops.row_logprob_capped): the mass
+    left at a step is the sum over the groups still open, every term positive.
+    Returns (logp fp32 [U, k], total fp32 [U]) on the device.  Fill entries (id 0, a short row) give 0; temperature 0 gives NaN,
+    as in sample_propensity; an entry the capped sampler cannot have drawn (its group was full) gives -inf.
+    groups: an ops.GroupOrder of news_group built beforehand (once per corpus); None builds it here."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    device = news_vecs.device
+    U = user.shape[0]
+    group, order = _group_order(news_group, groups, device)
+    rows = torch.as_tensor(ids).to(device=device, dtype=torch.int32)
+    if rows.dim() != 2 or rows.shape[0] != U:
+        raise RuntimeError(f"sample_propensity_capped: ids must be [U = {U}, k], got {tuple(rows.shape)}")
+    taken = ops.ExclusionLists(rows)
+    lists = taken if exclude is None else (exclude if isinstance(exclude, ops.ExclusionLists) else ops.ExclusionLists(exclude)).merged(taken)
+    tau = _device_temperature(temperature, U, device)
+    bases = ops.score_logz_groups(news_vecs, user, tau, order, exclude=lists, **kw)
+    return ops.row_logprob_capped(news_vecs, user, rows, tau, bases, group, group_cap, n_groups=order.n_groups, **kw)
 
 
 def _in_lists(exclude, tg):
