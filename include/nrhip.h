@@ -63,7 +63,10 @@ int nr_abi_sizes(size_t* out, int n);
  * each call: gradients are bit-reproducible from run to run.  scratch: DEVICE memory, ZERO filled, 8 bytes per element of
  * the largest set of accumulated outputs of one call (e.g. 3N*(d_model+1) + table_rows*d_model for nr_mhsa_bwd); the
  * library leaves it zero filled after every call.  scratch == NULL switches the mode off.  One stream at a time.
- * Gather sources need `table_rows` in their descriptor in this mode.                                               */
+ * Gather sources need `table_rows` in their descriptor in this mode.
+ * Not covered: nr_embed_gather_bwd (K1).  That stand-alone entry takes no table size, so it registers no range and adds
+ * with fp32 atomics in either mode; the deterministic table gradients are those of the fused gather sources, which carry
+ * `table_rows` (nr_mhsa_bwd, nr_conv1d_k3_bwd_table, nr_linear_bwd).                                                  */
 int nr_set_deterministic(void* scratch, size_t bytes);
 int nr_set_option(const char* name, int value);
 int nr_get_option(const char* name);
@@ -102,7 +105,10 @@ int nr_pack_conv_w_t(const float* w, int N, int D, void* dst, int ld, int dtype,
  * K1  embedding row gather — nn.Embedding(padding_idx=0) lookup,
  * src/model/NRMS.py:28, src/model/NAML.py:48-50, and the eval-time news-vector gather
  * src/dataset.py:68,72.  out[m, 0:cols] = table[ids[m*ids_stride], 0:cols] (fp32 out).
- * bwd: dtable[ids[m], :] += dout[m, :] for ids[m] != 0 (padding_idx row gets no gradient). */
+ * bwd: dtable[ids[m], :] += dout[m, :] for ids[m] != 0 (padding_idx row gets no gradient).
+ * The bwd adds with fp32 atomics with and without deterministic mode (it has no table size to register a fixed-point range
+ * with, see nr_set_deterministic, and leaves the scratch untouched): with repeated ids its last bits depend on the arrival
+ * order.  The fused gather sources, which carry `table_rows`, are the deterministic ones.      */
 int nr_embed_gather_fwd(const void* table, int ld_table, int dtype, const int32_t* ids, int n_ids,
                         int ids_stride, int cols, float* out, int ld_out, nr_stream_t stream);
 int nr_embed_gather_bwd(const float* dout, int ld_dout, const int32_t* ids, int n_ids, int ids_stride,
