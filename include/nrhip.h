@@ -252,7 +252,9 @@ int nr_sdpa_long_bwd(const void* qkv, const float* mask, const void* dy, void* d
 
 /* Index validation (what torch's embedding / cross_entropy raise IndexError for; the kernels themselves trust their
  * indices).  Counts the entries of ids[i*stride], i < count, outside [0, rows) into *bad (DEVICE int32, accumulated:
- * zero it first).  The Python layer calls it when ops.CHECK_INDICES is on and raises IndexError.                */
+ * zero it first).  nr_check_labels does the same for int64 labels outside [0, classes), compared as int64 (2^32 is
+ * bad, not 0).  rows / classes == 0 makes every entry bad; count == 0 launches nothing.  The Python layer calls them
+ * when ops.CHECK_INDICES is on and raises IndexError.                                                            */
 int nr_check_ids(const int32_t* ids, int count, int stride, int rows, int32_t* bad, nr_stream_t stream);
 int nr_check_labels(const int64_t* label, int count, int classes, int32_t* bad, nr_stream_t stream);
 
@@ -937,7 +939,9 @@ int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream);
  *   history [B, H, F] = news_combined[hist_idx]
  *   candidate [B, 1+K, F]: slot j holds neg[j] for j < label, pos for j == label, neg[j-1] beyond (src/dataset.py:46)
  * bad (optional, DEVICE int32, accumulated): number of out-of-range indices / labels met (row 0 / label 0 is used
- * instead; numpy / torch would raise IndexError).                                                               */
+ * instead; numpy / torch would raise IndexError).  An index outside [0, n_rows) counts once per slot (not once per
+ * feature), a label outside [0, K] once per impression, compared as int64; the slots of that impression are then
+ * checked in the order label 0 gives.  H == 0 and K == 0 are valid (hist_idx / history resp. neg_idx may be NULL).  */
 int nr_assemble_batch(const int32_t* news_combined, int n_rows, int F, const int32_t* hist_idx, const int32_t* pos_idx,
                       const int32_t* neg_idx, const int64_t* label, int B, int H, int K, int32_t* history, int32_t* candidate,
                       int32_t* bad, nr_stream_t stream);
@@ -945,7 +949,8 @@ int nr_assemble_batch(const int32_t* news_combined, int n_rows, int F, const int
 /* One encoder batch, Model.forward's `torch.cat([candidate titles, history titles])` (the reference encodes the two in two
  * passes, src/model/NRMS.py:87,90 / src/model/NAML.py forward; one pass here) plus the "is this title's vector used at all"
  * flags of the rows: out [rows_a + rows_b, F] = [a ; b], flags [rows_a + rows_b] = [1 .. 1 ; mask_b != 0] (flags and mask_b
- * optional; a NULL mask_b flags every row).                                                                          */
+ * optional; a NULL mask_b flags every row).  mask_b != 0 is the comparison of numbers: +0 and -0 give 0, subnormals and
+ * NaN give 1.  rows_a == 0 and rows_b == 0 are valid (both: nothing is launched).                                    */
 int nr_stack_rows(const int32_t* a, int rows_a, const int32_t* b, int rows_b, int F, const float* mask_b, int32_t* out,
                   int32_t* flags, nr_stream_t stream);
 
@@ -959,7 +964,14 @@ int nr_stack_rows(const int32_t* a, int rows_a, const int32_t* b, int rows_b, in
  *            fixed order (bit-reproducible)
  * max_cand: largest candidate count of an impression (host knowledge of `offsets`); at most 4096.
  * Ties between scores: descending order with the LATER candidate first (np.argsort(kind="stable")[::-1]); numpy's
- * default sort leaves the order of tied scores unspecified.                                                    */
+ * default sort leaves the order of tied scores unspecified.  +0 and -0 tie; +-inf and subnormal scores order as numbers.
+ * A label != 0 is a positive, and every positive has gain 1 (the reference's labels are 0 / 1, where its 2^y - 1 is the
+ * same); an impression without candidates is skipped like any other single-class one.  AUC is the Mann-Whitney
+ * statistic with half credit for a positive and a negative that tie.
+ * Outside the contract: NaN scores (a NaN compares false with everything, so a positive with a NaN score is counted at
+ * rank 0 without any AUC credit and a NaN negative neither outranks nor ties anything: the row is finite but means
+ * nothing -- filter NaN before the call), and an impression longer than max_cand (max_cand is not checked against
+ * `offsets` on the device; a longer impression overruns its wave's share of LDS).                                */
 size_t nr_eval_metrics_workspace_bytes(int n_imp);
 int nr_eval_metrics(const float* score, const int32_t* label, const int32_t* offsets, int n_imp, int max_cand, double* per_imp,
                     size_t per_imp_bytes, double* sums, nr_stream_t stream);
@@ -976,7 +988,10 @@ int nr_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, s
 /* The same update, plus the packed bf16 GEMM operands of parameter matrices that live in the bucket (what nr_cast_pad would
  * make of the new values -- bit-identical -- written in the same pass).  Job j: the matrix at elements [first, first + count)
  * of the bucket, `cols` columns per row (a multiple of 4, as is `first`), goes to dst [count / cols, ld_dst] bf16; padding
- * columns of dst are not touched (nr_cast_pad zeroed them when the operand was first made).  At most NR_ADAM_PACK_MAX jobs. */
+ * columns of dst are not touched (nr_cast_pad zeroed them when the operand was first made).  At most NR_ADAM_PACK_MAX jobs.
+ * Refused before any launch: more jobs, first % 4 != 0, cols < 4 or cols % 4 != 0, count % cols != 0, count >= 2^32,
+ * first + count > n, ld_dst < cols or ld_dst % 4 != 0, a dst that is not 8-byte aligned.  Jobs do not reach the n % 4 tail
+ * elements, and elements outside every job have no packed copy written.                                              */
 #define NR_ADAM_PACK_MAX 4
 typedef struct {
   size_t first, count;
