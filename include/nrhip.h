@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -928,6 +928,80 @@ typedef struct {
   int ld_window;
 } nr_logprob_capped_desc;
 int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K17  expected news vector under the full softmax: the gradient of K13's log-partition.  For
+ *   nll(u, t) = -(s_ut - max_u) / tau_u + logsum_u     (K14, independent entries)
+ *   d nll(u, t) / d user_u = (E_u - news[t]) / tau_u,   E_u = sum_{v eligible} p(v | u) news_v,
+ *   p(v | u) = exp((s_uv - max_u) / tau_u - logsum_u)
+ * E_u is the softmax-weighted mean news vector over exactly the news K13 sums over: same score bits, same pools, same CSR
+ * lists, through the same definitions (pool_key, csrc/nr_score_tile.h; the list cursor and masks, csrc/nr_logz_stream.h).  A
+ * news that is not a term of log Z has weight 0.  No [U, V] probability matrix exists: per chunk of 128 news the scoring tile
+ * is followed by a second MFMA contraction out[TU, N] += P[TU, 128] . news[128, N] over the same (L2-hot) rows.
+ * metrics.expect_reference states the contract on the host.
+ *   base_max, base_logsum   [U] fp32: out_max / out_logsum of a K13 call with the SAME vectors, lists, pools and temperatures.
+ *               The pass is two-pass by design: with the base known every weight is p <= 1 and no accumulator is rescaled.
+ *               p is formed as expf(fmaf(s - max, 1 / tau, -logsum)), 1 / tau ONE fp32 division per user (s == max: the
+ *               argument is -logsum, also where 1 / tau overflows).
+ *   weight      optional [U] fp32 (NULL = 1): the row's upstream-gradient scale
+ *   sub_ids, sub_w   optional, both or neither: [U, ld_sub] int32 / fp32, T <= NR_TOPK_MAX_K columns.  Ids outside [1, V) are fill
+ *               and skipped; a repeated id is simply two entries.
+ *   scale_inv_tau   nonzero: the finished row is multiplied by 1 / tau_u
+ *   out         [U, ld_out] fp32:  out[u] = (weight_u E_u - sum_t sub_w[u, t] news[sub_ids[u, t]]) (* 1 / tau_u): with
+ *               weight = sum_t g_t, sub_w = g the whole gradient of sum_t g_t nll(u, t) with respect to user_u in one call
+ *   out_mass    optional [U] fp32: sum_v p(v | u) -- 1 up to rounding when the base matches the arguments, a cheap check
+ *   edge cases  nothing eligible (base_max = -inf, whatever tau_u holds): E = 0, mass 0.  A tau_u entry that is <= 0, NaN or infinite, or a NaN in the
+ *               user's base: a row of NaN and mass NaN; every other user is untouched.  Components of a news row that are not
+ *               finite count as 0 in E: such a row's score is NaN or infinite for every user, so it has weight 0 (or its
+ *               +inf score makes the base, and with it the row, NaN).
+ * Bits.  Per-segment partials as in K13 would cost U * 256 * N floats, so a slice of the corpus (a run of whole segments of
+ * K13's plan, a function of V and splits) accumulates in fp32 registers: per (user, component) one MFMA chain over the slice's
+ * chunks ascending, per row-part of the chunk (128, 64 or 32 rows: a function of N), the parts added in ascending order; one
+ * [N] partial per (user, slice) plus its mass (per-lane fp64 chains, an xor butterfly); a second kernel merges the slices in
+ * ascending order in fp64, applies weight, the gather-subtract (fp64, t ascending) and 1 / tau, and rounds to fp32 once.  For
+ * a fixed explicit `splits`, row u depends on that user's inputs and V only -- not on the other users, the place in the tile,
+ * or U.  splits = 0 lets the library choose by U: the bits may then vary with the batch.  Across different `splits` rows agree
+ * within the error bound (derived in DESIGN.md section 5) against the exact result E* of the fp32 inputs:
+ *   |E_c - E*_c| <= kappa 2^-24 A_c,   A_c = sum_v p*_v |news_vc|,   kappa = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 26
+ *   |mass - 1|   <= (6 C + 5 ln n + 7 K + 23) 2^-24
+ * with n the eligible news, C = max_v |s_v| / tau, G = max_v (sum_c |user_c news_vc| + |prior_v|) / tau (the score chain: N fma
+ * roundings and the prior's add, twice: numerator and partition), K = 2 * seg / 128 the lane chain of K13's base, and L = 128 *
+ * (chunks of the longest slice) the fp32 accumulation chain of the second contraction.
+ *   ws          nr_score_expect_workspace_bytes(d): U * slices * (N * 4 + 8) bytes, rounded to 8 (0 = bad descriptor)
+ * Refused before any launch: what K13 refuses; a null base_max / base_logsum / out; sub_ids without sub_w or the reverse; T
+ * outside [1, NR_TOPK_MAX_K] or ld_sub < T when sub_ids is given; ld_out < N or an out that is not 16-byte aligned; an
+ * undersized workspace.  Layout: nr_logz_desc's fields in its order up to tau_u, then this call's, then the shared tail.      */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 */
+  const float* base_logsum;    /* [U]: out_logsum of K13 */
+  const float* weight;         /* optional [U] */
+  const int32_t* sub_ids;      /* optional [U, ld_sub]; with sub_w */
+  const float* sub_w;          /* optional [U, ld_sub]; with sub_ids */
+  int ld_sub, T;
+  int scale_inv_tau;
+  float* out;                  /* [U, ld_out] */
+  int ld_out;
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_desc;
+size_t nr_score_expect_workspace_bytes(const nr_expect_desc* d);
+int nr_score_expect(const nr_expect_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

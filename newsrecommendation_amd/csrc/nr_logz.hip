@@ -27,31 +27,13 @@
 //                           alone (independent).
 #include <math.h>
 
-#include "nr_score_tile.h"
+#include "nr_logz_stream.h"
 
 namespace {
 
-constexpr int LZ_MAX_SEGS = 256;
-constexpr float LZ_INF = __builtin_inff();
-
-struct LogzPlan {
-  int TU, seg, nseg, splits, segs_per;
-};
-// The tile is what the vectors and the staging buffers leave room for, as in the counting pass of nr_rank.hip.  seg and nseg
-// depend on V alone; `splits` (0: fill the chip, score_auto_splits) only groups whole segments into slices
-inline LogzPlan lz_plan(int U, int V, int N, int splits) {
-  LogzPlan p;
-  p.TU = score_user_tile(N, 0);
-  const long per = (long)TK_ROWS * LZ_MAX_SEGS;
-  p.seg = TK_ROWS * (int)(((long)V - 1 + per - 1) / per);
-  p.nseg = (int)(((long)V - 1 + p.seg - 1) / p.seg);
-  long s = splits > 0 ? splits : score_auto_splits(U, V, p.TU, LZ_MAX_SEGS);   // nseg <= chunks, nseg <= LZ_MAX_SEGS
-  if (s > p.nseg) s = p.nseg;
-  if (s < 1) s = 1;
-  p.segs_per = (int)((p.nseg + s - 1) / s);
-  p.splits = (p.nseg + p.segs_per - 1) / p.segs_per;   // no empty slice
-  return p;
-}
+// The tile is what the vectors and the staging buffers leave room for, as in the counting pass of nr_rank.hip (the segments and
+// slices: lz_plan_tile, nr_logz_stream.h)
+inline LogzPlan lz_plan(int U, int V, int N, int splits) { return lz_plan_tile(U, V, score_user_tile(N, 0), splits); }
 
 struct LogzArgs {
   const float* news;
@@ -114,49 +96,9 @@ __global__ __launch_bounds__(TK_THREADS) void logz_stream_kernel(LogzArgs a, Csr
     s[i] = 0.f;
     cnt[i] = 0;
   }
-  // LISTS: the cursor of every user of the wave = the first entry of its segment that is >= v_lo.  A 64-ary search, the users of
-  // the wave side by side (their probes are independent loads): answer in [lo, hi], 64 probes lo + lane * step a round; ascending
-  // entries make "probe < v_lo" a prefix of p lanes, which leaves (lo + (p - 1) step, lo + p step].  Every index formed lies in
-  // [lo, hi) within the clamped segment; a round shrinks an open range below its step, so the loop ends whatever the entries hold.
+  // LISTS: the cursor of every user of the wave = the first entry of its segment that is >= v_lo (LZ_SEEK, nr_logz_stream.h)
   int32_t cur[PER_WAVE], end[PER_WAVE];
-  if constexpr (LISTS) {
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-      const int u = u0 + wave + TK_WAVES * i;
-      cur[i] = end[i] = 0;
-      if (u < a.U) ca.segment(u, cur[i], end[i]);
-    }
-    int32_t hi[PER_WAVE];
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) hi[i] = end[i];
-    for (;;) {
-      int32_t val[PER_WAVE], step[PER_WAVE];
-#pragma unroll
-      for (int i = 0; i < PER_WAVE; ++i) {
-        const int32_t n = hi[i] - cur[i];
-        step[i] = (n + 63) >> 6;
-        const long idx = (long)cur[i] + (long)lane * step[i];
-        val[i] = n > 0 && idx < hi[i] ? ca.ids[idx] : 0x7fffffff;
-      }
-      bool open = false;
-#pragma unroll
-      for (int i = 0; i < PER_WAVE; ++i) {
-        const int32_t n = hi[i] - cur[i];
-        if (n <= 0) continue;
-        const long idx = (long)cur[i] + (long)lane * step[i];
-        const int p = __popcll(__ballot(idx < hi[i] && (long)val[i] < v_lo));
-        if (p == 0) hi[i] = cur[i];
-        else if (step[i] == 1) { cur[i] += p; hi[i] = cur[i]; }
-        else {
-          const long nh = (long)cur[i] + (long)p * step[i];
-          cur[i] = (int32_t)((long)cur[i] + (long)(p - 1) * step[i] + 1);
-          hi[i] = nh < hi[i] ? (int32_t)nh : hi[i];
-        }
-        open = open || hi[i] > cur[i];
-      }
-      if (!open) break;
-    }
-  }
+  if constexpr (LISTS) LZ_SEEK(ca, u0, wave, lane, a.U, v_lo, cur, end)
   // POOL: lane i keeps the window of this wave's i-th user; an empty one beyond U
   int32_t w_lo = 1, w_hi = 0;
   if constexpr (POOL) {
@@ -202,20 +144,7 @@ __global__ __launch_bounds__(TK_THREADS) void logz_stream_kernel(LogzArgs a, Csr
       const int ul = wave + TK_WAVES * i;
       // LISTS: the entries inside [vc, vc + 128) are a prefix of what the cursor points at; bit r of (l0, l1) = news vc + r is listed
       u64 l0 = 0ull, l1 = 0ull;
-      if constexpr (LISTS) {
-        int32_t e = e0[i];
-        for (;;) {
-          const int c = __popcll(__ballot((long)cur[i] + lane < end[i] && (long)e < vc + TK_ROWS));
-          for (int j = 0; j < c; ++j) {
-            const uint32_t r = (uint32_t)((long)__builtin_amdgcn_readlane(e, j) - vc);
-            if (r < 64u) l0 |= 1ull << r;
-            else if (r < 128u) l1 |= 1ull << (r - 64u);
-          }
-          cur[i] += c;
-          if (c < 64) break;                                  // a full probe: the chunk may hold 64 more
-          e = (long)cur[i] + lane < end[i] ? ca.ids[(long)cur[i] + lane] : 0x7fffffff;
-        }
-      }
+      if constexpr (LISTS) LZ_LISTED(ca, e0[i], cur[i], end[i], vc, lane, l0, l1)
       uint32_t k0, k1;
       if constexpr (POOL) {
         const int32_t lo = __builtin_amdgcn_readlane(w_lo, i), hi = __builtin_amdgcn_readlane(w_hi, i);

@@ -1,6 +1,7 @@
 // The exact-fp32 scoring tile of the full-corpus passes and what every pass builds around it.  Its consumers: the top-k
 // selection and the sampled selection (nr_topk.hip), the rank counting and its named passes (nr_rank.hip), the log-partition
-// stream and the named rows of nr_row_logprob (nr_logz.hip); nr_mmr.hip takes score_key and the width check only.  All of them
+// stream and the named rows of nr_row_logprob (nr_logz.hip), the expected news vector (nr_expect.hip: the tile followed by a
+// second contraction over the chunk); nr_mmr.hip takes score_key and the width check only.  All of them
 // must give one (u, v) pair the SAME bits -- "rank <= k", "is in the top-k row" and "is a term of the partition sum" are then
 // one statement -- so there is ONE definition of the tile, of the keys, and of the rows a chunk is made of.
 //

@@ -341,6 +341,45 @@ def logz_reference(a, b=None, *, temperature, exclude=None, prior=None, stamp=No
     return logsum, smax, count
 
 
+def expect_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None, weight=None):
+    """Host statement of the expected-news-vector contract (include/nrhip.h, nr_score_expect); tests check the device against
+    it, no product path calls it.
+
+    `a` [V, N] news vectors, `b` [U, N] user vectors; `exclude` and the pools are logz_reference's, and so is what is eligible
+    (through _pooled).  Per user, over its eligible news, in float64: p_v = exp((score_v - smax) / tau_u) / sum of these, and
+    expect[u] = weight_u * sum_v p_v * a[v] (weight None = 1), mass[u] = sum_v p_v = 1.  Nothing eligible: zeros and mass 0.  A
+    temperature that is not finite and > 0, or a largest score of +-inf: a row of NaN and mass NaN.  Components of `a` that are
+    not finite count as 0 in the sum (their news has weight 0 whenever the row is not NaN).
+    Returns (expect float64 [U, N], mass float64 [U])."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scores = b @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    tau, tau_ok = _temperatures(temperature, U)
+    w = np.ones(U) if weight is None else np.asarray(weight, dtype=np.float64).reshape(U)
+    clean = np.where(np.isfinite(a), a, 0.0)
+    expect, mass = np.zeros((U, a.shape[1])), np.zeros(U)
+    for u in range(U):
+        ok = ~np.isnan(scores[u]) & pool[u]
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        x = scores[u, ok]
+        if x.size == 0:
+            continue
+        if not tau_ok[u] or not np.isfinite(x.max()):
+            expect[u], mass[u] = np.nan, np.nan
+            continue
+        p = np.exp((x - x.max()) / tau[u])
+        p = p / p.sum()
+        expect[u] = w[u] * (p @ clean[ok])
+        mass[u] = p.sum()
+    return expect, mass
+
+
 def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
     """Host statement of the row log-probability contract (include/nrhip.h, nr_row_logprob); tests check the device against it,
     no product path calls it.

@@ -1351,6 +1351,15 @@ def score_logz(news_vecs, user_vecs, temperature, exclude=None, splits=0, prior=
     return logsum, smax, count
 
 
+def _base_args(what, base, U, dev):
+    """(logsum, smax) of a score_logz result as contiguous fp32 [U] tensors."""
+    bl, bm = base[0], base[1]
+    for name, t in (("base logsum", bl), ("base smax", bm)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
+            raise RuntimeError(f"{what}: {name} must be a floating point tensor of shape ({U},) on {dev}")
+    return bl.detach().to(torch.float32).contiguous(), bm.detach().to(torch.float32).contiguous()
+
+
 @torch.no_grad()
 def row_logprob(news_vecs, user_vecs, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
     """Log-probabilities of the entries of named rows (nr_row_logprob; include/nrhip.h, K14).  `row_ids`: integer tensor
@@ -1374,11 +1383,7 @@ def row_logprob(news_vecs, user_vecs, row_ids, temperature, base, sequential, pr
     total = torch.empty(U, dtype=torch.float32, device=dev)
     if U == 0:
         return logp, total
-    bl, bm = base[0], base[1]
-    for name, t in (("base logsum", bl), ("base smax", bm)):
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
-            raise RuntimeError(f"row_logprob: {name} must be a floating point tensor of shape ({U},) on {dev}")
-    bl, bm = bl.detach().to(torch.float32).contiguous(), bm.detach().to(torch.float32).contiguous()
+    bl, bm = _base_args("row_logprob", base, U, dev)
     ids = row_ids.detach().to(torch.int32).contiguous()
     pr, st, win = _pool_args("row_logprob", V, U, dev, prior, stamp, window)
     tau, tau_u = _tau_args("row_logprob", temperature, U, dev)
@@ -1389,6 +1394,112 @@ def row_logprob(news_vecs, user_vecs, row_ids, temperature, base, sequential, pr
                          ld_window=2 if win is not None else 0)
     check(_lib.lib().nr_row_logprob(C.byref(d), _stream()), "nr_row_logprob")
     return logp, total
+
+
+def _score_expect(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, sub_ids, sub_w, scale_inv_tau):
+    """One nr_score_expect call (include/nrhip.h, K17): (out [U, N] fp32, mass [U] fp32)."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, base[0], base[1],
+              weight, sub_ids, sub_w)
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    out = torch.empty(U, N, dtype=torch.float32, device=dev)
+    mass = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return out, mass
+    bl, bm = _base_args(what, base, U, dev)
+    if weight is not None:
+        if tuple(weight.shape) != (U,) or not weight.is_floating_point() or weight.device != dev:
+            raise RuntimeError(f"{what}: weight must be a floating point tensor of shape ({U},) on {dev}")
+        weight = weight.detach().to(torch.float32).contiguous()
+    T = 0
+    if sub_ids is not None:
+        if sub_ids.dim() != 2 or sub_ids.shape[0] != U or sub_ids.is_floating_point() or tuple(sub_w.shape) != tuple(sub_ids.shape):
+            raise RuntimeError(f"{what}: the named rows must be integer ids [U = {U}, T] with weights of the same shape")
+        T = sub_ids.shape[1]
+        sub_ids = sub_ids.detach().to(torch.int32).contiguous()
+        sub_w = sub_w.detach().to(torch.float32).contiguous()
+    ex_fields, ex_keep = _exclude_args(what, exclude, U, dev, dense=False)
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    d = _lib.ExpectDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                        ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u),
+                        base_max=ptr(bm), base_logsum=ptr(bl), weight=ptr(weight), sub_ids=ptr(sub_ids), sub_w=ptr(sub_w), ld_sub=T, T=T,
+                        scale_inv_tau=1 if scale_inv_tau else 0, out=ptr(out), ld_out=N, out_mass=ptr(mass),
+                        prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_workspace_bytes(C.byref(d)), dev)    # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect(C.byref(d), _stream()), "nr_score_expect")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect(news_vecs, user_vecs, temperature, base, exclude=None, splits=0, prior=None, stamp=None, window=None, weight=None):
+    """The expected news vector under the full softmax (nr_score_expect; include/nrhip.h, K17): per user
+    E = sum_v p(v) news_vecs[v], p(v) = exp((score_v - smax) / temperature - logsum), over exactly the news score_logz sums over
+    -- the gradient of temperature * log Z with respect to the user vector -- without the [U, V] probability matrix.
+    `base` = (logsum, smax[, count]): what score_logz returned for the SAME vectors, temperature, exclude and pools.
+    `weight`: optional floating point [U], a scale per row.  The other arguments are score_logz's.
+    Returns (expect fp32 [U, N], mass fp32 [U]): mass = sum_v p(v), 1 up to rounding when the base matches the arguments.  A user
+    with nothing eligible gets zeros and mass 0; a bad entry of a temperature tensor, or a NaN base, gives that user NaN.
+    `splits`: 0 = the library chooses the number of corpus slices by U.  For a fixed splits > 0 a user's row does not depend, bit
+    for bit, on the other users of the call; across different splits rows agree to within the bound of DESIGN.md section 5."""
+    return _score_expect("score_expect", news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, None, None, False)
+
+
+class FullSoftmaxNLLFunction(Function):
+    """nll [U, T] of named targets under the full softmax over the corpus, differentiable with respect to the user vectors."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window):
+        user = user_vecs.detach()
+        U, dev = user.shape[0], user.device
+        base = score_logz(news_vecs, user, temperature, exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+        logp, _ = row_logprob(news_vecs, user, targets, temperature, base, False, prior=prior, stamp=stamp, window=window)
+        V = news_vecs.shape[0]
+        valid = (targets >= 1) & (targets < V) & ~torch.isnan(logp)
+        if isinstance(temperature, torch.Tensor):
+            valid &= ((temperature > 0) & torch.isfinite(temperature))[:, None]
+        nll = torch.where(valid, -logp, torch.zeros_like(logp))
+        ctx.save_for_backward(user, news_vecs, targets, valid, base[0], base[1])
+        ctx.rest = (temperature, exclude, splits, prior, stamp, window)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return nll, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, news_vecs, targets, valid, bl, bm = ctx.saved_tensors
+        temperature, exclude, splits, prior, stamp, window = ctx.rest
+        if g is None:
+            return (None,) * 9
+        gw = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=g.device))
+        with torch.no_grad():
+            grad, _ = _score_expect("full_softmax_nll", news_vecs, user, temperature, (bl, bm), exclude, splits, prior, stamp, window,
+                                    gw.sum(dim=1), targets, gw, True)
+            # a user none of whose targets count (all fill or invalid, a bad temperature) has no gradient: exactly 0, not 0 * NaN
+            grad = torch.where(valid.any(dim=1)[:, None], grad, torch.zeros_like(grad))
+        return (grad,) + (None,) * 8
+
+
+def full_softmax_nll(news_vecs, user_vecs, targets, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """The full-softmax negative log-likelihood of named targets, differentiable with respect to `user_vecs`: the training-side
+    counterpart of score_logz / row_logprob.  targets: integer tensor [U, T <= 128], 0 (or anything outside [1, V)) = fill.
+    Forward: score_logz, then row_logprob(sequential=False).  Returns (nll fp32 [U, T], valid bool [U, T]): nll = -logp where
+    valid and 0 elsewhere; valid is False at fill entries, at entries row_logprob gives NaN (outside the pool, a NaN score) and
+    for users whose temperature is not finite and > 0.  A target inside the user's exclusion lists is the caller's statement and
+    is not checked, as in row_logprob.
+    Backward: ONE nr_score_expect call on the saved base: grad_user = (sum_t g_t E - sum_t g_t news[target_t]) / temperature over the
+    valid entries (include/nrhip.h, K17); a user without a valid target gets exactly 0.
+    `news_vecs` is a frozen table: one that requires grad is refused.  Temperature, prior and the other arguments get no gradient."""
+    if news_vecs.requires_grad:
+        raise RuntimeError("full_softmax_nll: news_vecs requires grad, but the table is frozen here: its gradient P^T . users is a "
+                           "[V, N] reduction over every user of the call and is not part of this call (detach the table)")
+    if targets.dim() != 2 or targets.shape[0] != user_vecs.shape[0] or targets.is_floating_point():
+        raise RuntimeError(f"full_softmax_nll: targets must be an integer tensor [U = {user_vecs.shape[0]}, T], got {tuple(targets.shape)} "
+                           f"{targets.dtype}")
+    if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"full_softmax_nll: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
+    return FullSoftmaxNLLFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
 
 
 class GroupOrder:

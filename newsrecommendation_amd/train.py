@@ -519,6 +519,15 @@ def _in_lists(exclude, tg):
     return keys[at] == q
 
 
+def _not_ranked(exclude, tg, V):
+    """[U, T] bool: what rank_eval does not rank and the kernels do not look at -- fill, a listed news, a later repeat (stable sort
+    by id: the first of equal ids is the earliest entry)."""
+    srt, at = torch.sort(tg, dim=1, stable=True)
+    rep = torch.zeros_like(tg, dtype=torch.bool)
+    rep[:, 1:] = srt[:, 1:] == srt[:, :-1]
+    return (tg < 1) | (tg >= V) | _in_lists(exclude, tg) | torch.zeros_like(rep).scatter(1, at, rep)
+
+
 @torch.no_grad()
 def target_logprob(model, news_vecs, hist_idx, mask, targets, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
                    window=None, seen=None):
@@ -540,13 +549,58 @@ def target_logprob(model, news_vecs, hist_idx, mask, targets, temperature, exclu
     W = _lib.NR_TOPK_MAX_K
     logp = torch.cat([ops.row_logprob(news_vecs, user, tg[:, c:c + W].contiguous(), tau, base, False, **kw)[0] for c in range(0, tg.shape[1], W)],
                      dim=1) if tg.shape[1] else torch.empty(U, 0, dtype=torch.float32, device=device)
-    # what rank_eval does not rank and the kernel does not look at: fill, a listed news, a later repeat (stable sort by id: the
-    # first of equal ids is the earliest entry)
-    srt, at = torch.sort(tg, dim=1, stable=True)
-    rep = torch.zeros_like(tg, dtype=torch.bool)
-    rep[:, 1:] = srt[:, 1:] == srt[:, :-1]
-    not_ranked = (tg < 1) | (tg >= V) | _in_lists(exclude, tg) | torch.zeros_like(rep).scatter(1, at, rep)
-    return logp.masked_fill(not_ranked, float("nan"))
+    return logp.masked_fill(_not_ranked(exclude, tg, V), float("nan"))
+
+
+def full_softmax_loss(model, news_vecs, hist_idx, mask, targets, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
+                      window=None, seen=None):
+    """The full-softmax training loss of held-out clicks over the whole (frozen) news-vector table: target_logprob's quantity with
+    a gradient.  For targets [U, T] (0 = no entry), loss = the mean over the valid entries of
+    -[(score - smax) / temperature - logsum], the softmax taken over everything recommend would consider for that user under the
+    same arguments (exclude_history, seen, prior, news_time, window: target_logprob's).  No negative sampling, no [U, V] matrix:
+    forward and backward are fused passes over the table (ops.full_softmax_nll; include/nrhip.h, K13, K14, K17).
+    Not under no_grad: the user vectors are formed WITH gradient, batch_size users at a time, as
+    model.user_encoder(ops.embed_gather(news_vecs, hist, code), mask), so `loss` is differentiable with respect to the user
+    encoder's parameters.  news_vecs is a constant (detached): the news encoder gets no gradient from this loss.
+    An entry is valid exactly where target_logprob is not NaN: not fill, not excluded, inside the pool, not NaN-scored, no repeat
+    of an earlier entry of its row, and the user's temperature finite and > 0.
+    Returns (loss, n): loss a 0-dim fp32 tensor = sum of nll over the valid entries / n (0 when n == 0), n the number of valid
+    entries as a 0-dim int64 device tensor.  To train on more users than one call should hold, call it per chunk of users, run
+    backward() on loss * n per call -- each call's graph is freed by its own backward -- and divide the accumulated gradients by
+    the total n."""
+    device = news_vecs.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    news_vecs = news_vecs.detach().float().contiguous()
+    U, V = hist.shape[0], news_vecs.shape[0]
+    tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
+    if tg.dim() != 2 or tg.shape[0] != U:
+        raise RuntimeError(f"full_softmax_loss: targets must be [U = {U}, T], got {tuple(tg.shape)}")
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    tg = tg.masked_fill(_not_ranked(exclude, tg, V), 0)       # what target_logprob does not score is named as fill: it is in no sum
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    W = _lib.NR_TOPK_MAX_K
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.embed_gather(news_vecs, hist[a:b], code), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) else tau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        for c in range(0, tg.shape[1], W):
+            nll, valid = ops.full_softmax_nll(news_vecs, user, tg[a:b, c:c + W].contiguous(), tau_b, exclude=ex_b, **kw_b)
+            total = total + nll.sum()
+            n = n + valid.sum()
+    return total / n.clamp(min=1).to(torch.float32), n
 
 
 def _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window, news_group, group_cap, seen):
