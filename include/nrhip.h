@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -1002,6 +1002,87 @@ typedef struct {
 } nr_expect_desc;
 size_t nr_score_expect_workspace_bytes(const nr_expect_desc* d);
 int nr_score_expect(const nr_expect_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K18  the news side of the full-softmax gradient: K17 with the roles of the two operands swapped.  For
+ *   L = sum_u sum_t g_ut nll(u, t),   nll(u, t) = -(s_ut - max_u) / tau_u + logsum_u     (K14, independent entries)
+ *   d L / d news_v = D_v - sum_{(u, t): target = v} (g_ut / tau_u) user_u,
+ *   D_v = sum_u c_u p(v | u) user_u,   c_u = (sum_t g_ut) / tau_u,   p(v | u) = exp((s_uv - max_u) / tau_u - logsum_u)
+ * over exactly the pairs (u, v) that are terms of K13's sums: same score bits (an fp32 fma is commutative in its factors and the
+ * chain order is by column only, so the tile of csrc/nr_score_tile.h is used as it is with the news stationary), same pools
+ * (pool_key), same lists, row 0 never.  No [U, V] probability matrix exists: a tile of news rows stays in LDS, the users are
+ * streamed past it in chunks of 128, and the scoring tile is followed by a second MFMA contraction
+ * out[TV, N] += P[TV, 128] . users[128, N] over the same (L2-hot) rows.  metrics.expect_news_reference states the contract on the host.
+ *   excl_offsets, excl_users   optional, both or neither: [V + 1] / [n_excl] int32, for news v the ascending 0-based indices of
+ *               the users that list it: the transposed CSR of nr_topk_desc's per-user lists (ops.ExclusionLists.by_news)
+ *   base_max, base_logsum   [U] fp32: out_max / out_logsum of a K13 call with the SAME vectors, lists, pools and temperatures
+ *   weight      optional [U] fp32 (NULL = 1)
+ *   scale_inv_tau   nonzero: a user's coefficient is c_u = fl(weight_u * fl(1 / tau_u)), otherwise weight_u; one fp32 multiply
+ *               fl(c_u * p) per pair inside the stream
+ *   named_offsets, named_user, named_w   optional, all three or none: [V + 1] int32, [n_named] int32, [n_named] fp32 -- the
+ *               named terms of news v are entries named_offsets[v] .. named_offsets[v + 1] - 1.  The finalize subtracts
+ *               sum_j named_w[j] (* 1 / tau_user if scale_inv_tau) user[named_user[j]] in fp64, j ascending; an entry with
+ *               named_w == 0 or a user index outside [0, U) is skipped.  Offsets are clamped into [0, n_named].
+ *   out         [V, ld_out] fp32, or NULL: the mass-only mode (no second contraction, kernels of its own, the same mass bits)
+ *   out_mass    [V] fp32, or NULL: sum_u weight_u p(v | u), without 1 / tau, summed in fp64 -- the expected exposure of news v.
+ *               At least one of the two outputs is given.
+ *   edge cases  a pair has weight 0 exactly when v is no term of user u's K13 sum.  A user whose temperature is <= 0, NaN or
+ *               infinite, or whose base is NaN or +-inf (nothing eligible: max = -inf), contributes nothing to any row, in the
+ *               stream and in the named terms, and puts no NaN anywhere.  Components of a user row that are not finite count as
+ *               0 in the second contraction and in the named terms.  Row 0 and rows nobody can be shown are exact zeros, minus
+ *               their named terms.
+ * Bits.  The user axis [0, U) is cut the way K13 cuts the news axis (seg = 128 ceil(U / (128 * 256)) users a segment, slices =
+ * runs of whole segments; splits = 0 lets the library choose by V).  A slice accumulates in fp32 registers: per (news,
+ * component) one MFMA chain over the slice's chunks ascending, per user-part of the chunk (128, 64 or 32 users: a function of N),
+ * the parts added in ascending order; one [N] partial per (news, slice) plus its mass (per-lane fp64 chains of the exact
+ * products weight_u p, an xor butterfly); the finalize (one workgroup per news row) merges the slices in ascending order in
+ * fp64, subtracts the named terms and rounds to fp32 once.  No atomics, no arrival order.  For a fixed explicit `splits`, row
+ * v's bits depend on that row's own inputs (vector, prior, stamp, list, named terms), on the users, on U and on `splits` -- not
+ * on any other news row, nor on the row's place in the table or the tile.  Error bound (derived in DESIGN.md section 5)
+ * against the exact result of the fp32 inputs, with n, C, G the maxima over the call's live users of K17's quantities:
+ *   |out_vc - out*_vc| <= kappa 2^-24 A_vc,   A_vc = sum_u |c_u| p*_uv |user_uc| + sum_j |d_j| |user_jc|,
+ *   kappa = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 29,   d_j = named_w[j] (/ tau_user)
+ *   |mass_v - mass*_v| <= (6 C + 5 ln n + 7 K + 29) 2^-24 sum_u |weight_u| p_uv   against the p of the device's own scores
+ *               (against the p* of exact scores the score chain 2 (N + 1) G enters as well)
+ * K = 2 * seg_V / 128 the lane chain of K13's base, L = 128 * (chunks of the longest user slice).
+ *   ws          nr_score_expect_news_workspace_bytes(d): V * slices * (N * 4 + 8) bytes, rounded to 8; V * slices * 8 in the
+ *               mass-only mode (0 = bad descriptor)
+ * Refused before any launch: what K17 refuses of the shared fields; excl_users without excl_offsets or the reverse; splits
+ * above the user segments; out and out_mass both null; a null base_max / base_logsum; one or two of the three named arrays;
+ * n_named < 0; ld_out < N or an out that is not 16-byte aligned; an undersized workspace.  Layout: nr_expect_desc's fields in
+ * its order up to base_logsum, then this call's, then the shared tail.                                                       */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [V + 1]: by news */
+  const int32_t* excl_users;   /* optional [n_excl]: ascending user indices per news */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 */
+  const float* base_logsum;    /* [U]: out_logsum of K13 */
+  const float* weight;         /* optional [U] */
+  int scale_inv_tau;
+  const int32_t* named_offsets; /* optional [V + 1]; with named_user and named_w */
+  const int32_t* named_user;    /* optional [n_named] */
+  const float* named_w;         /* optional [n_named] */
+  int n_named;
+  float* out;                  /* [V, ld_out] or NULL (mass only) */
+  int ld_out;
+  float* out_mass;             /* [V] or NULL */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_news_desc;
+size_t nr_score_expect_news_workspace_bytes(const nr_expect_news_desc* d);
+int nr_score_expect_news(const nr_expect_news_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

@@ -490,6 +490,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 14) out[13] = sizeof(nr_logz_groups_desc);
   if (n >= 15) out[14] = sizeof(nr_logprob_capped_desc);
   if (n >= 16) out[15] = sizeof(nr_expect_desc);
+  if (n >= 17) out[16] = sizeof(nr_expect_news_desc);
   return NR_OK;
 }
 

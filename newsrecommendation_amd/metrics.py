@@ -380,6 +380,68 @@ def expect_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None,
     return expect, mass
 
 
+def softmax_matrix_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None):
+    """The [U, V] float64 matrix p(v | u) of the full softmax over what logz_reference calls eligible (through _pooled), which
+    the device never forms: row u sums to 1 over its eligible news and is 0 elsewhere.  A dead user -- a temperature that is not
+    finite and > 0, a largest eligible score of +-inf, nothing eligible -- has a row of zeros.  Returns (p [U, V], live bool [U])."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scores = b @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    tau, tau_ok = _temperatures(temperature, U)
+    p, live = np.zeros((U, V)), np.zeros(U, dtype=bool)
+    for u in range(U):
+        ok = ~np.isnan(scores[u]) & pool[u]
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        x = scores[u, ok]
+        if x.size == 0 or not tau_ok[u] or not np.isfinite(x.max()):
+            continue
+        w = np.exp((x - x.max()) / tau[u])
+        p[u, ok] = w / w.sum()
+        live[u] = True
+    return p, live
+
+
+def expect_news_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None, weight=None, named=None, scale_inv_tau=False):
+    """Host statement of the news side of the full-softmax gradient (include/nrhip.h, nr_score_expect_news); tests check the
+    device against it, no product path calls it.  float64 throughout.
+
+    `a` [V, N] news vectors, `b` [U, N] user vectors; `exclude` (per USER, ragged), the pools and what is eligible are
+    expect_reference's.  With p(v | u) the softmax of softmax_matrix_reference and c_u = weight_u (/ tau_u if scale_inv_tau;
+    weight None = 1):
+      out[v]  = sum_u c_u p(v | u) b[u]  -  sum_j named_w[j] (/ tau_user if scale_inv_tau) b[named_user[j]]
+      mass[v] = sum_u weight_u p(v | u)                                   (never scaled by 1 / tau)
+    named = (offsets [V + 1], users [n], w [n]): the named terms of news v are entries offsets[v] .. offsets[v + 1] - 1; an entry
+    with w == 0 is skipped.  A dead user (softmax_matrix_reference) contributes nothing, in the sum and in the named terms.
+    Components of `b` that are not finite count as 0.  Row 0 and rows nobody can be shown are zeros minus their named terms.
+    Returns (out float64 [V, N], mass float64 [V])."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    p, live = softmax_matrix_reference(a, b, temperature=temperature, exclude=exclude, prior=prior, stamp=stamp, window=window)
+    U, V = p.shape
+    tau, _ = _temperatures(temperature, U)
+    w = np.ones(U) if weight is None else np.asarray(weight, dtype=np.float64).reshape(U)
+    w = np.where(live, w, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        it = np.where(live, 1.0 / tau, 0.0) if scale_inv_tau else np.where(live, 1.0, 0.0)
+    clean = np.where(np.isfinite(b), b, 0.0)
+    out = p.T @ ((w * it)[:, None] * clean)
+    mass = p.T @ w
+    if named is not None:
+        off, nu, nw = (np.asarray(x) for x in named)
+        for v in range(V):
+            for j in range(int(off[v]), int(off[v + 1])):
+                u = int(nu[j])
+                if nw[j] != 0 and 0 <= u < U and live[u]:
+                    out[v] -= float(nw[j]) * it[u] * clean[u]
+    return out, mass
+
+
 def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
     """Host statement of the row log-probability contract (include/nrhip.h, nr_row_logprob); tests check the device against it,
     no product path calls it.

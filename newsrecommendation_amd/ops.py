@@ -1146,6 +1146,25 @@ class ExclusionLists:
         src = torch.arange(int(new_off[-1]), device=self.device) + torch.repeat_interleave(off[:-1][rows] - new_off[:-1], counts)
         return ExclusionLists.from_sorted(new_off, self.ids[src])
 
+    def by_news(self, V):
+        """The transposed lists nr_score_expect_news takes (include/nrhip.h, K18): (offsets int32 [V + 1], users int32 [nnz]), for
+        news v the ascending 0-based indices of the users that list it = users[offsets[v] : offsets[v + 1]].  Ids >= V are
+        dropped (they mean nothing to the kernels).  Torch index arithmetic on the device of the lists: one sort of the keys
+        id * 2^31 + user, bincount -> offsets.  The last result is kept with the object (the lists are not meant to be edited in
+        place), so the calls of one batch of users transpose once."""
+        V = int(V)
+        kept = getattr(self, "_by_news", None)
+        if kept is not None and kept[0] == V and kept[1] is self.offsets and kept[2] is self.ids:
+            return kept[3]
+        users, ids = self._pairs()
+        keep = ids < V
+        keys = torch.sort((ids[keep] << self._ID_BITS) + users[keep]).values
+        offsets = torch.zeros(V + 1, dtype=torch.int64, device=self.device)
+        offsets[1:] = torch.cumsum(torch.bincount(keys >> self._ID_BITS, minlength=V), 0)
+        out = offsets.to(torch.int32), (keys & ((1 << self._ID_BITS) - 1)).to(torch.int32)
+        self._by_news = (V, self.offsets, self.ids, out)
+        return out
+
     def merged(self, other):
         """The per-user union with `other` (an ExclusionLists of the same U, or anything the constructor takes)."""
         if not isinstance(other, ExclusionLists):
@@ -1500,6 +1519,179 @@ def full_softmax_nll(news_vecs, user_vecs, targets, temperature, exclude=None, s
     if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
         raise RuntimeError(f"full_softmax_nll: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
     return FullSoftmaxNLLFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
+
+
+def _score_expect_news(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, named, scale_inv_tau, rows):
+    """One nr_score_expect_news call (include/nrhip.h, K18): (out [V, N] fp32 or None, mass [V] fp32).  named: None or (offsets
+    int32 [V + 1], users int32 [n], w fp32 [n]) on the device."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, base[0], base[1],
+              weight, *(named or ()))
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    if U == 0:                                                 # nobody: zeros, nothing to launch
+        return (torch.zeros(V, N, dtype=torch.float32, device=dev) if rows else None), torch.zeros(V, dtype=torch.float32, device=dev)
+    out = torch.empty(V, N, dtype=torch.float32, device=dev) if rows else None     # the finalize writes every row
+    mass = torch.empty(V, dtype=torch.float32, device=dev)
+    bl, bm = _base_args(what, base, U, dev)
+    if weight is not None:
+        if tuple(weight.shape) != (U,) or not weight.is_floating_point() or weight.device != dev:
+            raise RuntimeError(f"{what}: weight must be a floating point tensor of shape ({U},) on {dev}")
+        weight = weight.detach().to(torch.float32).contiguous()
+    if exclude is not None and not isinstance(exclude, ExclusionLists):
+        if not isinstance(exclude, torch.Tensor) or exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"{what}: exclude must be a tensor [U = {U}, E] or an ExclusionLists")
+        exclude = ExclusionLists(exclude)
+    ex_off = ex_users = None
+    if exclude is not None:
+        if exclude.U != U or exclude.device != dev:
+            raise RuntimeError(f"{what}: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
+        ex_off, ex_users = exclude.by_news(V)
+    n_excl = 0 if ex_users is None else ex_users.numel()
+    n_off = n_user = n_w = None
+    if named is not None:
+        n_off, n_user, n_w = named
+        if tuple(n_off.shape) != (V + 1,) or n_user.dim() != 1 or tuple(n_w.shape) != tuple(n_user.shape):
+            raise RuntimeError(f"{what}: the named terms must be offsets [V + 1 = {V + 1}] with users and weights of one length")
+        n_off, n_user, n_w = n_off.to(torch.int32).contiguous(), n_user.to(torch.int32).contiguous(), n_w.detach().to(torch.float32).contiguous()
+        if n_user.numel() == 0:
+            n_off = n_user = n_w = None
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    d = _lib.ExpectNewsDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                            ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits),
+                            excl_offsets=ptr(ex_off) if n_excl else None, excl_users=ptr(ex_users) if n_excl else None, n_excl=n_excl,
+                            tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl), weight=ptr(weight),
+                            scale_inv_tau=1 if scale_inv_tau else 0, named_offsets=ptr(n_off), named_user=ptr(n_user), named_w=ptr(n_w),
+                            n_named=0 if n_user is None else n_user.numel(), out=ptr(out), ld_out=N, out_mass=ptr(mass),
+                            prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_news_workspace_bytes(C.byref(d)), dev)    # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_news(C.byref(d), _stream()), "nr_score_expect_news")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_news(news_vecs, user_vecs, temperature, base, exclude=None, splits=0, prior=None, stamp=None, window=None, weight=None, rows=True):
+    """The news side of score_expect (nr_score_expect_news; include/nrhip.h, K18): per news
+    D_v = sum_u weight_u p(v | u) user_vecs[u], p(v | u) = exp((score_uv - smax_u) / temperature - logsum_u), over exactly the
+    pairs score_logz sums over -- the gradient of sum_u weight_u temperature log Z_u with respect to the news vector -- without
+    the [U, V] probability matrix.  `base`, `exclude` (PER USER, as everywhere: an ExclusionLists or a tensor [U, E]; it is
+    transposed here with ExclusionLists.by_news), the pools and `weight` are score_expect's.
+    Returns (out fp32 [V, N] or None, mass fp32 [V]): mass[v] = sum_u weight_u p(v | u), the expected exposure of news v.
+    rows=False is the mass-only mode: no second contraction, `out` is None, the same mass bits.  A user whose temperature is not
+    finite and > 0, whose base is NaN or infinite, or who has nothing eligible contributes nothing; row 0 is zeros.
+    `splits`: 0 = the library chooses the number of USER slices by V.  For a fixed splits > 0 a row's bits do not depend on the
+    other news rows or on its place in the table; across different splits rows agree within the bound of DESIGN.md section 5."""
+    return _score_expect_news("score_expect_news", news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, None,
+                              False, rows)
+
+
+def _named_by_news(targets, gw, V):
+    """The named terms of K18 from targets [U, T] and their weights gw [U, T] (0 = does not count): entries with gw != 0 and a
+    target in [1, V), by a STABLE sort on the news id, so within a news they come (user, t) ascending.  Returns (offsets int32
+    [V + 1], users int32 [n], w fp32 [n])."""
+    U, T = targets.shape
+    tg = targets.reshape(-1).to(torch.int64)
+    keep = (gw.reshape(-1) != 0) & (tg >= 1) & (tg < V)
+    at = torch.nonzero(keep).reshape(-1)                       # ascending flat index u * T + t
+    order = torch.sort(tg[at], stable=True).indices
+    at = at[order]
+    offsets = torch.zeros(V + 1, dtype=torch.int64, device=targets.device)
+    offsets[1:] = torch.cumsum(torch.bincount(tg[at], minlength=V), 0)
+    return offsets.to(torch.int32), (at // T).to(torch.int32), gw.reshape(-1)[at].to(torch.float32)
+
+
+class FullSoftmaxNLLJointFunction(Function):
+    """nll [U, T] of named targets under the full softmax over the corpus, differentiable with respect to the user vectors (one
+    K17 call) and the news-vector table (one K18 call)."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window):
+        user, news = user_vecs.detach(), news_vecs.detach()
+        base = score_logz(news, user, temperature, exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+        logp, _ = row_logprob(news, user, targets, temperature, base, False, prior=prior, stamp=stamp, window=window)
+        V = news.shape[0]
+        valid = (targets >= 1) & (targets < V) & ~torch.isnan(logp)
+        if isinstance(temperature, torch.Tensor):
+            valid &= ((temperature > 0) & torch.isfinite(temperature))[:, None]
+        nll = torch.where(valid, -logp, torch.zeros_like(logp))
+        ctx.save_for_backward(user, news, targets, valid, base[0], base[1])
+        ctx.rest = (temperature, exclude, splits, prior, stamp, window)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return nll, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, news, targets, valid, bl, bm = ctx.saved_tensors
+        temperature, exclude, splits, prior, stamp, window = ctx.rest
+        if g is None:
+            return (None,) * 9
+        gw = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=g.device))
+        grad_user = grad_news = None
+        with torch.no_grad():
+            if ctx.needs_input_grad[0]:
+                grad_user, _ = _score_expect("full_softmax_nll_joint", news, user, temperature, (bl, bm), exclude, splits, prior, stamp, window,
+                                             gw.sum(dim=1), targets, gw, True)
+                # a user none of whose targets count (all fill or invalid, a bad temperature) has no gradient: exactly 0, not 0 * NaN
+                grad_user = torch.where(valid.any(dim=1)[:, None], grad_user, torch.zeros_like(grad_user))
+            if ctx.needs_input_grad[1]:
+                # K18 takes the user slices by its own plan: `splits` is K13's / K17's cut of the news axis and does not apply
+                grad_news, _ = _score_expect_news("full_softmax_nll_joint", news, user, temperature, (bl, bm), exclude, 0, prior, stamp, window,
+                                                  gw.sum(dim=1), _named_by_news(targets, gw, news.shape[0]), True, True)
+        return (grad_user, grad_news) + (None,) * 7
+
+
+def full_softmax_nll_joint(news_vecs, user_vecs, targets, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """full_softmax_nll, differentiable with respect to `user_vecs` AND the table `news_vecs`: either may require grad.  The
+    forward is full_softmax_nll's (score_logz, then row_logprob(sequential=False)), bit for bit, and returns (nll fp32 [U, T],
+    valid bool [U, T]) as it does.  Backward: grad_user is full_softmax_nll's single nr_score_expect call (K17), bit for bit;
+    grad_news [V, N] is ONE nr_score_expect_news call (include/nrhip.h, K18) with weight = sum_t g_t, the 1 / temperature scale
+    inside, and the valid targets as its named terms (stable sort by news id; entries with g = 0 and invalid entries dropped):
+      grad_news[v] = sum_u (sum_t g_ut) / tau_u p(v | u) user_u  -  sum_{(u, t): target = v} g_ut / tau_u user_u.
+    News that are eligible for nobody and named by nobody get an exactly zero row; row 0 always.  A pass whose input does not
+    require grad is not launched.  Temperature, prior and the other arguments get no gradient."""
+    if targets.dim() != 2 or targets.shape[0] != user_vecs.shape[0] or targets.is_floating_point():
+        raise RuntimeError(f"full_softmax_nll_joint: targets must be an integer tensor [U = {user_vecs.shape[0]}, T], got {tuple(targets.shape)} "
+                           f"{targets.dtype}")
+    if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"full_softmax_nll_joint: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
+    return FullSoftmaxNLLJointFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
+
+
+class NewsGatherFunction(Function):
+    """out[i] = table[ids[i]] with a gradient for the table: nr_gather_cast_fwd forward, nr_embed_gather_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, table, ids, code):
+        ctx.save_for_backward(ids)
+        ctx.table_shape = tuple(table.shape)
+        return embed_gather(table, ids, code)
+
+    @staticmethod
+    def backward(ctx, dout):
+        _enter_backward()
+        (ids,) = ctx.saved_tensors
+        V, cols = ctx.table_shape
+        dout = dout.contiguous().float().reshape(-1, cols)
+        dtable = torch.zeros(V, cols, dtype=torch.float32, device=dout.device)
+        if ids.numel():
+            check(_lib.lib().nr_embed_gather_bwd(ptr(dout), cols, ptr(ids), ids.numel(), 1, cols, ptr(dtable), cols, _stream()),
+                  "nr_embed_gather_bwd")
+        return dtable, None, None
+
+
+def news_gather(table: torch.Tensor, ids: torch.Tensor, code: int = NR_F32) -> torch.Tensor:
+    """A differentiable embed_gather: out[i] = table[ids[i]] (fp32 table [V, N]; `code` = dtype of the result), and in backward
+    dtable[ids[i]] += dout[i] into a zeroed [V, N] fp32 (nr_embed_gather_bwd).  Row 0, the padding news, gets no gradient.  The
+    scatter adds with fp32 atomics: where an id repeats, the last bits of its row depend on the arrival order."""
+    _need_gpu(table, ids)
+    if table.dim() != 2 or table.dtype != torch.float32:
+        raise RuntimeError(f"news_gather: table must be a 2-D fp32 tensor, got {tuple(table.shape)} {table.dtype}")
+    ids = ids.to(torch.int32).contiguous()
+    if CHECK_INDICES:
+        check_ids(ids, table.shape[0], "news index")
+    return NewsGatherFunction.apply(table, ids, code)
 
 
 class GroupOrder:

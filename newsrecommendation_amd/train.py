@@ -603,6 +603,68 @@ def full_softmax_loss(model, news_vecs, hist_idx, mask, targets, temperature, ex
     return total / n.clamp(min=1).to(torch.float32), n
 
 
+def full_softmax_loss_joint(model, news_table, hist_idx, mask, targets, temperature, exclude_history=True, batch_size=8192, prior=None,
+                            news_time=None, window=None, seen=None):
+    """full_softmax_loss with a news-vector table that may require grad: the same loss, the same valid entries, the same
+    (loss, n), and a gradient for `news_table` ([V, news_dim] fp32 on the GPU: a table that is fine-tuned directly, or the
+    output of the news encoder, whose backward then receives the [V, news_dim] gradient) as well as for the user encoder.
+    The table is reached on two paths: the softmax itself (ops.full_softmax_nll_joint: one nr_score_expect_news call per chunk
+    of users and 128 targets, include/nrhip.h K18) and the clicked histories, whose vectors are gathered with ops.news_gather
+    (its backward is a scatter-add with fp32 atomics: the last bits of the table gradient depend on the arrival order).  A
+    table that does not require grad gives full_softmax_loss's gradients; the news pass is then not launched.
+    To train on more users than one call should hold, proceed as with full_softmax_loss."""
+    device = news_table.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    table = news_table.float().contiguous()                   # no detach: both are the identity for a contiguous fp32 table
+    U, V = hist.shape[0], table.shape[0]
+    tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
+    if tg.dim() != 2 or tg.shape[0] != U:
+        raise RuntimeError(f"full_softmax_loss_joint: targets must be [U = {U}, T], got {tuple(tg.shape)}")
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    tg = tg.masked_fill(_not_ranked(exclude, tg, V), 0)       # what target_logprob does not score is named as fill: it is in no sum
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    W = _lib.NR_TOPK_MAX_K
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.news_gather(table, hist[a:b], code), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) else tau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        for c in range(0, tg.shape[1], W):
+            nll, valid = ops.full_softmax_nll_joint(table, user, tg[a:b, c:c + W].contiguous(), tau_b, exclude=ex_b, **kw_b)
+            total = total + nll.sum()
+            n = n + valid.sum()
+    return total / n.clamp(min=1).to(torch.float32), n
+
+
+@torch.no_grad()
+def expected_exposure(model, news_vecs, hist_idx, mask, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
+                      window=None, seen=None):
+    """The expected exposure of every news under recommend_sample at `temperature`: exposure[v] = sum_u p(v | u), the expected
+    number of these users whose FIRST sampled place goes to news v -- the softmax over everything recommend_sample would consider
+    for that user under the same arguments (the user vectors, exclude_history, seen, prior, news_time and window are its).  It sums
+    to the number of users with anything eligible.  Two fused passes, no [U, V] matrix: the log-partition (ops.score_logz, K13),
+    then the mass-only mode of ops.score_expect_news (include/nrhip.h, K18).  A user whose temperature is not finite and > 0
+    (0 above all: a deterministic row) contributes nothing.  Returns exposure fp32 [V] on the device; exposure[0] = 0."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    tau = _device_temperature(temperature, user.shape[0], news_vecs.device)
+    base = ops.score_logz(news_vecs, user, tau, exclude=exclude, **kw)
+    _, mass = ops.score_expect_news(news_vecs, user, tau, base, exclude=exclude, rows=False, **kw)
+    return mass
+
+
 def _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window, news_group, group_cap, seen):
     """What recommend and recommend_diverse share: the fp32 table, the user vectors, the exclusions, the pool keywords and the
     cap keywords (group / group_cap; what is None is left out) of ops.score_topk."""
