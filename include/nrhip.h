@@ -416,6 +416,15 @@ int nr_score_eval(const float* news_vecs, int ld_news, const int32_t* cand_ids, 
  * ld_exclude, E <= 64): ids user u must not be given, e.g. the clicked history; entries that are 0 or outside [1, V) are
  * ignored, duplicates are allowed.  A news whose score is NaN is never returned and does not disturb the others.  With fewer
  * than k eligible news the tail of the row is id 0, score -inf.
+ * Special values, as the chain and the keys give them (K10 ranks by the same rules; tests/test_gpu_corpus_sweep.py holds each):
+ *   -0         the accumulator starts at +0, so a dot product is -0 only when every product of the chain rounds to -0.  A score
+ *              of -0 compares equal to +0: the two tie (news id ascending) and both come back as +0 in out_scores.
+ *   subnormal  products and partial sums below 2^-126 are kept as fp32 subnormals, never flushed to zero: the score is the fmaf
+ *              chain with gradual underflow, exact where the products and sums are representable.
+ *   +-inf      an infinite score is a score like any other: a chain that overflows, an infinite component or a prior of +inf
+ *              give +inf or -inf, ordered with everything else (ties by id).  A news whose score is -inf is eligible: it comes
+ *              back WITH ITS ID behind every finite score (and is ranked and counted by K10), unlike the fill, whose id is 0.
+ *              (-inf) + (+inf) is NaN and falls under the NaN rule.
  * One (u, v) score is one fmaf chain over the vector width in a fixed order: its bits are the same in any user tile, in any
  * corpus slice and for any `splits` (they need not equal nr_score_eval's, which sums in another order).
  * Two launches: the fused scoring + selection pass over a grid of user tiles x `splits` corpus slices, then a per-user merge
@@ -639,7 +648,8 @@ int nr_score_rank(const nr_rank_desc* d, nr_stream_t stream);
  *              places in the pool, 0-based;  the tail of a short row is id 0, score -inf, place -1
  * Consequences: with p_u = 0 the row is the pool walked in (score descending, place ascending) order under the cap -- for a
  * sorted pool without caps its first k places, bit for bit.  A row depends only on that user's pool row, its p_u and the
- * vectors that row names.
+ * vectors that row names.  Values of -0 and +0 tie (the lowest place wins); out_scores returns the pool's own bits, a -0
+ * included; a pool score of -inf or +inf is a live score like any other.
  * Unspecified: non-finite vector components, or a NaN or negative entry of penalty_u, give an unspecified row for that user
  * only, never an access outside the arrays (the library cannot check device arrays and does not synchronise).
  * Refused before any launch (nr_last_error; host arithmetic only): a null descriptor or required pointer; M or k out of range;
