@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -1093,6 +1093,59 @@ typedef struct {
 } nr_expect_news_desc;
 size_t nr_score_expect_news_workspace_bytes(const nr_expect_news_desc* d);
 int nr_score_expect_news(const nr_expect_news_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K19  the gradient coefficients of a sequential row: the backward of K14 with sequential = 1.  For a row i_0 .. i_{k-1}, a
+ * temperature tau and per-entry upstream gradients g_j, with (K14's quantities)
+ *   e_i = exp(s_i / tau),  B = the base: the mass of everything eligible that the row does not name (K13 with the row merged
+ *   into the lists),  W_j = B + sum_{i >= j} e_i,  nll_j = -(s_j / tau - log W_j),
+ * the gradient of L = sum_j g_j nll_j collapses onto K17 and K18 as they stand:
+ *   d L / d user   = (a E_rest - sum_i c_i news[i_i]) / tau          K17: weight = a, sub_ids = row, sub_w = c, scale_inv_tau
+ *   d L / d news_v = (a p_rest(v | u) - sum_{i: i_i = v} c_i) user / tau     K18: weight = a, named terms (row, c), scale_inv_tau
+ *   a   = sum_j g_j B / W_j,     c_i = g_i - e_i sum_{j <= i} g_j / W_j,
+ * E_rest / p_rest the softmax over exactly the news of B: K17 / K18 called with the lists of that K13 call and its base.  This
+ * call computes a and c; metrics.row_logprob_grad_reference states the contract on the host.  a = sum_i c_i in exact
+ * arithmetic (adding one vector to every news changes no probability).
+ * One launch, no workspace: K14's gather through the same MFMA tile (an entry has the stream's score bits and key), K14's
+ * suffix scan of (max, sum) pairs S_j = (M_j, sigma_j), W_j = exp(M_j / tau) sigma_j, then an inclusive PREFIX scan of the pairs
+ * (-M_j, g_j / sigma_j): M_j does not increase with j and the join is linear in the sum, so g may have any sign, and
+ *   c_i = g_i - exp((s_i - M_i) / tau) q_i,   a = exp((base_max - M_L) / tau + base_logsum) q_L   (L the last live entry)
+ * form no exponent above 0.  One wave per user in fp64, O(k log k) exponentials; each output is rounded to fp32 once.  The
+ * outputs of user u depend on that user's inputs only -- not on the other users of the call or the place in it.
+ *   row_ids, base_max, base_logsum, tau, tau_u, pools   as in K14, sequential = 1: the base formed WITHOUT the row's ids
+ *   g            optional [U, ld_g] fp32, ld_g >= k; NULL = 1 everywhere
+ *   out_weight   [U] fp32: a          out_sub_w   [U, k] fp32, contiguous: c
+ * Special entries: fill (an id that is 0 or outside [1, V)) and an entry whose key is 0 (NaN score, prior -inf, stamp outside
+ * the window) are no step of the row: c = 0, their g is not read.  A user whose temperature is <= 0, NaN or infinite, or
+ * whose base is NaN: a = 0 and every c = 0.  An empty base (max -inf, logsum -inf: the row takes everything eligible) gives
+ * a = 0 exactly; the last live entry's step then has logp 0 and adds nothing.  A row without a live entry: all zeros.
+ * Error bound (derived in DESIGN.md section 5) against the exact result on the fp32 inputs, e = 2^-24:
+ *   |a - a*| <= kappa e sum_j |g_j| B* / W*_j,   |c_i - c*_i| <= kappa e (|g_i| + e*_i sum_{j <= i} |g_j| / W*_j),
+ *   kappa = 2 (N + 1) G + 4 ln n + 7 K + 16     (G the score chain of K17, n the news of the base, K = 2 * seg / 128)
+ * Refused before any launch: what K14 refuses (sequential aside); g with ld_g < k; a null out_weight or out_sub_w.
+ * Layout: nr_logprob_desc without `sequential`, with g, ld_g and the two outputs in place of out_logp, out_total.            */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, k;
+  const int32_t* row_ids;
+  int ld_ids;
+  float tau;                /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;       /* optional [U] */
+  const float* base_max;    /* [U]: out_max of K13 */
+  const float* base_logsum; /* [U]: out_logsum of K13 */
+  const float* g;           /* optional [U, ld_g]: upstream gradient of nll per entry */
+  int ld_g;
+  float* out_weight;        /* [U]: a */
+  float* out_sub_w;         /* [U, k]: c */
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logprob_grad_desc;
+int nr_row_logprob_grad(const nr_logprob_grad_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

@@ -152,6 +152,13 @@ class ExpectNewsDesc(C.Structure):
                 ("ws_bytes", C.c_size_t), ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
 
 
+class LogprobGradDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("k", C.c_int), ("row_ids", C.c_void_p), ("ld_ids", C.c_int), ("tau", C.c_float), ("tau_u", C.c_void_p),
+                ("base_max", C.c_void_p), ("base_logsum", C.c_void_p), ("g", C.c_void_p), ("ld_g", C.c_int), ("out_weight", C.c_void_p),
+                ("out_sub_w", C.c_void_p), ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -242,6 +249,7 @@ SIGNATURES = {
     "nr_score_expect": [C.POINTER(ExpectDesc), _vp],
     "nr_score_expect_news_workspace_bytes": [C.POINTER(ExpectNewsDesc)],
     "nr_score_expect_news": [C.POINTER(ExpectNewsDesc), _vp],
+    "nr_row_logprob_grad": [C.POINTER(LogprobGradDesc), _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -290,7 +298,7 @@ def lib():
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
                 structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc, SampleDesc, LogzDesc,
-                           LogprobDesc, LogzGroupsDesc, LogprobCappedDesc, ExpectDesc, ExpectNewsDesc)
+                           LogprobDesc, LogzGroupsDesc, LogprobCappedDesc, ExpectDesc, ExpectNewsDesc, LogprobGradDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

@@ -491,6 +491,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 15) out[14] = sizeof(nr_logprob_capped_desc);
   if (n >= 16) out[15] = sizeof(nr_expect_desc);
   if (n >= 17) out[16] = sizeof(nr_expect_news_desc);
+  if (n >= 18) out[17] = sizeof(nr_logprob_grad_desc);
   return NR_OK;
 }
 

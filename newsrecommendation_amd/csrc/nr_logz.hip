@@ -25,6 +25,9 @@
 //                           suffix scan of (max, sum) pairs over the row joined with the user's base partition (sequential =
 //                           Plackett-Luce without replacement; only positive terms are added), or each entry against the base
 //                           alone (independent).
+//   logp_grad_kernel<POOL>  the sibling of logp_rows_kernel for the gradient of the sequential row (K19): the same gather and suffix
+//                           scan, then a prefix scan of (-M_j, g_j / sigma_j) pairs, which gives the coefficients (a, c) that turn
+//                           K17 and K18 into the row's gradient.  O(k log k) fp64 exp per user, every exponent <= 0.
 #include <math.h>
 
 #include "nr_logz_stream.h"
@@ -362,6 +365,139 @@ __global__ __launch_bounds__(TK_THREADS) void logp_rows_kernel(LogpArgs a) {
   }
 }
 
+// ---- K19 ----------------------------------------------------------------------------------------------------------------
+
+struct LogpGradArgs {
+  const float* news;
+  const float* user;
+  const int32_t* ids;
+  size_t ld_news, ld_user, ld_ids, ld_g;
+  int V, U, N, k;
+  PoolArgs pool;
+  float tau;
+  const float* tau_u;
+  const float* base_max;
+  const float* base_logsum;
+  const float* g;           // [U, ld_g] or null = 1
+  float* out_weight;        // [U]
+  float* out_sub_w;         // [U, k]
+};
+
+__device__ __forceinline__ LogpPair lp_up(LogpPair x, int o) { return {__shfl_up(x.m, o, 64), __shfl_up(x.s, o, 64)}; }
+
+// The gradient coefficients of the sequential row (include/nrhip.h, K19): the gather and the suffix scan of logp_rows_kernel,
+// statement for statement, so an entry has K14's key and step j K14's S_j = (M_j, sigma_j), W_j = exp(M_j / tau) sigma_j.  Then
+// g_j / W_j as the pair (-M_j, g_j / sigma_j) -- the same (max, sum) algebra, the sum signed: M_j does not increase with j, so
+// an inclusive PREFIX scan of these pairs ends, at a live entry i, on the maximum -M_i, and
+//   c_i = g_i - exp((x_i - M_i) / tau) q_i,   a = exp((base_max - M_L) / tau + base_logsum) q_L   (L = the last live entry)
+// form no exponent above 0.
+template <bool POOL>
+__global__ __launch_bounds__(TK_THREADS) void logp_grad_kernel(LogpGradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lg_smem[];
+  ScoreTile<1> t(lg_smem, a.N);
+  int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [16, 128] the ids the users name
+  uint32_t* sKey = reinterpret_cast<uint32_t*>(sIds + 16 * TK_ROWS);   // [16, 128] their keys, 0 = no score
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * 16;
+  const int users = a.U - u0 < 16 ? a.U - u0 : 16;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  for (int i = tid; i < 16 * TK_ROWS; i += TK_THREADS) {
+    const int ul = i / TK_ROWS, j = i - ul * TK_ROWS;
+    sIds[i] = ul < users && j < a.k ? a.ids[(size_t)(u0 + ul) * a.ld_ids + j] : 0;
+  }
+  __syncthreads();
+
+  ScoreNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  t.load_slab(rows, 0);
+  for (int c = 0; c < users; ++c) {
+    f32x4 acc[1];
+    rows.ids = sIds + c * TK_ROWS;
+    t.chunk(rows, acc);
+    if (c + 1 < users) {
+      rows.ids = sIds + (c + 1) * TK_ROWS;
+      t.load_slab(rows, 0);
+    }
+    t.put_scores(acc);
+    if (wave == 0) {
+      const size_t u = (size_t)(u0 + c);
+      int32_t lo = 0, hi = 0;
+      if constexpr (POOL) {
+        lo = a.pool.lo_of(u);
+        hi = a.pool.hi_of(u);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int r = lane + 64 * h;
+        const int32_t id = sIds[c * TK_ROWS + r];
+        uint32_t key = 0u;
+        if (id >= 1 && id < a.V) {
+          const float dot = t.scores()[c * TK_LDS_TILE + r];
+          if constexpr (POOL) key = pool_key(dot, a.pool.prior_of(id), a.pool.stamp_of(id), lo, hi);
+          else key = score_key(dot);
+        }
+        sKey[c * TK_ROWS + r] = key;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+
+  // one wave per user, in fp64; lane l holds entries 2 l and 2 l + 1 of the row
+  const double NINF = -(double)LZ_INF;
+  const LogpPair none = {NINF, 0.0};
+  for (int c = wave; c < users; c += TK_WAVES) {
+    const size_t u = (size_t)(u0 + c);
+    const float tau_f = a.tau_u != nullptr ? a.tau_u[u] : a.tau;
+    const float bm_f = a.base_max[u], bl_f = a.base_logsum[u];
+    const bool dead = !(tau_f > 0.f && tau_f < LZ_INF) || bm_f != bm_f || bl_f != bl_f;   // a = 0, every c = 0
+    const double tau = (double)tau_f, bm = (double)bm_f, bl = (double)bl_f;
+    const int j0 = 2 * lane, j1 = j0 + 1;
+    const uint32_t key0 = sKey[c * TK_ROWS + j0], key1 = sKey[c * TK_ROWS + j1];
+    const bool live0 = key0 != 0u, live1 = key1 != 0u;        // a step of the row: a real id (j < k) with a score inside the pool
+    const double x0 = (double)key_score(key0), x1 = (double)key_score(key1);
+    double g0 = live0 ? 1.0 : 0.0, g1 = live1 ? 1.0 : 0.0;    // the g of anything else is not read
+    if (a.g != nullptr) {
+      if (live0) g0 = (double)a.g[u * a.ld_g + j0];
+      if (live1) g1 = (double)a.g[u * a.ld_g + j1];
+    }
+    // K14's suffix scan: S_j = the base and the live entries j .. 127
+    const LogpPair P0 = live0 ? LogpPair{x0, 1.0} : none, P1 = live1 ? LogpPair{x1, 1.0} : none;
+    LogpPair R = lp_join(P0, P1, tau);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const LogpPair other = lp_down(R, o);
+      if (lane + o < 64) R = lp_join(R, other, tau);
+    }
+    LogpPair after = lp_down(R, 1);                           // entries 2 l + 2 .. 127
+    if (lane == 63) after = none;
+    const LogpPair base = {bm, exp(bl)};                      // everything eligible that the row does not name
+    const LogpPair S1 = lp_join(P1, lp_join(after, base, tau), tau);
+    const LogpPair S0 = lp_join(P0, S1, tau);
+    // inclusive prefix scan of (-M_j, g_j / sigma_j) over the live steps: Q_i = sum_{j <= i} g_j / W_j (sigma_j >= 1 at a live step)
+    const LogpPair T0 = live0 ? LogpPair{-S0.m, g0 / S0.s} : none, T1 = live1 ? LogpPair{-S1.m, g1 / S1.s} : none;
+    LogpPair Q = lp_join(T0, T1, tau);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const LogpPair other = lp_up(Q, o);
+      if (lane >= o) Q = lp_join(other, Q, tau);
+    }
+    LogpPair before = lp_up(Q, 1);                            // entries 0 .. 2 l - 1
+    if (lane == 0) before = none;
+    const LogpPair Q0 = lp_join(before, T0, tau), Q1 = lp_join(Q0, T1, tau);
+    const LogpPair all = {__shfl(Q.m, 63, 64), __shfl(Q.s, 63, 64)};
+    // at a live entry Q_i.m = -M_i, so the exponent is (x_i - M_i) / tau <= 0
+    const double c0 = live0 && !dead ? g0 - exp((x0 + Q0.m) / tau) * Q0.s : 0.0;
+    const double c1 = live1 && !dead ? g1 - exp((x1 + Q1.m) / tau) * Q1.s : 0.0;
+    if (j0 < a.k) a.out_sub_w[u * a.k + j0] = (float)c0;
+    if (j1 < a.k) a.out_sub_w[u * a.k + j1] = (float)c1;
+    if (lane == 0) {
+      // an empty base (max -inf) and a row without a live step have a = 0 exactly; base_max <= M_L, so the exponent's first term is <= 0
+      const bool zero = dead || bm == NINF || all.m == NINF;
+      a.out_weight[u] = zero ? 0.f : (float)(exp((bm + all.m) / tau + bl) * all.s);
+    }
+  }
+}
+
 // argument checks shared by the size query and the call; 0 = fine
 int logz_check(const nr_logz_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_logz: null descriptor");
@@ -454,6 +590,37 @@ int nr_row_logprob(const nr_logprob_desc* d, nr_stream_t stream) {
   const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
   NR_CHECK_RC(with_bool(a.pool.any(), [&](auto p) {
     return launch_lds(logp_rows_kernel<decltype(p)::value>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  }));
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_row_logprob_grad(const nr_logprob_grad_desc* d, nr_stream_t stream) {
+  NR_CHECK_ARG(d != nullptr, "row_logprob_grad: null descriptor");
+  NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "row_logprob_grad: k = %d entries per row, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
+  NR_CHECK_RC(check_vectors("row_logprob_grad", d->V, d->U, d->N));
+  NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LZ_INF), "row_logprob_grad: tau = %g, a scalar temperature must be finite and > 0",
+               (double)d->tau);
+  NR_CHECK_RC(check_pools("row_logprob_grad", d->stamp, d->window, d->ld_window));
+  NR_CHECK_ARG(d->news_vecs && d->user && d->row_ids && d->base_max && d->base_logsum && d->out_weight && d->out_sub_w,
+               "row_logprob_grad: null pointer (news_vecs, user, row_ids, base_max, base_logsum, out_weight, out_sub_w)");
+  NR_CHECK_RC(check_rows("row_logprob_grad", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
+  NR_CHECK_ARG(d->ld_ids >= d->k, "row_logprob_grad: id row stride %d < k = %d", d->ld_ids, d->k);
+  NR_CHECK_ARG(d->g == nullptr || d->ld_g >= d->k, "row_logprob_grad: g row stride %d < k = %d", d->ld_g, d->k);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  LogpGradArgs a;
+  a.news = d->news_vecs; a.user = d->user; a.ids = d->row_ids;
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_ids = (size_t)d->ld_ids; a.ld_g = (size_t)d->ld_g;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
+  a.tau = d->tau; a.tau_u = d->tau_u;
+  a.base_max = d->base_max; a.base_logsum = d->base_logsum;
+  a.g = d->g; a.out_weight = d->out_weight; a.out_sub_w = d->out_sub_w;
+  NrProfScope ps(s, "logp_grad[U=%d,N=%d,k=%d]", d->U, d->N, d->k);
+  const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
+  NR_CHECK_RC(with_bool(a.pool.any(), [&](auto p) {
+    return launch_lds(logp_grad_kernel<decltype(p)::value>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
   }));
   NR_CHECK_LAUNCH();
   return NR_OK;

@@ -488,6 +488,55 @@ def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, 
     return out, out.sum(axis=1)
 
 
+def row_logprob_grad_reference(a, b=None, *, row_ids, temperature, base, g=None, prior=None, stamp=None, window=None):
+    """Host statement of the gradient coefficients of a sequential row (include/nrhip.h, nr_row_logprob_grad); tests check the
+    device against it, no product path calls it.
+
+    The arguments are row_logprob_reference's (sequential rows: the base formed WITHOUT the row's ids); g [U, k] is the upstream
+    gradient of nll_j = -logp_j per entry (None = 1).  With s_i the score (+ prior) of entry i, e_i = exp(s_i / tau), B the
+    base's mass and W_j = B + sum_{i >= j} e_i over the live entries, in float64 around the running maxima:
+      weight[u]   = a   = sum_j g_j B / W_j
+      sub_w[u, i] = c_i = g_i - e_i sum_{j <= i} g_j / W_j
+    so that d (sum_j g_j nll_j) / d user = (a E_rest - sum_i c_i news[i_i]) / tau, E_rest the softmax mean over the news of B.
+    Fill entries (0 or outside [1, V)) and entries outside the pool or with a NaN score are no step: c = 0 and their g is not
+    looked at.  A temperature that is not finite and > 0, or a NaN base, gives that user zeros; an empty base (smax -inf) gives
+    a = 0.  Returns (weight float64 [U], sub_w float64 [U, k])."""
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    ids = np.asarray(row_ids, dtype=np.int64).reshape(U, -1)
+    k = ids.shape[1]
+    tau, tau_ok = _temperatures(temperature, U)
+    bl, bm = np.asarray(base[0], dtype=np.float64).reshape(U), np.asarray(base[1], dtype=np.float64).reshape(U)
+    gs = np.ones((U, k)) if g is None else np.asarray(g, dtype=np.float64).reshape(U, k)
+    weight, sub_w = np.zeros(U), np.zeros((U, k))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for u in range(U):
+            real = (ids[u] >= 1) & (ids[u] < V)
+            at = np.where(real, ids[u], 0)
+            s = scores[u, at]
+            live = real & pool[u, at] & ~np.isnan(s)
+            if not tau_ok[u] or np.isnan(bm[u]) or np.isnan(bl[u]) or not live.any():
+                continue
+            steps = np.flatnonzero(live)
+            x, gl = s[steps], gs[u, steps]
+            # in logs, around the row's largest score M: lw_j = log W_j - M / tau as a suffix log-add-exp, so that a tail far
+            # below the head keeps its digits and every ratio e_i / W_j, B / W_j is exp of a difference <= 0
+            M = max(bm[u], x.max())
+            lx = (x - M) / tau[u]
+            lb = (bm[u] - M) / tau[u] + bl[u] if bm[u] > -np.inf else -np.inf
+            lw = np.empty(len(steps))
+            run = lb
+            for n_i in range(len(steps) - 1, -1, -1):
+                run = np.logaddexp(lx[n_i], run)
+                lw[n_i] = run
+            for n_i, i in enumerate(steps):
+                sub_w[u, i] = gl[n_i] - np.sum(gl[:n_i + 1] * np.exp(lx[n_i] - lw[:n_i + 1]))
+            weight[u] = np.sum(gl * np.exp(lb - lw)) if lb > -np.inf else 0.0
+    return weight, sub_w
+
+
 def _bins(group, n_groups, V):
     """[V] int64 bins of the news under `group`: the group id, or n_groups for a negative one ("no group"); and n_groups
     (None = max id + 1, at least 1).  An id >= n_groups is an error."""

@@ -1659,6 +1659,120 @@ def full_softmax_nll_joint(news_vecs, user_vecs, targets, temperature, exclude=N
     return FullSoftmaxNLLJointFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
 
 
+@torch.no_grad()
+def row_logprob_grad(news_vecs, user_vecs, row_ids, temperature, base, g=None, prior=None, stamp=None, window=None):
+    """The gradient coefficients of sequential rows (nr_row_logprob_grad; include/nrhip.h, K19): the backward of
+    row_logprob(sequential=True).  `row_ids`, `temperature`, `base` and the pools are row_logprob's, the base formed WITHOUT the
+    row's ids; `g`: optional floating point [U, k], the upstream gradient of nll_j = -logp_j per entry (None = 1).
+    Returns (weight fp32 [U], sub_w fp32 [U, k]) = (a, c) with
+      d (sum_j g_j nll_j) / d user = (a E_rest - sum_i c_i news_vecs[row_i]) / temperature,
+    E_rest the expected news vector over what the base sums over: nr_score_expect with weight = a, the row and c as its named rows
+    and the lists of the base's score_logz call; the news side is nr_score_expect_news with the same weight and (row, c) as its
+    named terms.  Fill entries and entries outside the pool or with a NaN score get c = 0 and their g is not read; a user with
+    a bad temperature entry or a NaN base gets zeros; an empty base gives a = 0.  a = sum_i c_i up to rounding."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, row_ids, prior, stamp, window, tau_t, base[0], base[1], g)
+    V, N, U, dev = _vector_args("row_logprob_grad", news_vecs, user_vecs)
+    if row_ids.dim() != 2 or row_ids.shape[0] != U or row_ids.is_floating_point() or row_ids.device != dev:
+        raise RuntimeError(f"row_logprob_grad: row_ids must be an integer tensor [U = {U}, k] on {dev}, got {tuple(row_ids.shape)} {row_ids.dtype} "
+                           f"on {row_ids.device}")
+    k = row_ids.shape[1]
+    weight = torch.empty(U, dtype=torch.float32, device=dev)
+    sub_w = torch.empty(U, k, dtype=torch.float32, device=dev)
+    if U == 0:
+        return weight, sub_w
+    if g is not None:
+        if tuple(g.shape) != (U, k) or not g.is_floating_point() or g.device != dev:
+            raise RuntimeError(f"row_logprob_grad: g must be a floating point tensor of shape ({U}, {k}) on {dev}")
+        g = g.detach().to(torch.float32).contiguous()
+    bl, bm = _base_args("row_logprob_grad", base, U, dev)
+    ids = row_ids.detach().to(torch.int32).contiguous()
+    pr, st, win = _pool_args("row_logprob_grad", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("row_logprob_grad", temperature, U, dev)
+    d = _lib.LogprobGradDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                             ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=k, row_ids=ptr(ids), ld_ids=k, tau=tau,
+                             tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl), g=ptr(g), ld_g=k if g is not None else 0,
+                             out_weight=ptr(weight), out_sub_w=ptr(sub_w), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
+                             ld_window=2 if win is not None else 0)
+    check(_lib.lib().nr_row_logprob_grad(C.byref(d), _stream()), "nr_row_logprob_grad")
+    return weight, sub_w
+
+
+class PlackettLuceNLLFunction(Function):
+    """nll [U, k] of the places of sequential rows (Plackett-Luce without replacement over the corpus), differentiable with respect
+    to the user vectors (K19, then one K17 call) and the news-vector table (K19, then one K18 call)."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, news_vecs, rows, temperature, exclude, splits, prior, stamp, window):
+        user, news = user_vecs.detach(), news_vecs.detach()
+        V = news.shape[0]
+        taken = ExclusionLists(rows)
+        if exclude is None:
+            lists = taken
+        else:
+            lists = (exclude if isinstance(exclude, ExclusionLists) else ExclusionLists(exclude)).merged(taken)
+        base = score_logz(news, user, temperature, exclude=lists, splits=splits, prior=prior, stamp=stamp, window=window)
+        logp, _ = row_logprob(news, user, rows, temperature, base, True, prior=prior, stamp=stamp, window=window)
+        valid = (rows >= 1) & (rows < V) & ~torch.isnan(logp)
+        if isinstance(temperature, torch.Tensor):
+            valid &= ((temperature > 0) & torch.isfinite(temperature))[:, None]
+        nll = torch.where(valid, -logp, torch.zeros_like(logp))
+        ctx.save_for_backward(user, news, rows, valid, base[0], base[1])
+        ctx.rest = (temperature, lists, splits, prior, stamp, window)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return nll, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, news, rows, valid, bl, bm = ctx.saved_tensors
+        temperature, lists, splits, prior, stamp, window = ctx.rest
+        if g is None:
+            return (None,) * 9
+        gw = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=g.device))
+        grad_user = grad_news = None
+        with torch.no_grad():
+            a, c = row_logprob_grad(news, user, rows, temperature, (bl, bm), g=gw, prior=prior, stamp=stamp, window=window)
+            if ctx.needs_input_grad[0]:
+                grad_user, _ = _score_expect("plackett_luce_nll", news, user, temperature, (bl, bm), lists, splits, prior, stamp, window,
+                                             a, rows, c, True)
+                # a user none of whose places count (all fill or invalid, a bad temperature) has no gradient: exactly 0, not 0 * NaN
+                grad_user = torch.where(valid.any(dim=1)[:, None], grad_user, torch.zeros_like(grad_user))
+            if ctx.needs_input_grad[1]:
+                # K18 leaves out a user with nothing eligible, named terms included.  A row that takes everything eligible has such a
+                # base and still has named terms (a = 0, c != 0); nothing of its stream is eligible, so any finite base gives them
+                # back and adds nothing else.  `splits` is K13's / K17's cut of the news axis and does not apply to K18.
+                empty = torch.isneginf(bm)
+                zero = torch.zeros_like(bm)
+                grad_news, _ = _score_expect_news("plackett_luce_nll", news, user, temperature,
+                                                  (torch.where(empty, zero, bl), torch.where(empty, zero, bm)), lists, 0, prior, stamp, window,
+                                                  a, _named_by_news(rows, c, news.shape[0]), True, True)
+        return (grad_user, grad_news) + (None,) * 7
+
+
+def plackett_luce_nll(news_vecs, user_vecs, rows, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """The negative log-likelihood of ordered rows under the Plackett-Luce law score_sample draws from, place by place, with a
+    gradient for `user_vecs` AND the table `news_vecs` (either may require grad): the training-side counterpart of
+    train.sample_propensity.  rows: integer tensor [U, k <= 128], 0 (or anything outside [1, V)) = fill; place j is scored
+    against everything eligible that places 0 .. j-1 have not taken.
+    Forward: `rows` merged into `exclude` (ExclusionLists(rows), .merged), score_logz on those lists, row_logprob(sequential=True)
+    -- what sample_propensity launches, so nll[valid] = -logp of it, bit for bit.  Returns (nll fp32 [U, k], valid bool [U, k]):
+    valid is False at fill entries, at entries row_logprob gives NaN (outside the pool, a NaN score) and for users whose
+    temperature is not finite and > 0; nll is 0 there.  Repeats within a row and entries inside `exclude` are the caller's
+    statement and are not checked, as in row_logprob (train.listwise_loss turns them into fill).
+    Backward: ONE nr_row_logprob_grad call (include/nrhip.h, K19) with g zeroed where not valid gives the coefficients (a, c);
+    then grad_user = (a E_rest - sum_i c_i news[row_i]) / temperature is one nr_score_expect call (K17: weight a, named rows
+    (rows, c), the merged lists, the saved base) and grad_news one nr_score_expect_news call (K18: weight a, named terms (rows,
+    c)).  A pass whose input does not require grad is not launched; a user without a valid place gets an exactly zero row.
+    Temperature, prior and the other arguments get no gradient."""
+    if rows.dim() != 2 or rows.shape[0] != user_vecs.shape[0] or rows.is_floating_point():
+        raise RuntimeError(f"plackett_luce_nll: rows must be an integer tensor [U = {user_vecs.shape[0]}, k], got {tuple(rows.shape)} {rows.dtype}")
+    if rows.shape[1] < 1 or rows.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"plackett_luce_nll: k = {rows.shape[1]} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential row "
+                           "cannot be cut into chunks")
+    return PlackettLuceNLLFunction.apply(user_vecs, news_vecs, rows, temperature, exclude, splits, prior, stamp, window)
+
+
 class NewsGatherFunction(Function):
     """out[i] = table[ids[i]] with a gradient for the table: nr_gather_cast_fwd forward, nr_embed_gather_bwd backward."""
 

@@ -648,6 +648,72 @@ def full_softmax_loss_joint(model, news_table, hist_idx, mask, targets, temperat
     return total / n.clamp(min=1).to(torch.float32), n
 
 
+def listwise_loss(model, news_table, hist_idx, mask, rows, temperature, weight=None, exclude_history=True, batch_size=8192, prior=None,
+                  news_time=None, window=None, news_group=None, group_cap=None, seen=None):
+    """The listwise training loss on ordered rows -- served rows of recommend_sample, or any ranked list -- under the Plackett-Luce
+    law the sampler draws from: sample_propensity's quantity with a gradient.  rows [U, k <= 128] (0 = no entry); place j of a
+    row is scored against everything recommend_sample would still consider for that user after places 0 .. j-1 (the user vectors,
+    exclude_history, seen, prior, news_time and window are its), and
+      loss = sum_u sum_j weight * nll[u, j] / n,   nll[u, j] = -log P(entry j is drawn at step j | entries 0 .. j-1 are taken),
+    n the number of rows with at least one valid entry.  weight: None (1: listwise maximum likelihood, ListMLE), [U] (one per row:
+    a reward, or a reward times a clipped importance ratio for off-policy policy gradient; negative is allowed) or
+    [U, k] (per place: a position discount).  It is a constant: no gradient reaches it.
+    No [U, V] matrix: forward and backward are fused passes over the table (ops.plackett_luce_nll; include/nrhip.h, K13, K14,
+    K19, K17, K18).  Built like full_softmax_loss_joint: the user vectors are formed WITH gradient, batch_size users at a time,
+    from ops.news_gather of the histories, so a `news_table` that requires grad is reached on both paths; one that does not
+    gives the user encoder's gradients alone and the news pass is not launched.
+    An entry that is 0 or out of range, inside the user's exclusions, or a repeat of an earlier entry of its row is turned into
+    fill; an entry outside the pool or NaN-scored, and every entry of a user whose temperature is not finite and > 0, is not valid
+    either.  None of these is a step of the row or part of the loss.
+    Returns (loss, n): loss a 0-dim fp32 tensor (0 when n == 0), n a 0-dim int64 device tensor.  Rows wider than 128 are
+    refused: a sequential row cannot be cut into chunks.  Rows drawn under group caps follow another law
+    (sample_propensity_capped); passing news_group or group_cap raises ValueError."""
+    if news_group is not None or group_cap is not None:
+        raise ValueError("listwise_loss: rows drawn under group caps (news_group / group_cap) follow another law: "
+                         "the remaining mass under caps needs per-group partitions")
+    device = news_table.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    table = news_table.float().contiguous()                   # no detach: both are the identity for a contiguous fp32 table
+    U, V = hist.shape[0], table.shape[0]
+    rw = torch.as_tensor(rows).to(device=device, dtype=torch.int32)
+    if rw.dim() != 2 or rw.shape[0] != U:
+        raise RuntimeError(f"listwise_loss: rows must be [U = {U}, k], got {tuple(rw.shape)}")
+    k = rw.shape[1]
+    if k < 1 or k > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"listwise_loss: k = {k} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential row cannot be cut "
+                           "into chunks")
+    w = None
+    if weight is not None:
+        w = torch.as_tensor(weight).detach().to(device=device, dtype=torch.float32)
+        if tuple(w.shape) not in ((U,), (U, k)):
+            raise RuntimeError(f"listwise_loss: weight must be [U = {U}] or [U, k = {k}], got {tuple(w.shape)}")
+        w = w[:, None].expand(U, k) if w.dim() == 1 else w
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    rw = rw.masked_fill(_not_ranked(exclude, rw, V), 0)       # what is no step of the row is named as fill: it is in no sum
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.news_gather(table, hist[a:b], code), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) else tau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        nll, valid = ops.plackett_luce_nll(table, user, rw[a:b].contiguous(), tau_b, exclude=ex_b, **kw_b)
+        total = total + (nll.sum() if w is None else (nll * w[a:b]).sum())
+        n = n + valid.any(dim=1).sum()
+    return total / n.clamp(min=1).to(torch.float32), n
+
+
 @torch.no_grad()
 def expected_exposure(model, news_vecs, hist_idx, mask, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
                       window=None, seen=None):
