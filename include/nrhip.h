@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc, with n >= 20 out[18..19] = nr_expect_groups_desc, nr_logprob_capped_grad_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -1146,6 +1146,144 @@ typedef struct {
   int ld_window;
 } nr_logprob_grad_desc;
 int nr_row_logprob_grad(const nr_logprob_grad_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K20  the gradient of K15: the expected news vector PER BIN, weighted per (user, bin).  K17 with per-bin bases and a weight
+ * omega[u, b] in front of every bin's softmax, streamed over the group-major order K15 streams over:
+ *   out[u] = ( sum_b omega[u, b] E_{u,b}  -  sum_t sub_w[u, t] news[sub_ids[u, t]] ) (* 1 / tau_u)
+ *   E_{u,b} = sum_{v in bin b, eligible, not listed} p_b(v | u) news_v,   p_b(v | u) = exp((s_uv - gmax_ub) / tau_u - logsum_ub)
+ * the softmax INSIDE bin b on K15's base of that bin.  With omega and sub_w from K21 this is the whole user-side gradient of
+ * the capped row's loss.  metrics.expect_groups_reference states the contract on the host.
+ *   order, n_pos, seg_start, nseg, bin_seg, n_groups, lists IN POSITION SPACE, pools by news id   as in K15
+ *   base_max, base_logsum   [U, ld_base] fp32, ld_base >= n_groups + 1: out_max / out_logsum of a K15 call with the SAME arguments
+ *   bin_w       [U, ld_base] fp32: omega
+ *   sub_ids, sub_w, ld_sub, T, scale_inv_tau   K17's fields and meaning
+ *   out         [U, ld_out] fp32;   out_mass optional [U] fp32: sum_v omega p over the EXACT products, summed in fp64 -- up to
+ *               rounding sum of omega_b over the non-empty bins
+ * Stream: K17's kernel (the scoring tile, the P tile in LDS, out[TU, N] += P[TU, 128] . rows[128, N] on
+ * v_mfma_f32_16x16x4_f32, accumulators in registers for the whole slice, nothing rescaled) with rows read through order[] for
+ * both contractions and prior / stamp gathered by id.  A position whose id is 0 is padding: weight 0.  A segment never
+ * straddles two bins; when the bin changes the wave reloads (gmax, -logsum, omega) of its users.  The weight of a pair is
+ * fl(omega * p), p = expf(fmaf(s - gmax, 1 / tau, -logsum)) exactly as in K17: ONE fp32 multiply per pair.  A (user, bin) with
+ * omega == 0 contributes exactly nothing whatever its base holds; so does an empty bin (gmax = -inf).
+ * Slices are K15's (slice y of s: the segments that start in [y n_pos / s, (y + 1) n_pos / s)); the user tile is K17's.  A
+ * slice without a segment writes nothing and the finalize skips it.  Finalize: K17's -- the slices ascending in fp64, the
+ * gather-subtract in fp64 with t ascending, times 1 / tau, one rounding.
+ * Bits.  For a fixed explicit `splits`, row u depends on that user's inputs and on the order only -- not on the other users,
+ * the place in the tile, or U.  splits = 0 lets the library choose by U.
+ * Edge cases, K17's read per bin.  A user whose tau_u entry is <= 0, NaN or infinite and who has a non-empty bin, or who has
+ * a non-empty bin with omega != 0 whose gmax is NaN or +inf, whose logsum is NaN, or whose omega is not finite: a row of NaN
+ * and mass NaN, every other user untouched.  Non-finite components of a news row count as 0.
+ * Error bound (derived in DESIGN.md section 5) against the exact result on the fp32 inputs, e = 2^-24:
+ *   |out_c - out*_c| <= kappa e (sum_b |omega_b| sum_v p*_bv |news_vc| + sum_t |sub_w_t| |news[sub_ids_t, c]|) (* 1 / tau)
+ *   kappa = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 27
+ * K17's kappa with one more rounding (fl(omega * p)), n the eligible news of the largest bin, C and G over the bins with
+ * omega != 0 (C = max |s_v| / tau there), K = 2 S (S = the chunks of K15's longest segment) and L = 128 * (chunks of
+ * this call's longest slice).
+ *   |mass - sum_{b non-empty} omega_b| <= (6 C + 5 ln n + 7 K + 23) e sum_{b non-empty} |omega_b|      (K17's mass bound, per bin)
+ *   ws          nr_score_expect_groups_workspace_bytes(d): U * slices * (N * 4 + 8) bytes rounded to 8 (0 = bad descriptor)
+ * Refused before any launch: everything K15 refuses (null descriptor; V, U, N; the list form; a bad scalar tau; n_groups,
+ * n_pos, nseg, splits out of range; stamp without window or the reverse; a null news_vecs, user, order, seg_start, bin_seg;
+ * rows off 16 bytes); a null base_max, base_logsum, bin_w or out; ld_base < n_groups + 1; sub_ids without sub_w or the
+ * reverse; T outside [1, NR_TOPK_MAX_K] or ld_sub < T when sub_ids is given; ld_out < N or an out off 16 bytes; an undersized
+ * workspace.  Layout: nr_logz_groups_desc's fields in its order up to n_groups, then this call's, then the shared tail.   */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1] */
+  const int32_t* excl_ids;     /* optional [n_excl]: POSITIONS, per user strictly ascending */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const int32_t* order;        /* [n_pos] */
+  int n_pos;
+  const int32_t* seg_start;    /* [nseg + 1] */
+  int nseg;
+  const int32_t* bin_seg;      /* [n_groups + 2] */
+  int n_groups;
+  const float* base_max;       /* [U, ld_base]: out_max of K15 */
+  const float* base_logsum;    /* [U, ld_base]: out_logsum of K15 */
+  const float* bin_w;          /* [U, ld_base]: omega */
+  int ld_base;
+  const int32_t* sub_ids;      /* optional [U, ld_sub]; with sub_w */
+  const float* sub_w;          /* optional [U, ld_sub]; with sub_ids */
+  int ld_sub, T;
+  int scale_inv_tau;
+  float* out;                  /* [U, ld_out] */
+  int ld_out;
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V], indexed by news id */
+  const int32_t* stamp;  /* optional [V], indexed by news id; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_groups_desc;
+size_t nr_score_expect_groups_workspace_bytes(const nr_expect_groups_desc* d);
+int nr_score_expect_groups(const nr_expect_groups_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K21  the gradient coefficients of a capped row: the backward of K16.  In K16's notation (w_v = exp(s_v / tau), B_b the
+ * mass of bin b in the K15 bases formed with the row's ids merged into the lists, t_b the step at which the row takes its
+ * c-th live entry of bin b, D_j = sum_{b: t_b >= j} (B_b + sum_{i >= j, bin(i) = b} w_i), nll_j = -(s_j / tau - log D_j)
+ * over the live steps j) and upstream gradients g_j, let Q_j = sum_{j' <= j, j' a live step} g_j' / D_j' and Q_b = Q at
+ * min(t_b, last live step).  Then
+ *   d (sum_j g_j nll_j) / d user_u = ( sum_b omega_b E_b - sum_i c_i news[row_i] ) / tau          (K20)
+ *   omega_b = B_b Q_b                       per (user, bin), E_b the softmax mean inside the bin on K15's base
+ *   c_i = g_i - w_i Q_i                     for a live step i (K19's form)
+ *   c_i = -w_i Q_{bin(i)}                   for a blocked entry (its group already full: K16's -inf entry); it is no step and
+ *                                           its g is not read
+ * sum_b omega_b = sum_i c_i in exact arithmetic.  metrics.capped_row_logprob_grad_reference states the contract on the host.
+ * One launch, one wave per user, fp64, no workspace: K16's gather (the stream's score bits), K16's determination of t_b and
+ * its walk from the last place to the first, each D_j kept as the pair (M_j, sigma_j), D_j = exp(M_j / tau) sigma_j; the
+ * supports of the steps are nested, so M_j does not increase with j and K19's inclusive prefix scan of (-M_j, g_j / sigma_j)
+ * applies:  omega_b = exp((gmax_b - M_{t_b}) / tau + logsum_b) q_{t_b},  c_i = g_i - exp((s_i - M_i) / tau) q_i  form no
+ * exponent above 0 -- B_b and w_i are terms of the D they are divided by.  g may have any sign.  Each output is rounded to
+ * fp32 once; a user's outputs depend on that user's inputs only.
+ *   row_ids, group, group_cap, n_groups, base_max, base_logsum, ld_base, tau, tau_u, pools   as in K16
+ *   g            optional [U, ld_g] fp32, ld_g >= k; NULL = 1 everywhere
+ *   out_bin_w    [U, ld_base] fp32: omega; bins 0 .. n_groups all written, 0 for empty bins
+ *   out_sub_w    [U, k] fp32, contiguous: c
+ * Special entries: fill and key-0 entries are no step: c = 0, their g is not read.  A user whose temperature is <= 0, NaN or
+ * infinite, or with a NaN in a base (gmax NaN, or logsum NaN in a non-empty bin; every bin is open at step 0, so the row
+ * needs them all): all zeros.  A row without a live step: all zeros.
+ * Error bound (derived in DESIGN.md section 5) against the exact result on the fp32 inputs, e = 2^-24:
+ *   |omega_b - omega*_b| <= kappa e B*_b sum_{j <= t_b} |g_j| / D*_j
+ *   |c_i - c*_i| <= kappa e (|g_i| + w*_i sum_{j <= i} |g_j| / D*_j)     (blocked: without |g_i|, the sum up to t_bin(i))
+ *   kappa = 2 (N + 1) G + 4 ln n + 7 K + 17
+ * K19's kappa plus 1 for the fp64 joins over the open bins and the later entries (at most 513 + 128 of them, each 2^-53);
+ * n the eligible news of the largest bin, K = 2 S of K15's segments.
+ * Refused before any launch: what K16 refuses (the outputs aside); g with ld_g < k; a null out_bin_w or out_sub_w.
+ * Layout: nr_logprob_capped_desc without out_logp / out_total, with g, ld_g and the two outputs in their place.            */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N, k;
+  const int32_t* row_ids;
+  int ld_ids;
+  const int32_t* group;     /* [V] */
+  int group_cap, n_groups;
+  float tau;                /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;       /* optional [U] */
+  const float* base_max;    /* [U, ld_base]: out_max of K15 */
+  const float* base_logsum; /* [U, ld_base]: out_logsum of K15 */
+  int ld_base;
+  const float* g;           /* optional [U, ld_g]: upstream gradient of nll per entry */
+  int ld_g;
+  float* out_bin_w;         /* [U, ld_base]: omega */
+  float* out_sub_w;         /* [U, k]: c */
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_logprob_capped_grad_desc;
+int nr_row_logprob_capped_grad(const nr_logprob_capped_grad_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

@@ -159,6 +159,25 @@ class LogprobGradDesc(C.Structure):
                 ("out_sub_w", C.c_void_p), ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
 
 
+class ExpectGroupsDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("splits", C.c_int), ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int),
+                ("tau", C.c_float), ("tau_u", C.c_void_p), ("order", C.c_void_p), ("n_pos", C.c_int), ("seg_start", C.c_void_p),
+                ("nseg", C.c_int), ("bin_seg", C.c_void_p), ("n_groups", C.c_int),
+                ("base_max", C.c_void_p), ("base_logsum", C.c_void_p), ("bin_w", C.c_void_p), ("ld_base", C.c_int),
+                ("sub_ids", C.c_void_p), ("sub_w", C.c_void_p), ("ld_sub", C.c_int), ("T", C.c_int), ("scale_inv_tau", C.c_int),
+                ("out", C.c_void_p), ("ld_out", C.c_int), ("out_mass", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
+
+
+class LogprobCappedGradDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("k", C.c_int), ("row_ids", C.c_void_p), ("ld_ids", C.c_int), ("group", C.c_void_p), ("group_cap", C.c_int),
+                ("n_groups", C.c_int), ("tau", C.c_float), ("tau_u", C.c_void_p), ("base_max", C.c_void_p), ("base_logsum", C.c_void_p),
+                ("ld_base", C.c_int), ("g", C.c_void_p), ("ld_g", C.c_int), ("out_bin_w", C.c_void_p), ("out_sub_w", C.c_void_p),
+                ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -178,7 +197,7 @@ RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": 
             "nr_score_topk_workspace_bytes": C.c_size_t, "nr_score_rank_workspace_bytes": C.c_size_t,
             "nr_score_sample_workspace_bytes": C.c_size_t, "nr_score_logz_workspace_bytes": C.c_size_t,
             "nr_score_logz_groups_workspace_bytes": C.c_size_t, "nr_score_expect_workspace_bytes": C.c_size_t,
-            "nr_score_expect_news_workspace_bytes": C.c_size_t}
+            "nr_score_expect_news_workspace_bytes": C.c_size_t, "nr_score_expect_groups_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
     "nr_last_error": [C.c_char_p, C.c_size_t],
@@ -250,6 +269,9 @@ SIGNATURES = {
     "nr_score_expect_news_workspace_bytes": [C.POINTER(ExpectNewsDesc)],
     "nr_score_expect_news": [C.POINTER(ExpectNewsDesc), _vp],
     "nr_row_logprob_grad": [C.POINTER(LogprobGradDesc), _vp],
+    "nr_score_expect_groups_workspace_bytes": [C.POINTER(ExpectGroupsDesc)],
+    "nr_score_expect_groups": [C.POINTER(ExpectGroupsDesc), _vp],
+    "nr_row_logprob_capped_grad": [C.POINTER(LogprobCappedGradDesc), _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -298,7 +320,8 @@ def lib():
                     fn.argtypes = argtypes
                     fn.restype = RESTYPES.get(name, C.c_int)
                 structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc, SampleDesc, LogzDesc,
-                           LogprobDesc, LogzGroupsDesc, LogprobCappedDesc, ExpectDesc, ExpectNewsDesc, LogprobGradDesc)
+                           LogprobDesc, LogzGroupsDesc, LogprobCappedDesc, ExpectDesc, ExpectNewsDesc, LogprobGradDesc, ExpectGroupsDesc,
+                           LogprobCappedGradDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

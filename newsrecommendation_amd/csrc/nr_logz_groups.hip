@@ -1,5 +1,5 @@
 // Propensities under group caps: the log-partition of a user's score row PER GROUP (K15), and on these the log-probabilities of
-// the entries of rows drawn by the capped sampler (K16).  The fourth consumer of the tile of nr_score_tile.h, built like
+// the entries of rows drawn by the capped sampler (K16) and the coefficients of their gradient (K21).  The fourth consumer of the tile of nr_score_tile.h, built like
 // nr_logz.hip: scores and eligibility come from score_key / pool_key, so one (u, v) pair has here the bits and the verdict it
 // has in nr_score_topk, nr_score_sample and nr_score_logz.
 //
@@ -16,6 +16,9 @@
 //   logp_capped_kernel<POOL>   the named-row gather of logp_rows_kernel, then per user one wave in fp64 (K16): the step t_b at
 //                           which the row fills each of its bins, the never-closing bins joined in a fixed order, and the walk
 //                           from the last place to the first.  Only positive terms are added.
+//   logp_capped_grad_kernel<POOL>   the sibling of logp_capped_kernel for the gradient of the capped row (K21): the same gather, t_b
+//                           and walk, each D_j kept as (M_j, sigma_j) by the lane that holds place j; then the inclusive prefix scan
+//                           of (-M_j, g_j / sigma_j) of K19, omega per bin and c per entry.
 #include <math.h>
 
 #include "nr_score_tile.h"
@@ -503,6 +506,246 @@ __global__ __launch_bounds__(TK_THREADS) void logp_capped_kernel(LogpcArgs a) {
   }
 }
 
+// ---- K21 ----------------------------------------------------------------------------------------------------------------
+
+struct LogpcGradArgs {
+  const float* news;
+  const float* user;
+  const int32_t* ids;
+  const int32_t* group;
+  size_t ld_news, ld_user, ld_ids, ld_base, ld_g;
+  int V, U, N, k, cap, G;
+  PoolArgs pool;
+  float tau;
+  const float* tau_u;
+  const float* base_max;
+  const float* base_logsum;
+  const float* g;           // [U, ld_g] or null = 1
+  float* out_bin_w;         // [U, ld_base]
+  float* out_sub_w;         // [U, k]
+};
+
+__device__ __forceinline__ LgPair lg_up(LgPair x, int o) { return {__shfl_up(x.m, o, 64), __shfl_up(x.s, o, 64)}; }
+
+// The gradient coefficients of the capped row (include/nrhip.h, K21): the gather, the t_b and the walk of logp_capped_kernel,
+// statement for statement, so an entry has K16's key and a live step j K16's D_j = exp(M_j / tau) sigma_j; the lane that holds
+// entry j keeps (M_j, sigma_j).  Then K19's inclusive prefix scan of (-M_j, g_j / sigma_j) over the live steps -- the supports of
+// the steps are nested, so M_j does not increase with j -- and
+//   omega_b = exp((gmax_b - M_{t_b}) / tau + logsum_b) q_{t_b},   c_i = g_i - exp((x_i - M_i) / tau) q_i   (blocked: the q of t_bin(i))
+// form no exponent above 0.
+template <bool POOL>
+__global__ __launch_bounds__(TK_THREADS) void logp_capped_grad_kernel(LogpcGradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lc_smem[];
+  ScoreTile<1> t(lc_smem, a.N);
+  int32_t* sIds = reinterpret_cast<int32_t*>(t.end());        // [16, 128] the ids the users name
+  uint32_t* sKey = reinterpret_cast<uint32_t*>(sIds + 16 * TK_ROWS);   // [16, 128] their keys, 0 = no score
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
+  const int u0 = blockIdx.x * 16;
+  const int users = a.U - u0 < 16 ? a.U - u0 : 16;
+
+  t.load_users(a.user, a.ld_user, u0, a.U);
+  for (int i = tid; i < 16 * TK_ROWS; i += TK_THREADS) {
+    const int ul = i / TK_ROWS, j = i - ul * TK_ROWS;
+    sIds[i] = ul < users && j < a.k ? a.ids[(size_t)(u0 + ul) * a.ld_ids + j] : 0;
+  }
+  __syncthreads();
+
+  ScoreNamedRows rows = {a.news, a.ld_news, sIds, a.V};
+  t.load_slab(rows, 0);
+  for (int c = 0; c < users; ++c) {
+    f32x4 acc[1];
+    rows.ids = sIds + c * TK_ROWS;
+    t.chunk(rows, acc);
+    if (c + 1 < users) {
+      rows.ids = sIds + (c + 1) * TK_ROWS;
+      t.load_slab(rows, 0);
+    }
+    t.put_scores(acc);
+    if (wave == 0) {
+      const size_t u = (size_t)(u0 + c);
+      int32_t lo = 0, hi = 0;
+      if constexpr (POOL) {
+        lo = a.pool.lo_of(u);
+        hi = a.pool.hi_of(u);
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int r = lane + 64 * h;
+        const int32_t id = sIds[c * TK_ROWS + r];
+        uint32_t key = 0u;
+        if (id >= 1 && id < a.V) {
+          const float dot = t.scores()[c * TK_LDS_TILE + r];
+          if constexpr (POOL) key = pool_key(dot, a.pool.prior_of(id), a.pool.stamp_of(id), lo, hi);
+          else key = score_key(dot);
+        }
+        sKey[c * TK_ROWS + r] = key;
+      }
+    }
+    __syncthreads();                                          // the score tile is the next chunk's staging buffer
+  }
+
+  // one wave per user, in fp64.  Every wave runs both rounds and every barrier; a wave without a user only skips the work.
+  char* scratch = reinterpret_cast<char*>(t.sB) + (size_t)wave * LC_WAVE_BYTES;
+  double* stM = reinterpret_cast<double*>(scratch);           // [128] the walk's stash; afterwards the prefix q of every place
+  double* stS = stM + TK_ROWS;
+  int32_t* sBin = reinterpret_cast<int32_t*>(stS + TK_ROWS);  // [128] bin of a live entry, -1 otherwise
+  int32_t* sTc = sBin + TK_ROWS;                              // [128] the place at which the entry's bin closes, -1 = never
+  unsigned char* sClose = reinterpret_cast<unsigned char*>(sTc + TK_ROWS);   // [G + 1] that place per bin, 0xff = never
+  const double NINF = -(double)LG_INF;
+  const LgPair none = {NINF, 0.0};
+  for (int c0 = 0; c0 < 16; c0 += TK_WAVES) {
+    const int c = c0 + wave;
+    const bool active = c < users;
+    const size_t u = (size_t)(u0 + (active ? c : 0));
+    const int j0 = 2 * lane, j1 = j0 + 1;
+    int b0 = -1, b1 = -1;
+    if (active) {
+      const int32_t id0 = sIds[c * TK_ROWS + j0], id1 = sIds[c * TK_ROWS + j1];
+      if (sKey[c * TK_ROWS + j0] != 0u) {
+        const int32_t g = a.group[id0];
+        b0 = g >= 0 && g < a.G ? g : a.G;
+      }
+      if (sKey[c * TK_ROWS + j1] != 0u) {
+        const int32_t g = a.group[id1];
+        b1 = g >= 0 && g < a.G ? g : a.G;
+      }
+      sBin[j0] = b0;
+      sBin[j1] = b1;
+      stM[j0] = stM[j1] = NINF;
+      stS[j0] = stS[j1] = 0.0;
+      for (int b = lane; b <= a.G; b += 64) sClose[b] = 0xff;
+    }
+    __syncthreads();
+    if (active) {
+      // the c-th live entry of a group closes it: the entry with cap - 1 live entries of its bin before it
+      int n0 = 0, n1 = 0;
+      for (int i = 0; i < j1; ++i) {
+        const int32_t bi = sBin[i];
+        n0 += (i < j0 && bi == b0) ? 1 : 0;
+        n1 += (bi == b1) ? 1 : 0;
+      }
+      if (b0 >= 0 && b0 < a.G && n0 == a.cap - 1) sClose[b0] = (unsigned char)j0;
+      if (b1 >= 0 && b1 < a.G && n1 == a.cap - 1) sClose[b1] = (unsigned char)j1;
+    }
+    __syncthreads();
+    LgPair open = none;
+    double tau = 1.0;
+    bool dead = true;                                         // all zeros: a bad temperature, a NaN in a base
+    if (active) {
+      sTc[j0] = b0 >= 0 && b0 < a.G && sClose[b0] != 0xff ? (int32_t)sClose[b0] : -1;
+      sTc[j1] = b1 >= 0 && b1 < a.G && sClose[b1] != 0xff ? (int32_t)sClose[b1] : -1;
+      const float tau_f = a.tau_u != nullptr ? a.tau_u[u] : a.tau;
+      const bool tau_ok = tau_f > 0.f && tau_f < LG_INF;
+      tau = tau_ok ? (double)tau_f : 1.0;
+      bool nan = false;
+      // the bins that never close, bin G among them: each lane its bins in ascending order, then the xor butterfly
+      for (int b = lane; b <= a.G; b += 64) {
+        const float gm = a.base_max[u * a.ld_base + b], bl = a.base_logsum[u * a.ld_base + b];
+        nan = nan || gm != gm || (gm != -LG_INF && bl != bl);
+        if (sClose[b] == 0xff) {
+          const LgPair B = {(double)gm, exp((double)bl)};
+          open = lg_join(open, B, tau);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const LgPair other = {__shfl_xor(open.m, o, 64), __shfl_xor(open.s, o, 64)};
+        open = lg_join(open, other, tau);
+      }
+      dead = !tau_ok || __any(nan);
+    }
+    __syncthreads();
+    LgPair S0 = none, S1 = none;                              // (M_j, sigma_j) of this lane's two places, where they are live steps
+    bool step0 = false, step1 = false;
+    if (active && !dead) {
+      // the walk, from the last place to the first, the same in every lane; the lane that holds place j keeps its D_j
+      LgPair acc = open;
+      for (int j = a.k - 1; j >= 0; --j) {
+        const uint32_t key = sKey[c * TK_ROWS + j];
+        if (key == 0u) continue;                              // fill or key 0: no step, in no sum
+        const LgPair P = {(double)key_score(key), 1.0};
+        const int32_t tc = sTc[j];
+        if (tc >= 0 && j > tc) {                              // blocked: its weight waits for the step its bin was last open
+          const LgPair st = lg_join({stM[tc], stS[tc]}, P, tau);
+          stM[tc] = st.m;
+          stS[tc] = st.s;
+        } else {
+          acc = lg_join(acc, P, tau);
+          if (tc == j) {
+            const int b = sBin[j];
+            const LgPair B = {(double)a.base_max[u * a.ld_base + b], exp((double)a.base_logsum[u * a.ld_base + b])};
+            acc = lg_join(acc, lg_join(B, {stM[j], stS[j]}, tau), tau);
+          }
+          if (j == j0) {
+            S0 = acc;
+            step0 = true;
+          }
+          if (j == j1) {
+            S1 = acc;
+            step1 = true;
+          }
+        }
+      }
+    }
+    __syncthreads();                                          // the stash is read; its arrays take the prefix sums
+    double x0 = 0.0, x1 = 0.0, g0 = 0.0, g1 = 0.0;
+    LgPair all = none, Q0 = none, Q1 = none;
+    if (active && !dead) {
+      x0 = (double)key_score(sKey[c * TK_ROWS + j0]);
+      x1 = (double)key_score(sKey[c * TK_ROWS + j1]);
+      g0 = step0 ? 1.0 : 0.0;
+      g1 = step1 ? 1.0 : 0.0;                                 // the g of anything that is no step is not read
+      if (a.g != nullptr) {
+        if (step0) g0 = (double)a.g[u * a.ld_g + j0];
+        if (step1) g1 = (double)a.g[u * a.ld_g + j1];
+      }
+      // inclusive prefix scan of (-M_j, g_j / sigma_j) over the live steps (sigma_j >= 1 there)
+      const LgPair T0 = step0 ? LgPair{-S0.m, g0 / S0.s} : none, T1 = step1 ? LgPair{-S1.m, g1 / S1.s} : none;
+      LgPair Q = lg_join(T0, T1, tau);
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const LgPair other = lg_up(Q, o);
+        if (lane >= o) Q = lg_join(other, Q, tau);
+      }
+      LgPair before = lg_up(Q, 1);                            // places 0 .. 2 l - 1
+      if (lane == 0) before = none;
+      Q0 = lg_join(before, T0, tau);
+      Q1 = lg_join(Q0, T1, tau);
+      all = {__shfl(Q.m, 63, 64), __shfl(Q.s, 63, 64)};
+      stM[j0] = Q0.m;
+      stS[j0] = Q0.s;
+      stM[j1] = Q1.m;
+      stS[j1] = Q1.s;
+    }
+    __syncthreads();
+    if (active) {
+      // c: at a live step q.m = -M_i; a blocked entry takes the q of the step that closed its bin, whose D holds its weight
+      double c0v = 0.0, c1v = 0.0;
+      if (!dead) {
+        const int32_t tc0 = sTc[j0], tc1 = sTc[j1];
+        if (step0) c0v = g0 - exp((x0 + Q0.m) / tau) * Q0.s;
+        else if (b0 >= 0 && tc0 >= 0 && j0 > tc0) c0v = -exp((x0 + stM[tc0]) / tau) * stS[tc0];
+        if (step1) c1v = g1 - exp((x1 + Q1.m) / tau) * Q1.s;
+        else if (b1 >= 0 && tc1 >= 0 && j1 > tc1) c1v = -exp((x1 + stM[tc1]) / tau) * stS[tc1];
+      }
+      if (j0 < a.k) a.out_sub_w[u * a.k + j0] = (float)c0v;
+      if (j1 < a.k) a.out_sub_w[u * a.k + j1] = (float)c1v;
+      // omega: lanes striding the bins; a closed bin takes the q of its closing step, an open one the q of the last live step
+      for (int b = lane; b <= a.G; b += 64) {
+        double w = 0.0;
+        if (!dead && all.m != NINF) {
+          const double gm = (double)a.base_max[u * a.ld_base + b], bl = (double)a.base_logsum[u * a.ld_base + b];
+          const int cl = sClose[b];
+          const double qm = cl == 0xff ? all.m : stM[cl], qs = cl == 0xff ? all.s : stS[cl];
+          if (gm != NINF) w = exp((gm + qm) / tau + bl) * qs;
+        }
+        a.out_bin_w[u * a.ld_base + b] = (float)w;
+      }
+    }
+    __syncthreads();                                          // the scratch is the next round's
+  }
+}
+
 // argument checks shared by the size query and the call; 0 = fine
 int logzg_check(const nr_logz_groups_desc* d) {
   NR_CHECK_ARG(d != nullptr, "score_logz_groups: null descriptor");
@@ -605,6 +848,42 @@ int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream) {
   const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
   NR_CHECK_RC(with_bool(a.pool.any(), [&](auto p) {
     return launch_lds(logp_capped_kernel<decltype(p)::value>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
+  }));
+  NR_CHECK_LAUNCH();
+  return NR_OK;
+}
+
+int nr_row_logprob_capped_grad(const nr_logprob_capped_grad_desc* d, nr_stream_t stream) {
+  NR_CHECK_ARG(d != nullptr, "row_logprob_capped_grad: null descriptor");
+  NR_CHECK_ARG(d->k >= 1 && d->k <= NR_TOPK_MAX_K, "row_logprob_capped_grad: k = %d entries per row, must be in [1, %d]", d->k, NR_TOPK_MAX_K);
+  NR_CHECK_RC(check_vectors("row_logprob_capped_grad", d->V, d->U, d->N));
+  NR_CHECK_ARG(d->tau_u != nullptr || (d->tau > 0.f && d->tau < LG_INF),
+               "row_logprob_capped_grad: tau = %g, a scalar temperature must be finite and > 0", (double)d->tau);
+  NR_CHECK_ARG(d->group_cap >= 1 && d->group_cap <= 128, "row_logprob_capped_grad: group_cap = %d, must be in [1, 128]", d->group_cap);
+  NR_CHECK_ARG(d->n_groups >= 1 && d->n_groups <= NR_RANK_MAX_GROUPS, "row_logprob_capped_grad: n_groups = %d, must be in [1, %d]", d->n_groups,
+               NR_RANK_MAX_GROUPS);
+  NR_CHECK_RC(check_pools("row_logprob_capped_grad", d->stamp, d->window, d->ld_window));
+  NR_CHECK_ARG(d->news_vecs && d->user && d->row_ids && d->group && d->base_max && d->base_logsum && d->out_bin_w && d->out_sub_w,
+               "row_logprob_capped_grad: null pointer (news_vecs, user, row_ids, group, base_max, base_logsum, out_bin_w, out_sub_w)");
+  NR_CHECK_RC(check_rows("row_logprob_capped_grad", d->news_vecs, d->ld_news, d->user, d->ld_user, d->N));
+  NR_CHECK_ARG(d->ld_ids >= d->k, "row_logprob_capped_grad: id row stride %d < k = %d", d->ld_ids, d->k);
+  NR_CHECK_ARG(d->ld_base >= d->n_groups + 1, "row_logprob_capped_grad: base row stride %d < n_groups + 1 = %d", d->ld_base, d->n_groups + 1);
+  NR_CHECK_ARG(d->g == nullptr || d->ld_g >= d->k, "row_logprob_capped_grad: g row stride %d < k = %d", d->ld_g, d->k);
+  NR_DEVICE_GUARD(stream, d->news_vecs);
+  hipStream_t s = (hipStream_t)stream;
+  LogpcGradArgs a;
+  a.news = d->news_vecs; a.user = d->user; a.ids = d->row_ids; a.group = d->group;
+  a.ld_news = (size_t)d->ld_news; a.ld_user = (size_t)d->ld_user; a.ld_ids = (size_t)d->ld_ids; a.ld_base = (size_t)d->ld_base;
+  a.ld_g = (size_t)d->ld_g;
+  a.V = d->V; a.U = d->U; a.N = d->N; a.k = d->k; a.cap = d->group_cap; a.G = d->n_groups;
+  a.pool = pool_args(d->prior, d->stamp, d->window, d->ld_window);
+  a.tau = d->tau; a.tau_u = d->tau_u;
+  a.base_max = d->base_max; a.base_logsum = d->base_logsum;
+  a.g = d->g; a.out_bin_w = d->out_bin_w; a.out_sub_w = d->out_sub_w;
+  NrProfScope ps(s, "logp_capped_grad[U=%d,N=%d,k=%d,cap=%d,G=%d]", d->U, d->N, d->k, d->group_cap, d->n_groups);
+  const size_t smem = tk_tile_bytes(16, d->N) + (size_t)2 * 16 * TK_ROWS * sizeof(int32_t);
+  NR_CHECK_RC(with_bool(a.pool.any(), [&](auto p) {
+    return launch_lds(logp_capped_grad_kernel<decltype(p)::value>, dim3((unsigned)((d->U + 15) / 16)), dim3(TK_THREADS), smem, s, a);
   }));
   NR_CHECK_LAUNCH();
   return NR_OK;

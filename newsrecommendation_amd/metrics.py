@@ -647,6 +647,155 @@ def capped_row_logprob_reference(a, b=None, *, row_ids, temperature, bases, grou
     return out, out.sum(axis=1)
 
 
+def expect_groups_reference(a, b, *, temperature, group, n_groups=None, bases=None, bin_w, exclude=None, prior=None, stamp=None, window=None):
+    """Host statement of the per-bin expected-news-vector contract (include/nrhip.h, nr_score_expect_groups); tests check the
+    device against it, no product path calls it.  float64 throughout.
+
+    `a` [V, N], `b` [U, N], `exclude`, the pools and what is eligible are logz_groups_reference's, and so are the bins of
+    `group` / `n_groups`.  bin_w [U, n_groups + 1] is omega.  Per (user, bin) over the bin's eligible news
+      p_b(v) = exp((score_v - gmax_b) / tau_u - logsum_b)
+    with (logsum, gmax) = bases when given (what logz_groups_reference or the device returned for the same arguments) and the
+    bin's own exact softmax when bases is None, and
+      expect[u] = sum_b omega_b sum_v p_b(v) a[v],   mass[u] = sum_b omega_b sum_v p_b(v)
+    A bin with omega == 0 contributes exactly nothing whatever its base holds; so does an empty bin.  A user with a non-empty
+    bin and a temperature that is not finite and > 0, or with a non-empty bin whose omega != 0 and whose omega is not finite,
+    whose gmax is NaN or +inf or whose logsum is NaN: a row of NaN and mass NaN.  Components of `a` that are not finite count as 0.
+    Returns (expect float64 [U, N], mass float64 [U])."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scores = b @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    bins, G = _bins(group, n_groups, V)
+    tau, tau_ok = _temperatures(temperature, U)
+    om = np.asarray(bin_w, dtype=np.float64).reshape(U, G + 1)
+    clean = np.where(np.isfinite(a), a, 0.0)
+    expect, mass = np.zeros((U, a.shape[1])), np.zeros(U)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for u in range(U):
+            ok = ~np.isnan(scores[u]) & pool[u]
+            ok[0] = False
+            if exclude is not None:
+                ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+                ok[ex[(ex >= 1) & (ex < V)]] = False
+            bad = False
+            for bb in range(G + 1):
+                sel = ok & (bins == bb)
+                x = scores[u, sel]
+                if bases is None:
+                    if x.size == 0:
+                        continue
+                    gm = x.max()
+                    ls = np.log(np.sum(np.exp((x - gm) / tau[u]))) if tau_ok[u] and np.isfinite(gm) else np.nan
+                else:
+                    ls, gm = float(np.asarray(bases[0], dtype=np.float64)[u, bb]), float(np.asarray(bases[1], dtype=np.float64)[u, bb])
+                    if gm == -np.inf:
+                        continue
+                if not tau_ok[u]:
+                    bad = True
+                    continue
+                if om[u, bb] == 0:
+                    continue
+                if not np.isfinite(om[u, bb]) or np.isnan(gm) or gm == np.inf or np.isnan(ls):
+                    bad = True
+                    continue
+                pw = np.exp((x - gm) / tau[u] - ls)
+                expect[u] += om[u, bb] * (pw @ clean[sel])
+                mass[u] += om[u, bb] * pw.sum()
+            if bad:
+                expect[u], mass[u] = np.nan, np.nan
+    return expect, mass
+
+
+def _capped_grad_rows(a, b, row_ids, temperature, bases, group, group_cap, n_groups, g, prior, stamp, window, mutant=None):
+    """capped_row_logprob_grad_reference's body.  `mutant` names a deliberately wrong formula (tests/test_capgrad_host.py shows
+    that each is caught by finite differences): "q_after_close" (Q at t_b + 1), "blocked_zero" (a blocked entry given c = 0),
+    "closed_full_q" (a closed bin given the full Q)."""
+    if not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
+    a = np.asarray(a, dtype=np.float64)
+    scores = a if b is None else np.asarray(b, dtype=np.float64) @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    bins, G = _bins(group, n_groups, V)
+    ids = np.asarray(row_ids, dtype=np.int64).reshape(U, -1)
+    k, c = ids.shape[1], int(group_cap)
+    tau, tau_ok = _temperatures(temperature, U)
+    bl, bm = np.asarray(bases[0], dtype=np.float64).reshape(U, G + 1), np.asarray(bases[1], dtype=np.float64).reshape(U, G + 1)
+    gs = np.ones((U, k)) if g is None else np.asarray(g, dtype=np.float64).reshape(U, k)
+    bin_w, sub_w = np.zeros((U, G + 1)), np.zeros((U, k))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for u in range(U):
+            real = (ids[u] >= 1) & (ids[u] < V)
+            at = np.where(real, ids[u], 0)
+            s = scores[u, at]
+            live = real & pool[u, at] & ~np.isnan(s)
+            if not tau_ok[u] or np.isnan(bm[u]).any() or (np.isnan(bl[u]) & (bm[u] > -np.inf)).any():
+                continue
+            bn = bins[at]
+            t_close = np.full(G + 1, k, dtype=np.int64)                # k stands for "never"
+            seen, capped = np.zeros(G + 1, dtype=np.int64), np.zeros(k, dtype=bool)
+            for j in np.flatnonzero(live):
+                if bn[j] < G:
+                    capped[j] = seen[bn[j]] >= c
+                    seen[bn[j]] += 1
+                    if seen[bn[j]] == c:
+                        t_close[bn[j]] = j
+            steps = np.flatnonzero(live & ~capped)
+            if steps.size == 0:
+                continue
+            lB = np.where(bm[u] > -np.inf, bm[u] / tau[u] + bl[u], -np.inf)      # log B_b
+            lx = s / tau[u]                                                   # log w_i
+            lD = np.full(k, np.inf)
+            for j in steps:
+                open_bins = t_close >= j
+                terms = np.concatenate([lx[j:][live[j:] & open_bins[bn[j:]]], lB[open_bins]])
+                lD[j] = np.logaddexp.reduce(terms)
+            gl = np.where(live & ~capped, gs[u], 0.0)
+            last = steps[-1]
+
+            def q_times(log_num, upto):
+                """sum_{j <= upto, j a live step} g_j exp(log_num - log D_j): every exponent <= 0 where log_num is a term of D_upto"""
+                js = steps[steps <= upto]
+                return float(np.sum(gl[js] * np.exp(log_num - lD[js]))) if js.size else 0.0
+
+            for i in range(k):
+                if not live[i]:
+                    continue
+                if capped[i]:
+                    sub_w[u, i] = 0.0 if mutant == "blocked_zero" else -q_times(lx[i], t_close[bn[i]])
+                else:
+                    sub_w[u, i] = gs[u, i] - q_times(lx[i], i)
+            for bb in range(G + 1):
+                if lB[bb] == -np.inf:
+                    continue
+                upto = min(t_close[bb], last)
+                if mutant == "q_after_close" and t_close[bb] < k:
+                    upto = t_close[bb] + 1
+                if mutant == "closed_full_q":
+                    upto = last
+                bin_w[u, bb] = q_times(lB[bb], upto)
+    return bin_w, sub_w
+
+
+def capped_row_logprob_grad_reference(a, b=None, *, row_ids, temperature, bases, group, group_cap, n_groups=None, g=None, prior=None,
+                                      stamp=None, window=None):
+    """Host statement of the gradient coefficients of a capped row (include/nrhip.h, nr_row_logprob_capped_grad); tests check
+    the device against it, no product path calls it.  float64, in logs.
+
+    The arguments are capped_row_logprob_reference's; g [U, k] is the upstream gradient of nll_j = -logp_j per entry (None = 1).
+    In that function's notation, with Q_j = sum_{j' <= j, j' a live step} g_j' / D_j' and Q_b = Q at min(t_b, last live step):
+      bin_w[u, b] = omega_b = B_b Q_b
+      sub_w[u, i] = c_i = g_i - w_i Q_i at a live step;  -w_i Q_{bin(i)} at a blocked entry (group already full; no step, its g
+                    is not looked at);  0 at fill and at entries outside the pool or with a NaN score
+    so that d (sum_j g_j nll_j) / d user = (sum_b omega_b E_b - sum_i c_i news[row_i]) / tau, E_b the softmax mean inside bin b
+    over the news of B_b (expect_groups_reference).  sum_b omega_b = sum_i c_i.  A temperature that is not finite and > 0, a NaN
+    gmax, a NaN logsum of a non-empty bin, or a row without a live step: zeros.  An empty bin has omega = 0.
+    Returns (bin_w float64 [U, n_groups + 1], sub_w float64 [U, k])."""
+    return _capped_grad_rows(a, b, row_ids, temperature, bases, group, group_cap, n_groups, g, prior, stamp, window)
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

@@ -1979,6 +1979,201 @@ def row_logprob_capped(news_vecs, user_vecs, row_ids, temperature, bases, group,
     return logp, total
 
 
+def _bin_args(what, bases, bin_w, U, B, dev):
+    """(logsum, gmax, omega) as contiguous fp32 [U, B] tensors: the first two results of score_logz_groups and the weights."""
+    out = []
+    for name, t in (("base logsum", bases[0]), ("base gmax", bases[1]), ("bin_w", bin_w)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U, B) or not t.is_floating_point() or t.device != dev:
+            raise RuntimeError(f"{what}: {name} must be a floating point tensor of shape ({U}, n_groups + 1 = {B}) on {dev}, "
+                               f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        out.append(t.detach().to(torch.float32).contiguous())
+    return out
+
+
+def _score_expect_groups(what, news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude, splits, prior, stamp, window, sub_ids, sub_w,
+                         scale_inv_tau):
+    """One nr_score_expect_groups call (include/nrhip.h, K20): (out [U, N] fp32, mass [U] fp32).  `exclude` holds ids and is
+    mapped to positions here, as in score_logz_groups."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    gr = _groups_arg(what, groups, V, dev)                                  # shapes first: these refusals need no GPU
+    bl, bm, om = _bin_args(what, bases, bin_w, U, gr.n_groups + 1, dev)
+    T = 0
+    if sub_ids is not None:
+        if sub_ids.dim() != 2 or sub_ids.shape[0] != U or sub_ids.is_floating_point() or tuple(sub_w.shape) != tuple(sub_ids.shape):
+            raise RuntimeError(f"{what}: the named rows must be integer ids [U = {U}, T] with weights of the same shape")
+        T = sub_ids.shape[1]
+        sub_ids = sub_ids.detach().to(torch.int32).contiguous()
+        sub_w = sub_w.detach().to(torch.float32).contiguous()
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, gr.order, bl, bm, om,
+              sub_ids, sub_w)
+    out = torch.empty(U, N, dtype=torch.float32, device=dev)
+    mass = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return out, mass
+    if isinstance(exclude, torch.Tensor):
+        if exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"{what}: exclude must be [U = {U}, E], got {tuple(exclude.shape)}")
+        exclude = ExclusionLists(exclude)
+    if isinstance(exclude, ExclusionLists) and exclude.U == U and exclude.device == dev:
+        exclude = gr.positions(exclude)
+    ex_fields, ex_keep = _exclude_args(what, exclude, U, dev, dense=False)
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    B = gr.n_groups + 1
+    d = _lib.ExpectGroupsDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                              ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u),
+                              order=ptr(gr.order), n_pos=gr.n_pos, seg_start=ptr(gr.seg_start), nseg=gr.nseg, bin_seg=ptr(gr.bin_seg),
+                              n_groups=gr.n_groups, base_max=ptr(bm), base_logsum=ptr(bl), bin_w=ptr(om), ld_base=B, sub_ids=ptr(sub_ids),
+                              sub_w=ptr(sub_w), ld_sub=T, T=T, scale_inv_tau=1 if scale_inv_tau else 0, out=ptr(out), ld_out=N, out_mass=ptr(mass),
+                              prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_groups_workspace_bytes(C.byref(d)), dev)    # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_groups(C.byref(d), _stream()), "nr_score_expect_groups")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_groups(news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """The expected news vector per bin under per-(user, bin) weights (nr_score_expect_groups; include/nrhip.h, K20): per user
+    sum_b bin_w[u, b] E_b, E_b = sum_{v in bin b} p_b(v) news_vecs[v], p_b(v) = exp((score_v - gmax_b) / temperature - logsum_b)
+    the softmax INSIDE bin b -- the gradient of score_logz_groups' per-group partitions with respect to the user vector, without
+    the [U, V] matrix.  `groups`: the ops.GroupOrder of the corpus; `bases` = (logsum, gmax[, count]): what score_logz_groups
+    returned for the SAME vectors, temperature, exclude and pools; `bin_w`: floating point [U, n_groups + 1].  The other
+    arguments are score_logz_groups' (`exclude` holds ids; `splits` at most groups.nseg).
+    Returns (expect fp32 [U, N], mass fp32 [U]): mass = sum_b bin_w_b sum_v p_b(v), up to rounding the sum of bin_w over the
+    non-empty bins.  A bin with bin_w == 0 contributes exactly nothing whatever its base holds, and so does an empty bin.  A user
+    with a non-empty bin and a bad entry of a temperature tensor, or with a non-empty bin of weight != 0 whose base is NaN (or
+    gmax +inf) or whose weight is not finite, gets NaN.  For a fixed splits > 0 a user's row does not depend, bit for bit, on
+    the other users of the call; across different splits rows agree to within the bound of DESIGN.md section 5."""
+    return _score_expect_groups("score_expect_groups", news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude, splits, prior, stamp,
+                                window, None, None, False)
+
+
+@torch.no_grad()
+def row_logprob_capped_grad(news_vecs, user_vecs, row_ids, temperature, bases, group, group_cap, n_groups=None, g=None, prior=None, stamp=None,
+                            window=None):
+    """The gradient coefficients of rows drawn under group caps (nr_row_logprob_capped_grad; include/nrhip.h, K21): the backward
+    of row_logprob_capped.  `row_ids`, `temperature`, `bases`, `group`, `group_cap`, `n_groups` and the pools are
+    row_logprob_capped's, the bases formed WITHOUT the row's ids; `g`: optional floating point [U, k], the upstream gradient of
+    nll_j = -logp_j per entry (None = 1).
+    Returns (bin_w fp32 [U, n_groups + 1], sub_w fp32 [U, k]) = (omega, c) with
+      d (sum_j g_j nll_j) / d user = (sum_b omega_b E_b - sum_i c_i news_vecs[row_i]) / temperature,
+    E_b the expected news vector inside bin b over what the bases sum over: nr_score_expect_groups with bin_w = omega, the row
+    and c as its named rows and the lists of the bases' score_logz_groups call.  Fill entries and entries outside the pool or
+    with a NaN score get c = 0 and their g is not read; an entry whose group was already full (logp -inf) is no step either, its
+    g is not read, and its c = -w_i Q is the pull of the earlier steps at which its group was open.  A user with a bad
+    temperature entry or a NaN base gets zeros; an empty bin gets omega = 0.  sum_b omega_b = sum_i c_i up to rounding."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    V, N, U, dev = _vector_args("row_logprob_capped_grad", news_vecs, user_vecs)
+    if row_ids.dim() != 2 or row_ids.shape[0] != U or row_ids.is_floating_point() or row_ids.device != dev:
+        raise RuntimeError(f"row_logprob_capped_grad: row_ids must be an integer tensor [U = {U}, k] on {dev}, got {tuple(row_ids.shape)} "
+                           f"{row_ids.dtype} on {row_ids.device}")
+    k = row_ids.shape[1]
+    bl, bm = bases[0], bases[1]
+    G = int(n_groups) if n_groups is not None else (bl.shape[1] - 1 if isinstance(bl, torch.Tensor) and bl.dim() == 2 else 0)
+    for name, t in (("base logsum", bl), ("base gmax", bm)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U, G + 1) or not t.is_floating_point() or t.device != dev:
+            raise RuntimeError(f"row_logprob_capped_grad: {name} must be a floating point tensor of shape ({U}, n_groups + 1 = {G + 1}) on "
+                               f"{dev}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != (U, k) or not g.is_floating_point() or g.device != dev):
+        raise RuntimeError(f"row_logprob_capped_grad: g must be a floating point tensor of shape ({U}, {k}) on {dev}")
+    gr = _group_args("row_logprob_capped_grad", group, V, dev)
+    _need_gpu(news_vecs, user_vecs, row_ids, prior, stamp, window, tau_t, bl, bm, gr, g)   # after the shapes: those refusals need no GPU
+    bin_w = torch.empty(U, G + 1, dtype=torch.float32, device=dev)
+    sub_w = torch.empty(U, k, dtype=torch.float32, device=dev)
+    if U == 0:
+        return bin_w, sub_w
+    if g is not None:
+        g = g.detach().to(torch.float32).contiguous()
+    bl, bm = bl.detach().to(torch.float32).contiguous(), bm.detach().to(torch.float32).contiguous()
+    ids = row_ids.detach().to(torch.int32).contiguous()
+    pr, st, win = _pool_args("row_logprob_capped_grad", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("row_logprob_capped_grad", temperature, U, dev)
+    d = _lib.LogprobCappedGradDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                                   ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, k=k, row_ids=ptr(ids), ld_ids=k, group=ptr(gr),
+                                   group_cap=int(group_cap), n_groups=G, tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl),
+                                   ld_base=G + 1, g=ptr(g), ld_g=k if g is not None else 0, out_bin_w=ptr(bin_w), out_sub_w=ptr(sub_w),
+                                   prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    check(_lib.lib().nr_row_logprob_capped_grad(C.byref(d), _stream()), "nr_row_logprob_capped_grad")
+    return bin_w, sub_w
+
+
+class CappedPlackettLuceNLLFunction(Function):
+    """nll [U, k] of the places of rows drawn under group caps, differentiable with respect to the user vectors (K21, then one
+    K20 call).  The news side has no pass yet: plackett_luce_nll_capped refuses a table that requires grad."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior, stamp, window):
+        user, news = user_vecs.detach(), news_vecs.detach()
+        V = news.shape[0]
+        taken = ExclusionLists(rows)
+        if exclude is None:
+            lists = taken
+        else:
+            lists = (exclude if isinstance(exclude, ExclusionLists) else ExclusionLists(exclude)).merged(taken)
+        bases = score_logz_groups(news, user, temperature, groups, exclude=lists, splits=splits, prior=prior, stamp=stamp, window=window)
+        logp, _ = row_logprob_capped(news, user, rows, temperature, bases, group, group_cap, n_groups=groups.n_groups, prior=prior, stamp=stamp,
+                                     window=window)
+        valid = (rows >= 1) & (rows < V) & torch.isfinite(logp)              # NaN: outside the pool; -inf: its group was full
+        if isinstance(temperature, torch.Tensor):
+            valid &= ((temperature > 0) & torch.isfinite(temperature))[:, None]
+        nll = torch.where(valid, -logp, torch.zeros_like(logp))
+        ctx.save_for_backward(user, news, rows, valid, bases[0], bases[1], group)
+        ctx.rest = (temperature, groups, group_cap, lists, splits, prior, stamp, window)
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return nll, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, news, rows, valid, bl, bm, group = ctx.saved_tensors
+        temperature, groups, group_cap, lists, splits, prior, stamp, window = ctx.rest
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 12
+        gw = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=g.device))
+        with torch.no_grad():
+            om, c = row_logprob_capped_grad(news, user, rows, temperature, (bl, bm), group, group_cap, n_groups=groups.n_groups, g=gw, prior=prior,
+                                            stamp=stamp, window=window)
+            grad_user, _ = _score_expect_groups("plackett_luce_nll_capped", news, user, temperature, groups, (bl, bm), om, lists, splits, prior,
+                                                stamp, window, rows, c, True)
+            # a user none of whose places count (all fill or invalid, a bad temperature) has no gradient: exactly 0, not 0 * NaN
+            grad_user = torch.where(valid.any(dim=1)[:, None], grad_user, torch.zeros_like(grad_user))
+        return (grad_user,) + (None,) * 11
+
+
+def plackett_luce_nll_capped(news_vecs, user_vecs, rows, temperature, groups, group, group_cap, exclude=None, splits=0, prior=None, stamp=None,
+                             window=None):
+    """The negative log-likelihood of ordered rows under the law score_sample(..., group, group_cap) draws from -- at every place
+    the softmax over the eligible news not yet taken whose group has fewer than group_cap entries in the row so far -- with a
+    gradient for `user_vecs`: the training-side counterpart of train.sample_propensity_capped.  rows: integer tensor
+    [U, k <= 128], 0 (or anything outside [1, V)) = fill.  `groups`: the ops.GroupOrder of `group` (int32 [V] on the device).
+    Forward: `rows` merged into `exclude`, score_logz_groups on those lists, row_logprob_capped -- what sample_propensity_capped
+    launches, so nll[valid] = -logp of it, bit for bit.  Returns (nll fp32 [U, k], valid bool [U, k]): valid is False at fill
+    entries, at entries row_logprob_capped gives NaN (outside the pool, a NaN score) or -inf (the entry's group was already
+    full: the capped sampler cannot have drawn it) and for users whose temperature is not finite and > 0; nll is 0 there.
+    Repeats within a row and entries inside `exclude` are the caller's statement (train.listwise_loss_capped turns them into fill).
+    Backward: ONE nr_row_logprob_capped_grad call (include/nrhip.h, K21) with g zeroed where not valid gives (omega, c); then
+    grad_user = (sum_b omega_b E_b - sum_i c_i news[row_i]) / temperature is ONE nr_score_expect_groups call (K20: bin_w omega,
+    named rows (rows, c), the merged lists, the saved bases).  A user without a valid place gets an exactly zero row.
+    `news_vecs` is a frozen table here: one that requires grad raises RuntimeError -- the news side of this gradient needs an
+    nr_score_expect_news with per-(user, bin) weights, which does not exist yet.  Temperature, prior and the rest get no gradient."""
+    if news_vecs.requires_grad:
+        raise RuntimeError("plackett_luce_nll_capped: news_vecs requires grad, but the news side of the capped gradient is a missing pass "
+                           "(nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table")
+    if rows.dim() != 2 or rows.shape[0] != user_vecs.shape[0] or rows.is_floating_point():
+        raise RuntimeError(f"plackett_luce_nll_capped: rows must be an integer tensor [U = {user_vecs.shape[0]}, k], got {tuple(rows.shape)} "
+                           f"{rows.dtype}")
+    if rows.shape[1] < 1 or rows.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"plackett_luce_nll_capped: k = {rows.shape[1]} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential "
+                           "row cannot be cut into chunks")
+    if not 1 <= int(group_cap) <= 128:
+        raise RuntimeError(f"plackett_luce_nll_capped: group_cap = {group_cap}, must be in [1, 128]")
+    _groups_arg("plackett_luce_nll_capped", groups, news_vecs.shape[0], news_vecs.device)
+    return CappedPlackettLuceNLLFunction.apply(user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior, stamp,
+                                               window)
+
+
 @torch.no_grad()
 def mmr_select(news_vecs, pool_ids, pool_scores, k, penalty, group=None, group_cap=None):
     """Diversified re-ranking of a pool (nr_mmr_select; include/nrhip.h, K11): Maximal Marginal Relevance over the M places of

@@ -714,6 +714,91 @@ def listwise_loss(model, news_table, hist_idx, mask, rows, temperature, weight=N
     return total / n.clamp(min=1).to(torch.float32), n
 
 
+def _blocked(rw, group, n_groups, group_cap):
+    """[U, k] bool: entries whose group already holds group_cap entries of the row before them (fill, id 0, counts for nothing;
+    news of no group are never blocked).  Such an entry is no step of a capped row, and neither it nor any later one of its group
+    is: the earlier ones alone use up the cap."""
+    bins = group.to(torch.int64)[rw.to(torch.int64)]
+    capped = (rw > 0) & (bins >= 0) & (bins < n_groups)
+    # a stable sort by group puts a group's entries side by side in row order: an entry's place in its run = the entries before it
+    srt, at = torch.sort(torch.where(capped, bins, torch.full_like(bins, n_groups)), dim=1, stable=True)
+    pos = torch.arange(rw.shape[1], device=rw.device, dtype=torch.int64)[None, :].expand_as(srt)
+    first = torch.ones_like(srt, dtype=torch.bool)
+    first[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    run = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), dim=1).values
+    return capped & torch.zeros_like(capped).scatter(1, at, (pos - run) >= int(group_cap))
+
+
+def listwise_loss_capped(model, news_table, hist_idx, mask, rows, temperature, news_group, group_cap, weight=None, exclude_history=True,
+                         batch_size=8192, prior=None, news_time=None, window=None, seen=None, groups=None):
+    """listwise_loss for rows served under group caps -- recommend_sample(..., news_group, group_cap): sample_propensity_capped's
+    quantity with a gradient for the user encoder.  rows [U, k <= 128] (0 = no entry); place j of a row is scored against the
+    eligible news not yet taken whose group has fewer than group_cap entries in the row so far, and
+      loss = sum_u sum_j weight * nll[u, j] / n,   nll[u, j] = -log P(entry j is drawn at step j | entries 0 .. j-1 are taken),
+    n the number of rows with at least one valid entry; weight as in listwise_loss: None, [U] or [U, k], a constant.
+    No [U, V] matrix: ops.plackett_luce_nll_capped (include/nrhip.h, K15, K16 forward; K21, K20 backward).  Built like
+    listwise_loss: the user vectors are formed WITH gradient, batch_size users at a time.  The news table is frozen here: the news
+    side of the capped gradient is a pass that does not exist yet, so a `news_table` that requires grad is refused.
+    An entry that is 0 or out of range, inside the user's exclusions, a repeat of an earlier entry of its row, or BLOCKED -- its
+    group already holds group_cap entries of the row -- is turned into fill before the forward.  For a blocked entry this
+    changes no D_j of a real step: as fill it is not merged into the lists, so its weight sits in its bin's base, which is part
+    of D_j at exactly the steps at which the bin is open -- the steps at which K16 counts the weight of a blocked entry.  An entry
+    outside the pool or NaN-scored, and every entry of a user whose temperature is not finite and > 0, is not valid either.  The
+    entries of a group are counted over the real entries of the row; K16 counts the live ones, so the two agree on every row
+    recommend_sample can have served under the same pools (it serves nothing outside the pool).
+    Returns (loss, n) as listwise_loss does.  groups: an ops.GroupOrder of news_group built beforehand; None builds it here."""
+    if isinstance(news_table, torch.Tensor) and news_table.requires_grad:
+        raise RuntimeError("listwise_loss_capped: news_table requires grad, but the news side of the capped gradient is a missing pass "
+                           "(nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table")
+    if not 1 <= int(group_cap) <= 128:
+        raise ValueError(f"listwise_loss_capped: group_cap = {group_cap}, must be in [1, 128]")
+    device = news_table.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    table = news_table.detach().float().contiguous()
+    U, V = hist.shape[0], table.shape[0]
+    rw = torch.as_tensor(rows).to(device=device, dtype=torch.int32)
+    if rw.dim() != 2 or rw.shape[0] != U:
+        raise RuntimeError(f"listwise_loss_capped: rows must be [U = {U}, k], got {tuple(rw.shape)}")
+    k = rw.shape[1]
+    if k < 1 or k > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"listwise_loss_capped: k = {k} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential row cannot be "
+                           "cut into chunks")
+    w = None
+    if weight is not None:
+        w = torch.as_tensor(weight).detach().to(device=device, dtype=torch.float32)
+        if tuple(w.shape) not in ((U,), (U, k)):
+            raise RuntimeError(f"listwise_loss_capped: weight must be [U = {U}] or [U, k = {k}], got {tuple(w.shape)}")
+        w = w[:, None].expand(U, k) if w.dim() == 1 else w
+    group, order = _group_order(news_group, groups, device)
+    if tuple(group.shape) != (V,):
+        raise RuntimeError(f"listwise_loss_capped: news_group must hold one id per news, [V = {V}], got {tuple(group.shape)}")
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    rw = rw.masked_fill(_not_ranked(exclude, rw, V), 0)       # what is no step of the row is named as fill: it is in no sum
+    rw = rw.masked_fill(_blocked(rw, group, order.n_groups, group_cap), 0)
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.embed_gather(table, hist[a:b], code), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) else tau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        nll, valid = ops.plackett_luce_nll_capped(table, user, rw[a:b].contiguous(), tau_b, order, group, group_cap, exclude=ex_b, **kw_b)
+        total = total + (nll.sum() if w is None else (nll * w[a:b]).sum())
+        n = n + valid.any(dim=1).sum()
+    return total / n.clamp(min=1).to(torch.float32), n
+
+
 @torch.no_grad()
 def expected_exposure(model, news_vecs, hist_idx, mask, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None,
                       window=None, seen=None):
