@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc, with n >= 20 out[18..19] = nr_expect_groups_desc, nr_logprob_capped_grad_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc, with n >= 20 out[18..19] = nr_expect_groups_desc, nr_logprob_capped_grad_desc, with n >= 21 out[20] = nr_expect_news_groups_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -1284,6 +1284,104 @@ typedef struct {
   int ld_window;
 } nr_logprob_capped_grad_desc;
 int nr_row_logprob_capped_grad(const nr_logprob_capped_grad_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K22  the news side of the capped row's gradient: K18 with K20's per-bin treatment.  With omega[u, b] and c[u, i] of K21,
+ *   d L / d news_v = sum_u (omega[u, bin(v)] / tau_u) p_bin(v)(v | u) user_u  -  sum_{(u, i): row_ui = v} (c_ui / tau_u) user_u
+ *   p_b(v | u) = exp((s_uv - gmax_ub) / tau_u - logsum_ub)        the softmax INSIDE bin b on K15's base of that bin
+ * over exactly the pairs (u, v) that are terms of K15's sum for bin(v): same score bits, same pools, same lists, row 0 never.
+ * The same d L / d s_uv that K20 contracts with news_v is contracted with user_u here.  No [U, V] matrix exists: a tile of news
+ * rows stays in LDS, the users are streamed past it in chunks of 128, and the scoring tile is followed by a second MFMA
+ * contraction out[TV, N] += P[TV, 128] . users[128, N] (K18's kernel).  metrics.expect_news_groups_reference states the contract
+ * on the host.
+ *   order, n_pos, n_groups   K15's group-major order (ops.GroupOrder).  The stationary tile (64, 32 or 16 rows: K18's table, a
+ *               function of N alone) is a tile of POSITIONS whose rows are gathered through order[].  Every bin's run starts at
+ *               a multiple of 128 positions, so a tile lies in ONE bin.  A position whose id is 0 (or outside [1, V)) is
+ *               padding: it is never alive and nothing is written for it; a tile that holds only padding returns before it
+ *               loads anything, so a run's padded tail costs at most one partly filled tile per bin.  Every id in [1, V) must
+ *               stand in order[] EXACTLY ONCE (ops.GroupOrder builds it so): a row is written where its id is met, so an id
+ *               that is left out leaves its row of `out` and `out_mass` unspecified (the finalize reads workspace nothing
+ *               wrote), and one that stands twice gets one of its two partials, whichever is stored last.  Neither reads or
+ *               writes outside the arrays.
+ *   bin_start   [n_groups + 2] int32: bin b owns positions bin_start[b] .. bin_start[b + 1] - 1.  A workgroup finds its bin once
+ *               (a search clamped into [0, n_groups]).
+ *   base_max, base_logsum, bin_w   BIN-MAJOR: [n_groups + 1, ld_bin] fp32, ld_bin >= U -- the transposes of K15's out_max /
+ *               out_logsum (of a call with the SAME vectors, lists, pools and temperatures) and of K21's omega.  Per chunk the
+ *               lanes load the three values of THEIR users for the tile's bin: 64 consecutive floats a wave.
+ *   excl_offsets, excl_users   optional, both or neither: the lists BY POSITION, [n_pos + 1] / [n_excl] int32: for position p
+ *               the ascending 0-based indices of the users whose list holds order[p] (ops.GroupOrder.by_position)
+ *   prior, stamp   indexed by news id, gathered for the tile's rows
+ *   scale_inv_tau   nonzero: a pair's coefficient is cf = fl(omega * fl(1 / tau_u)), otherwise omega; the pair's weight is
+ *               P = fl(cf * p), p = expf(s == gmax ? -logsum : fmaf(s - gmax, 1 / tau, -logsum)): K18's, omega for `weight`
+ *   named_offsets, named_user, named_w, n_named   K18's named terms, offsets [V + 1] BY NEWS ID
+ *   out         [V, ld_out] fp32, required.   out_mass   optional [V] fp32: sum_u omega[u, bin(v)] p over the exact products,
+ *               summed in fp64, without 1 / tau.  There is no mass-only mode.
+ * Live pairs.  A (user, bin) pair is live exactly when tau_u is finite and > 0, gmax and logsum are finite, and omega is finite
+ * and != 0.  A pair that is not live contributes exactly nothing and puts no NaN anywhere.  This differs from K20 ON PURPOSE:
+ * K20 answers such a user with a row of NaN, which stays with that user; on the news side one NaN would reach every row of the
+ * table.  Components of a user row that are not finite count as 0 in the second contraction and in the named terms.
+ * Named terms are gated by the USER ONLY: tau finite and > 0, named_w != 0, an index in [0, U), finite components -- NOT by a
+ * base.  Under caps a bin is routinely empty because the row took all of it, and its entries still carry c != 0.  (K18 gates
+ * its named terms by the user's single base; that contract is K18's and stays.)  Row 0 is in no order: it reads no partials
+ * and is exact zeros minus its named terms.
+ * Bits.  The user axis is cut by K18's plan (seg = 128 ceil(U / (128 * 256)) users a segment, slices = runs of whole segments;
+ * splits = 0: the library's choice by V).  Per (news, component) K18's chain; one [N] partial and one fp64 mass per (news,
+ * slice), written at the news ID, so the workspace is K18's and the finalize (K18's: slices ascending in fp64, minus the named
+ * terms with j ascending, one rounding) needs no position map.  For a fixed explicit `splits`, row v's bits depend on v's own
+ * inputs (vector, prior, stamp, list, named terms, its bin), on the users and their omega and bases for that bin, on U and on
+ * `splits` -- not on any other news, on v's place in its run or tile, or on the sizes of the other bins.  With one bin holding
+ * every news, omega = weight and K13's base in that bin's row, rows and mass are K18's bit for bit (live users).
+ * Error bound (derived in DESIGN.md section 5) against the exact result of the fp32 inputs, e = 2^-24:
+ *   |out_vc - out*_vc| <= kappa e A_vc,   A_vc = sum_u |cf_u| p*_uv |user_uc| + sum_j |d_j| |user_jc|,
+ *   kappa = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 29,   d_j = named_w[j] (/ tau_user)
+ *   |mass_v - mass*_v| <= (6 C + 5 ln n + 7 K + 29) e sum_u |omega_u,bin(v)| p_uv    against the p of the device's own scores
+ *               (against the p* of exact scores the score chain 2 (N + 1) G enters as well, as in K18)
+ * K18's kappa with omega for weight and K15's per-bin base for K13's: n the eligible news of the largest bin, C and G the
+ * maxima over the live (user, bin) pairs, K = 2 S (S = the chunks of K15's longest segment), L = 128 * (chunks of the longest
+ * user slice).
+ *   ws          nr_score_expect_news_groups_workspace_bytes(d): V * slices * (N * 4 + 8) bytes, rounded to 8 (0 = bad descriptor)
+ * Refused before any launch: what K18 refuses of the shared fields (null descriptor; V, U, N; n_excl < 0; excl_users without
+ * excl_offsets or the reverse; a bad scalar tau; splits above the user segments; stamp without window or the reverse; rows off
+ * 16 bytes); what K15 refuses of n_groups and n_pos; a null news_vecs, user, order, bin_start, base_max, base_logsum, bin_w or
+ * out; ld_bin < U; one or two of the three named arrays; n_named < 0; ld_out < N or an out off 16 bytes; an undersized
+ * workspace.  Layout: nr_expect_news_desc's fields in its order up to tau_u, then this call's, then the shared tail.        */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [n_pos + 1]: by position */
+  const int32_t* excl_users;   /* optional [n_excl]: ascending user indices per position */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const int32_t* order;        /* [n_pos] */
+  int n_pos;
+  const int32_t* bin_start;    /* [n_groups + 2] */
+  int n_groups;
+  const float* base_max;       /* [n_groups + 1, ld_bin]: out_max of K15, transposed */
+  const float* base_logsum;    /* [n_groups + 1, ld_bin]: out_logsum of K15, transposed */
+  const float* bin_w;          /* [n_groups + 1, ld_bin]: omega, transposed */
+  int ld_bin;
+  int scale_inv_tau;
+  const int32_t* named_offsets; /* optional [V + 1]; with named_user and named_w */
+  const int32_t* named_user;    /* optional [n_named] */
+  const float* named_w;         /* optional [n_named] */
+  int n_named;
+  float* out;                  /* [V, ld_out] */
+  int ld_out;
+  float* out_mass;             /* optional [V] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V], indexed by news id */
+  const int32_t* stamp;  /* optional [V], indexed by news id; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_news_groups_desc;
+size_t nr_score_expect_news_groups_workspace_bytes(const nr_expect_news_groups_desc* d);
+int nr_score_expect_news_groups(const nr_expect_news_groups_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

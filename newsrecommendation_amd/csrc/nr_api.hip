@@ -493,6 +493,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 17) out[16] = sizeof(nr_expect_news_desc);
   if (n >= 18) out[17] = sizeof(nr_logprob_grad_desc);
   if (n >= 20) { out[18] = sizeof(nr_expect_groups_desc); out[19] = sizeof(nr_logprob_capped_grad_desc); }
+  if (n >= 21) out[20] = sizeof(nr_expect_news_groups_desc);
   return NR_OK;
 }
 

@@ -796,6 +796,78 @@ def capped_row_logprob_grad_reference(a, b=None, *, row_ids, temperature, bases,
     return _capped_grad_rows(a, b, row_ids, temperature, bases, group, group_cap, n_groups, g, prior, stamp, window)
 
 
+def expect_news_groups_reference(a, b, *, temperature, group, n_groups=None, bases=None, bin_w, exclude=None, prior=None, stamp=None, window=None,
+                                 named=None, scale_inv_tau=False, dead=None):
+    """Host statement of the news side of the capped row's gradient (include/nrhip.h, nr_score_expect_news_groups); tests check
+    the device against it, no product path calls it.  float64 throughout.
+
+    `a` [V, N], `b` [U, N], `exclude` (per USER, ragged), the pools and what is eligible are logz_groups_reference's, and so are
+    the bins of `group` / `n_groups`.  bin_w [U, n_groups + 1] is omega, as everywhere (user-major).  Per (user, bin) over the
+    bin's eligible news p_b(v | u) = exp((score_uv - gmax_ub) / tau_u - logsum_ub), with (logsum, gmax) = bases when given and
+    the bin's own exact softmax when bases is None, and with cf_ub = omega_ub (/ tau_u if scale_inv_tau)
+      out[v]  = sum_u cf[u, bin(v)] p_bin(v)(v | u) b[u]  -  sum_j named_w[j] (/ tau_user if scale_inv_tau) b[named_user[j]]
+      mass[v] = sum_u omega[u, bin(v)] p_bin(v)(v | u)                          (never scaled by 1 / tau)
+    A (user, bin) pair is live exactly when tau_u is finite and > 0, gmax and logsum are finite and omega is finite and != 0; a
+    pair that is not live -- or that `dead` [U, n_groups + 1] marks: what only the device's bases know, a NaN in them -- contributes
+    nothing and leaves no NaN.  named = (offsets [V + 1], users [n], w [n]) as in expect_news_reference, but a named term is gated
+    by the USER only (temperature finite and > 0, w != 0, the index in [0, U)), never by a base: a bin emptied by the row still
+    receives its entries' terms.  Components of `b` that are not finite count as 0.  Row 0 is zeros minus its named terms.
+    Returns (out float64 [V, N], mass float64 [V], A float64 [V, N], M float64 [V]): A_vc = sum_u |cf| p |b_uc| + sum_j |d_j| |b_jc|
+    and M_v = sum_u |omega| p, the magnitude sums the error bound of DESIGN.md section 5 is stated on."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scores = b @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    bins, G = _bins(group, n_groups, V)
+    tau, tau_ok = _temperatures(temperature, U)
+    om = np.asarray(bin_w, dtype=np.float64).reshape(U, G + 1)
+    clean = np.where(np.isfinite(b), b, 0.0)
+    N = b.shape[1]
+    out, mass, A, M = np.zeros((V, N)), np.zeros(V), np.zeros((V, N)), np.zeros(V)
+    ok = ~np.isnan(scores) & pool
+    ok[:, 0] = False
+    if exclude is not None:
+        for u in range(U):
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[u, ex[(ex >= 1) & (ex < V)]] = False
+    tau_s = np.where(tau_ok, tau, 1.0)
+    it = np.where(tau_ok, 1.0 / tau_s, 0.0) if scale_inv_tau else tau_ok.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for bb in np.unique(bins[1:]):                                 # the users side by side, bin after bin
+            cols = np.flatnonzero(bins == bb)
+            okb = ok[:, cols]
+            has = okb.any(axis=1)
+            x = np.where(okb, scores[:, cols], -np.inf)
+            if bases is None:
+                gm = x.max(axis=1)
+                fin = has & tau_ok & np.isfinite(gm)
+                ls = np.where(fin, np.log(np.sum(np.exp((x - np.where(fin, gm, 0.0)[:, None]) / tau_s[:, None]), axis=1)), np.nan)
+            else:
+                ls, gm = np.asarray(bases[0], dtype=np.float64)[:, bb], np.asarray(bases[1], dtype=np.float64)[:, bb]
+            w = om[:, bb]
+            livep = tau_ok & has & np.isfinite(gm) & np.isfinite(ls) & np.isfinite(w) & (w != 0)
+            if dead is not None:
+                livep &= ~np.asarray(dead, dtype=bool)[:, bb]
+            w = np.where(livep, w, 0.0)
+            pw = np.where(okb & livep[:, None], np.exp((x - np.where(livep, gm, 0.0)[:, None]) / tau_s[:, None] - np.where(livep, ls, 0.0)[:, None]), 0.0)
+            out[cols] += pw.T @ ((w * it)[:, None] * clean)
+            A[cols] += pw.T @ (np.abs(w * it)[:, None] * np.abs(clean))
+            mass[cols] += pw.T @ w
+            M[cols] += pw.T @ np.abs(w)
+        if named is not None:
+            off, nu, nw = (np.asarray(x) for x in named)
+            for v in range(V):
+                for j in range(int(off[v]), int(off[v + 1])):
+                    u = int(nu[j])
+                    if nw[j] == 0 or not 0 <= u < U or not tau_ok[u]:
+                        continue
+                    out[v] -= float(nw[j]) * it[u] * clean[u]
+                    A[v] += abs(float(nw[j])) * it[u] * np.abs(clean[u])
+    return out, mass, A, M
+
+
 def retrieval_metrics_reference(ranks, ks):
     """Per-user full-corpus retrieval metrics from rank_reference-style ranks [U, T] (0 = not ranked; -1 = capped out, under
     group caps), and their sums over the users with n_u >= 1 ranked targets; n_u counts the ranks != 0, and a rank of -1 adds

@@ -1884,6 +1884,25 @@ class GroupOrder:
         offsets[1:] = torch.cumsum(torch.bincount(keys >> 31, minlength=lists.U), 0)
         return ExclusionLists.from_sorted(offsets, keys & ((1 << 31) - 1))
 
+    def by_position(self, lists):
+        """The lists transposed BY POSITION, which nr_score_expect_news_groups takes (include/nrhip.h, K22): (offsets int32
+        [n_pos + 1], users int32 [nnz]), for position p the ascending 0-based indices of the users whose list holds order[p] =
+        users[offsets[p] : offsets[p + 1]].  ExclusionLists.by_news with the ids mapped through `pos`; ids outside [1, V) are
+        dropped.  One sort of the keys position * 2^31 + user, bincount -> offsets.  The last result is kept with the lists (as
+        by_news keeps its own), so the calls of one batch of users over one order transpose once."""
+        kept = getattr(lists, "_by_position", None)
+        if kept is not None and kept[0] is self and kept[1] is lists.offsets and kept[2] is lists.ids:
+            return kept[3]
+        users, ids = lists._pairs()
+        keep = (ids >= 1) & (ids < self.V)
+        users, ids = users[keep], ids[keep]
+        keys = torch.unique_consecutive(torch.sort((self.pos.to(torch.int64)[ids] << 31) + users).values)
+        offsets = torch.zeros(self.n_pos + 1, dtype=torch.int64, device=keys.device)
+        offsets[1:] = torch.cumsum(torch.bincount(keys >> 31, minlength=self.n_pos), 0)
+        out = offsets.to(torch.int32), (keys & ((1 << 31) - 1)).to(torch.int32)
+        lists._by_position = (self, lists.offsets, lists.ids, out)
+        return out
+
 
 def _groups_arg(what, groups, V, dev):
     if not isinstance(groups, GroupOrder):
@@ -2101,7 +2120,7 @@ def row_logprob_capped_grad(news_vecs, user_vecs, row_ids, temperature, bases, g
 
 class CappedPlackettLuceNLLFunction(Function):
     """nll [U, k] of the places of rows drawn under group caps, differentiable with respect to the user vectors (K21, then one
-    K20 call).  The news side has no pass yet: plackett_luce_nll_capped refuses a table that requires grad."""
+    K20 call).  The news side is CappedPlackettLuceNLLJointFunction's: plackett_luce_nll_capped refuses a table that requires grad."""
 
     @staticmethod
     def forward(ctx, user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior, stamp, window):
@@ -2156,11 +2175,12 @@ def plackett_luce_nll_capped(news_vecs, user_vecs, rows, temperature, groups, gr
     Backward: ONE nr_row_logprob_capped_grad call (include/nrhip.h, K21) with g zeroed where not valid gives (omega, c); then
     grad_user = (sum_b omega_b E_b - sum_i c_i news[row_i]) / temperature is ONE nr_score_expect_groups call (K20: bin_w omega,
     named rows (rows, c), the merged lists, the saved bases).  A user without a valid place gets an exactly zero row.
-    `news_vecs` is a frozen table here: one that requires grad raises RuntimeError -- the news side of this gradient needs an
-    nr_score_expect_news with per-(user, bin) weights, which does not exist yet.  Temperature, prior and the rest get no gradient."""
+    `news_vecs` is a frozen table here: one that requires grad raises RuntimeError -- the news side of this gradient is the pass
+    of plackett_luce_nll_capped_joint (nr_score_expect_news_groups, K22); use that.  Temperature, prior and the rest get no gradient."""
     if news_vecs.requires_grad:
         raise RuntimeError("plackett_luce_nll_capped: news_vecs requires grad, but the news side of the capped gradient is a missing pass "
-                           "(nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table")
+                           "of this function (nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table, or "
+                           "use plackett_luce_nll_capped_joint")
     if rows.dim() != 2 or rows.shape[0] != user_vecs.shape[0] or rows.is_floating_point():
         raise RuntimeError(f"plackett_luce_nll_capped: rows must be an integer tensor [U = {user_vecs.shape[0]}, k], got {tuple(rows.shape)} "
                            f"{rows.dtype}")
@@ -2172,6 +2192,137 @@ def plackett_luce_nll_capped(news_vecs, user_vecs, rows, temperature, groups, gr
     _groups_arg("plackett_luce_nll_capped", groups, news_vecs.shape[0], news_vecs.device)
     return CappedPlackettLuceNLLFunction.apply(user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior, stamp,
                                                window)
+
+
+def _score_expect_news_groups(what, news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude, splits, prior, stamp, window, named,
+                              scale_inv_tau):
+    """One nr_score_expect_news_groups call (include/nrhip.h, K22): (out [V, N] fp32, mass [V] fp32).  `bases` / `bin_w` are
+    user-major [U, n_groups + 1] and transposed here; `exclude` holds ids per user and goes through GroupOrder.by_position;
+    named: None or (offsets int32 [V + 1], users int32 [n], w fp32 [n]) on the device."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    gr = _groups_arg(what, groups, V, dev)                                  # shapes first: these refusals need no GPU
+    B = gr.n_groups + 1
+    bl, bm, om = _bin_args(what, bases, bin_w, U, B, dev)
+    if exclude is not None and not isinstance(exclude, ExclusionLists):
+        if not isinstance(exclude, torch.Tensor) or exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"{what}: exclude must be a tensor [U = {U}, E] or an ExclusionLists")
+        exclude = ExclusionLists(exclude)
+    if exclude is not None and (exclude.U != U or exclude.device != dev):
+        raise RuntimeError(f"{what}: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
+    n_off = n_user = n_w = None
+    if named is not None:
+        n_off, n_user, n_w = named
+        if tuple(n_off.shape) != (V + 1,) or n_user.dim() != 1 or tuple(n_w.shape) != tuple(n_user.shape):
+            raise RuntimeError(f"{what}: the named terms must be offsets [V + 1 = {V + 1}] with users and weights of one length")
+    _need_gpu(news_vecs, user_vecs, exclude.ids if exclude is not None else None, prior, stamp, window, tau_t, gr.order, bl, bm, om,
+              *(named or ()))
+    if U == 0:                                                 # nobody: zeros, nothing to launch
+        return torch.zeros(V, N, dtype=torch.float32, device=dev), torch.zeros(V, dtype=torch.float32, device=dev)
+    out = torch.empty(V, N, dtype=torch.float32, device=dev)   # the finalize writes every row
+    mass = torch.empty(V, dtype=torch.float32, device=dev)
+    # bin-major [n_groups + 1, U]: a wave's 64 lanes then read 64 consecutive floats of their users for the tile's bin
+    bl, bm, om = bl.t().contiguous(), bm.t().contiguous(), om.t().contiguous()
+    ex_off = ex_users = None
+    if exclude is not None:
+        ex_off, ex_users = gr.by_position(exclude)
+    n_excl = 0 if ex_users is None else ex_users.numel()
+    if named is not None:
+        n_off, n_user, n_w = n_off.to(torch.int32).contiguous(), n_user.to(torch.int32).contiguous(), n_w.detach().to(torch.float32).contiguous()
+        if n_user.numel() == 0:
+            n_off = n_user = n_w = None
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    d = _lib.ExpectNewsGroupsDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                                  ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits),
+                                  excl_offsets=ptr(ex_off) if n_excl else None, excl_users=ptr(ex_users) if n_excl else None, n_excl=n_excl,
+                                  tau=tau, tau_u=ptr(tau_u), order=ptr(gr.order), n_pos=gr.n_pos, bin_start=ptr(gr.bin_start),
+                                  n_groups=gr.n_groups, base_max=ptr(bm), base_logsum=ptr(bl), bin_w=ptr(om), ld_bin=U,
+                                  scale_inv_tau=1 if scale_inv_tau else 0, named_offsets=ptr(n_off), named_user=ptr(n_user), named_w=ptr(n_w),
+                                  n_named=0 if n_user is None else n_user.numel(), out=ptr(out), ld_out=N, out_mass=ptr(mass),
+                                  prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_news_groups_workspace_bytes(C.byref(d)), dev)     # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_news_groups(C.byref(d), _stream()), "nr_score_expect_news_groups")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_news_groups(news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """The news side of score_expect_groups (nr_score_expect_news_groups; include/nrhip.h, K22): per news
+    D_v = sum_u bin_w[u, bin(v)] p_bin(v)(v | u) user_vecs[u], p_b(v | u) = exp((score_uv - gmax_ub) / temperature - logsum_ub) the
+    softmax INSIDE the news' bin, over exactly the pairs score_logz_groups sums over -- the gradient of sum_u sum_b bin_w[u, b]
+    temperature log Z_ub with respect to the news vector -- without the [U, V] matrix.  `groups`, `bases` = (logsum, gmax[, count])
+    and `bin_w` are score_expect_groups': user-major [U, n_groups + 1] (transposed inside, once per call); `exclude` is PER USER, in
+    ids, as everywhere (it goes through GroupOrder.by_position); the pools are score_logz_groups'.
+    Returns (out fp32 [V, N], mass fp32 [V]): mass[v] = sum_u bin_w[u, bin(v)] p_bin(v)(v | u).  A (user, bin) pair whose temperature
+    is not finite and > 0, whose base is NaN or infinite (an empty bin: gmax = -inf) or whose weight is 0, NaN or infinite
+    contributes nothing and leaves no NaN -- unlike score_expect_groups, which gives such a user a NaN row: here one NaN would
+    reach every row of the table.  Row 0 is zeros.
+    `splits`: 0 = the library chooses the number of USER slices by V (at most the user segments of K18's plan).  For a fixed
+    splits > 0 a row's bits do not depend on the other news, on its place in its bin's run, or on the sizes of the other bins;
+    across different splits rows agree within the bound of DESIGN.md section 5."""
+    return _score_expect_news_groups("score_expect_news_groups", news_vecs, user_vecs, temperature, groups, bases, bin_w, exclude, splits, prior,
+                                     stamp, window, None, False)
+
+
+class CappedPlackettLuceNLLJointFunction(Function):
+    """nll [U, k] of the places of rows drawn under group caps, differentiable with respect to the user vectors (K21, then one
+    K20 call) and the news-vector table (the same K21 call's coefficients, then one K22 call)."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior, stamp, window):
+        return CappedPlackettLuceNLLFunction.forward(ctx, user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits,
+                                                     prior, stamp, window)
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, news, rows, valid, bl, bm, group = ctx.saved_tensors
+        temperature, groups, group_cap, lists, splits, prior, stamp, window = ctx.rest
+        if g is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 12
+        gw = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=g.device))
+        grad_user = grad_news = None
+        with torch.no_grad():
+            # ONE K21 call for both sides: omega per (user, bin), c per entry
+            om, c = row_logprob_capped_grad(news, user, rows, temperature, (bl, bm), group, group_cap, n_groups=groups.n_groups, g=gw, prior=prior,
+                                            stamp=stamp, window=window)
+            if ctx.needs_input_grad[0]:
+                grad_user, _ = _score_expect_groups("plackett_luce_nll_capped_joint", news, user, temperature, groups, (bl, bm), om, lists, splits, prior,
+                                                    stamp, window, rows, c, True)
+                # a user none of whose places count (all fill or invalid, a bad temperature) has no gradient: exactly 0, not 0 * NaN
+                grad_user = torch.where(valid.any(dim=1)[:, None], grad_user, torch.zeros_like(grad_user))
+            if ctx.needs_input_grad[1]:
+                # K22 takes the user slices by its own plan: `splits` is K15's / K20's cut of the order and does not apply
+                grad_news, _ = _score_expect_news_groups("plackett_luce_nll_capped_joint", news, user, temperature, groups, (bl, bm), om, lists, 0,
+                                                         prior, stamp, window, _named_by_news(rows, c, news.shape[0]), True)
+        return (grad_user, grad_news) + (None,) * 10
+
+
+def plackett_luce_nll_capped_joint(news_vecs, user_vecs, rows, temperature, groups, group, group_cap, exclude=None, splits=0, prior=None,
+                                   stamp=None, window=None):
+    """plackett_luce_nll_capped, differentiable with respect to `user_vecs` AND the table `news_vecs`: either may require grad.
+    The forward is plackett_luce_nll_capped's (the rows merged into `exclude`, score_logz_groups, row_logprob_capped), bit for
+    bit, and returns (nll fp32 [U, k], valid bool [U, k]) as it does.  Backward: ONE nr_row_logprob_capped_grad call (K21) gives
+    (omega, c) for both sides; grad_user is plackett_luce_nll_capped's single nr_score_expect_groups call (K20), bit for bit;
+    grad_news [V, N] is ONE nr_score_expect_news_groups call (include/nrhip.h, K22) with bin_w = omega, the 1 / temperature scale
+    inside, the merged lists, the saved bases, and the row's entries with their c as its named terms (stable sort by news id;
+    entries with c = 0 and fill dropped):
+      grad_news[v] = sum_u omega[u, bin(v)] / tau_u p_bin(v)(v | u) user_u  -  sum_{(u, i): row_ui = v} c_ui / tau_u user_u.
+    A named term does not depend on its bin's base: a bin the row emptied still receives its entries' terms.  News that are
+    eligible for nobody and named by nobody get an exactly zero row; row 0 always.  A pass whose input does not require grad is
+    not launched (neither requires grad: K21 is not launched either).  Temperature, prior and the other arguments get no gradient."""
+    if rows.dim() != 2 or rows.shape[0] != user_vecs.shape[0] or rows.is_floating_point():
+        raise RuntimeError(f"plackett_luce_nll_capped_joint: rows must be an integer tensor [U = {user_vecs.shape[0]}, k], got {tuple(rows.shape)} "
+                           f"{rows.dtype}")
+    if rows.shape[1] < 1 or rows.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"plackett_luce_nll_capped_joint: k = {rows.shape[1]} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a "
+                           "sequential row cannot be cut into chunks")
+    if not 1 <= int(group_cap) <= 128:
+        raise RuntimeError(f"plackett_luce_nll_capped_joint: group_cap = {group_cap}, must be in [1, 128]")
+    _groups_arg("plackett_luce_nll_capped_joint", groups, news_vecs.shape[0], news_vecs.device)
+    return CappedPlackettLuceNLLJointFunction.apply(user_vecs, news_vecs, rows, temperature, groups, group, group_cap, exclude, splits, prior,
+                                                    stamp, window)
 
 
 @torch.no_grad()

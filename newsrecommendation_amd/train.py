@@ -737,8 +737,8 @@ def listwise_loss_capped(model, news_table, hist_idx, mask, rows, temperature, n
       loss = sum_u sum_j weight * nll[u, j] / n,   nll[u, j] = -log P(entry j is drawn at step j | entries 0 .. j-1 are taken),
     n the number of rows with at least one valid entry; weight as in listwise_loss: None, [U] or [U, k], a constant.
     No [U, V] matrix: ops.plackett_luce_nll_capped (include/nrhip.h, K15, K16 forward; K21, K20 backward).  Built like
-    listwise_loss: the user vectors are formed WITH gradient, batch_size users at a time.  The news table is frozen here: the news
-    side of the capped gradient is a pass that does not exist yet, so a `news_table` that requires grad is refused.
+    listwise_loss: the user vectors are formed WITH gradient, batch_size users at a time.  The news table is frozen here: a
+    `news_table` that requires grad is refused; listwise_loss_capped_joint is the function that trains it.
     An entry that is 0 or out of range, inside the user's exclusions, a repeat of an earlier entry of its row, or BLOCKED -- its
     group already holds group_cap entries of the row -- is turned into fill before the forward.  For a blocked entry this
     changes no D_j of a real step: as fill it is not merged into the lists, so its weight sits in its bin's base, which is part
@@ -749,30 +749,52 @@ def listwise_loss_capped(model, news_table, hist_idx, mask, rows, temperature, n
     Returns (loss, n) as listwise_loss does.  groups: an ops.GroupOrder of news_group built beforehand; None builds it here."""
     if isinstance(news_table, torch.Tensor) and news_table.requires_grad:
         raise RuntimeError("listwise_loss_capped: news_table requires grad, but the news side of the capped gradient is a missing pass "
-                           "(nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table")
+                           "of this function (nr_score_expect_news with per-(user, bin) weights); it is not emulated: detach the table, "
+                           "or use listwise_loss_capped_joint")
+    return _listwise_loss_capped("listwise_loss_capped", False, model, news_table, hist_idx, mask, rows, temperature, news_group, group_cap, weight,
+                                 exclude_history, batch_size, prior, news_time, window, seen, groups)
+
+
+def listwise_loss_capped_joint(model, news_table, hist_idx, mask, rows, temperature, news_group, group_cap, weight=None, exclude_history=True,
+                               batch_size=8192, prior=None, news_time=None, window=None, seen=None, groups=None):
+    """listwise_loss_capped with a news-vector table that may require grad: the same loss, the same valid entries, the same
+    (loss, n), and a gradient for `news_table` ([V, news_dim] fp32 on the GPU: a table that is fine-tuned directly, or the output
+    of the news encoder) as well as for the user encoder.  The table is reached on two paths: the capped law itself
+    (ops.plackett_luce_nll_capped_joint: one nr_score_expect_news_groups call per chunk of users, include/nrhip.h K22, on the
+    coefficients of the same K21 call that serves the user side) and the clicked histories, whose vectors are gathered with
+    ops.news_gather (a scatter-add with fp32 atomics in backward: the last bits of the table gradient depend on the arrival
+    order).  A table that does not require grad gives listwise_loss_capped's gradients; the news pass is then not launched."""
+    return _listwise_loss_capped("listwise_loss_capped_joint", True, model, news_table, hist_idx, mask, rows, temperature, news_group, group_cap,
+                                 weight, exclude_history, batch_size, prior, news_time, window, seen, groups)
+
+
+def _listwise_loss_capped(what, joint, model, news_table, hist_idx, mask, rows, temperature, news_group, group_cap, weight, exclude_history,
+                          batch_size, prior, news_time, window, seen, groups):
+    """The body of listwise_loss_capped (joint = False: the table detached, gathered without gradient) and of
+    listwise_loss_capped_joint (joint = True: ops.news_gather and ops.plackett_luce_nll_capped_joint)."""
     if not 1 <= int(group_cap) <= 128:
-        raise ValueError(f"listwise_loss_capped: group_cap = {group_cap}, must be in [1, 128]")
+        raise ValueError(f"{what}: group_cap = {group_cap}, must be in [1, 128]")
     device = news_table.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
-    table = news_table.detach().float().contiguous()
+    table = news_table.float().contiguous() if joint else news_table.detach().float().contiguous()
     U, V = hist.shape[0], table.shape[0]
     rw = torch.as_tensor(rows).to(device=device, dtype=torch.int32)
     if rw.dim() != 2 or rw.shape[0] != U:
-        raise RuntimeError(f"listwise_loss_capped: rows must be [U = {U}, k], got {tuple(rw.shape)}")
+        raise RuntimeError(f"{what}: rows must be [U = {U}, k], got {tuple(rw.shape)}")
     k = rw.shape[1]
     if k < 1 or k > _lib.NR_TOPK_MAX_K:
-        raise RuntimeError(f"listwise_loss_capped: k = {k} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential row cannot be "
+        raise RuntimeError(f"{what}: k = {k} places per row, must be in [1, {_lib.NR_TOPK_MAX_K}]: a sequential row cannot be "
                            "cut into chunks")
     w = None
     if weight is not None:
         w = torch.as_tensor(weight).detach().to(device=device, dtype=torch.float32)
         if tuple(w.shape) not in ((U,), (U, k)):
-            raise RuntimeError(f"listwise_loss_capped: weight must be [U = {U}] or [U, k = {k}], got {tuple(w.shape)}")
+            raise RuntimeError(f"{what}: weight must be [U = {U}] or [U, k = {k}], got {tuple(w.shape)}")
         w = w[:, None].expand(U, k) if w.dim() == 1 else w
     group, order = _group_order(news_group, groups, device)
     if tuple(group.shape) != (V,):
-        raise RuntimeError(f"listwise_loss_capped: news_group must hold one id per news, [V = {V}], got {tuple(group.shape)}")
+        raise RuntimeError(f"{what}: news_group must hold one id per news, [V = {V}], got {tuple(group.shape)}")
     exclude = _exclusions(hist, m, exclude_history, seen, device)
     kw = _pool_kwargs(device, prior, news_time, window)
     tau = _device_temperature(temperature, U, device)
@@ -782,10 +804,12 @@ def listwise_loss_capped(model, news_table, hist_idx, mask, rows, temperature, n
     code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
     total = torch.zeros((), dtype=torch.float32, device=device)
     n = torch.zeros((), dtype=torch.int64, device=device)
+    gather = ops.news_gather if joint else ops.embed_gather
+    nll_op = ops.plackett_luce_nll_capped_joint if joint else ops.plackett_luce_nll_capped
     step = max(int(batch_size), 1)
     for a in range(0, U, step):
         b = min(U, a + step)
-        user = model.user_encoder(ops.embed_gather(table, hist[a:b], code), m[a:b]).float().contiguous()
+        user = model.user_encoder(gather(table, hist[a:b], code), m[a:b]).float().contiguous()
         kw_b = dict(kw)
         if "window" in kw_b:
             kw_b["window"] = kw_b["window"][a:b].contiguous()
@@ -793,7 +817,7 @@ def listwise_loss_capped(model, news_table, hist_idx, mask, rows, temperature, n
         ex_b = exclude
         if exclude is not None and (a, b) != (0, U):
             ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
-        nll, valid = ops.plackett_luce_nll_capped(table, user, rw[a:b].contiguous(), tau_b, order, group, group_cap, exclude=ex_b, **kw_b)
+        nll, valid = nll_op(table, user, rw[a:b].contiguous(), tau_b, order, group, group_cap, exclude=ex_b, **kw_b)
         total = total + (nll.sum() if w is None else (nll * w[a:b]).sum())
         n = n + valid.any(dim=1).sum()
     return total / n.clamp(min=1).to(torch.float32), n

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""The gradient of rows served under group caps (ops.score_expect_groups, K20; ops.row_logprob_capped_grad, K21; include/nrhip.h)
+"""The gradient of rows served under group caps (ops.score_expect_groups, K20; ops.row_logprob_capped_grad, K21;
+ops.score_expect_news_groups, K22; include/nrhip.h)
 beside the calls it is built like, and the capped listwise loss (ops.plackett_luce_nll_capped) beside the uncapped one.
 
     python tools/capgrad_probe.py [--news 100001] [--dim 400] [--users 64 8192] [--groups 18 285] [--places 10] [--cap 2]
@@ -13,11 +14,16 @@ one process, each between a pair of device events (median, minimum, maximum and 
   row_logprob_capped (K16) beside row_logprob_capped_grad (K21);
   forward + backward (user gradient) of plackett_luce_nll_capped beside plackett_luce_nll and beside the two forward launches alone
   (train.sample_propensity_capped's: score_logz_groups + row_logprob_capped).
+  the news side: score_expect_news (K18) beside score_expect_news_groups (K22) with the same users, table, lists and named terms --
+  `tile_floor` = (non-padding tiles of the order) / (tiles of V) is the floor of that ratio; forward + backward with BOTH gradients
+  of plackett_luce_nll_capped_joint beside plackett_luce_nll_capped (user gradient alone) and beside plackett_luce_nll with both
+  gradients; the three transposes K22's Python layer makes per call, GroupOrder.by_position and ExclusionLists.by_news, each alone.
 One JSON line per (U, groups).  Needs a GPU: there is nothing to fall back to."""
 import argparse
 import json
 import math
 import os
+import re
 import sys
 
 import torch
@@ -25,7 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from logz_probe import interleaved, launch_shares  # noqa: E402
-from newsrecommendation_amd import ops  # noqa: E402
+from newsrecommendation_amd import _lib, ops  # noqa: E402
 
 TAU = 0.5
 
@@ -36,6 +42,68 @@ def skewed_groups(V, n_groups, gen):
     g = torch.multinomial(w / w.sum(), V, replacement=True, generator=gen).to(torch.int32)
     g[torch.rand(V, generator=gen) < 0.1] = -1
     return g
+
+
+def stream_tile(call):
+    """The news tile of a K22 call, read from the label the library gives its stream launch (`TV=`): the LDS plan is the library's."""
+    call()
+    torch.cuda.synchronize()
+    _lib.prof_enable(1)
+    try:
+        _lib.prof_collect()
+        call()
+        torch.cuda.synchronize()
+        labels = list(_lib.prof_collect())
+    finally:
+        _lib.prof_enable(0)
+    (label,) = [x for x in labels if x.startswith("expect_news_groups_stream[")]
+    return int(re.search(r"TV=(\d+)", label).group(1))
+
+
+def tile_floor(order, V, TV):
+    """(non-padding tiles of the order) / (tiles of V): what K22 streams the users past, beside K18"""
+    alive = (order.order.reshape(-1, TV) != 0).any(dim=1).sum().item()
+    return alive, math.ceil(V / TV)
+
+
+def news_side(news, user, rows, lists, base, bases, om, c, a19, gup, order, group, n_groups, cap, args):
+    """K22 beside K18 with the same users and table; the capped joint loss (both gradients) beside the frozen-table one and beside
+    plackett_luce_nll with both gradients; the three transposes and GroupOrder.by_position each on its own."""
+    V, N = news.shape
+    named = ops._named_by_news(rows, c, V)
+    calls = {"expect_news": lambda: ops._score_expect_news("probe", news, user, TAU, base, lists, 0, None, None, None, a19, named, True, True),
+             "expect_news_groups": lambda: ops._score_expect_news_groups("probe", news, user, TAU, order, bases, om, lists, 0, None, None, None,
+                                                                         named, True),
+             "three_transposes": lambda: (bases[0].t().contiguous(), bases[1].t().contiguous(), om.t().contiguous()),
+             "by_position": lambda: order.by_position(ops.ExclusionLists.from_sorted(lists.offsets, lists.ids)),     # a fresh object: nothing kept
+             "by_news": lambda: ops.ExclusionLists.from_sorted(lists.offsets, lists.ids).by_news(V)}
+    TV = stream_tile(calls["expect_news_groups"])
+    alive, tiles_v = tile_floor(order, V, TV)
+    out = {"news_tile": TV, "tiles_alive": alive, "tiles_of_V": tiles_v, "tile_floor": round(alive / tiles_v, 4)}
+    out.update(interleaved(calls, args.calls, args.warmup))
+    out["expect_news_groups_over_expect_news"] = round(out["expect_news_groups"]["median_ms"] / out["expect_news"]["median_ms"], 4)
+    out["expect_news_groups_launch_shares"] = launch_shares(calls["expect_news_groups"])
+    uv, nv = user.clone().requires_grad_(True), news.clone().requires_grad_(True)
+
+    def joint():
+        uv.grad = nv.grad = None
+        o, _ = ops.plackett_luce_nll_capped_joint(nv, uv, rows, TAU, order, group, cap)
+        (o * gup).sum().backward()
+
+    def frozen():
+        uv.grad = None
+        o, _ = ops.plackett_luce_nll_capped(news, uv, rows, TAU, order, group, cap)
+        (o * gup).sum().backward()
+
+    def free_both():
+        uv.grad = nv.grad = None
+        o, _ = ops.plackett_luce_nll(nv, uv, rows, TAU)
+        (o * gup).sum().backward()
+
+    out.update(interleaved({"pl_capped_joint": joint, "pl_capped_frozen": frozen, "pl_both": free_both}, args.calls, args.warmup))
+    out["pl_capped_joint_over_frozen"] = round(out["pl_capped_joint"]["median_ms"] / out["pl_capped_frozen"]["median_ms"], 4)
+    out["pl_capped_joint_over_pl_both"] = round(out["pl_capped_joint"]["median_ms"] / out["pl_both"]["median_ms"], 4)
+    return out
 
 
 def main():
@@ -100,6 +168,7 @@ def main():
             row.update(interleaved({"pl_capped": capped, "pl": free, "propensity_capped": propensity}, args.calls, args.warmup))
             row["pl_capped_over_pl"] = round(row["pl_capped"]["median_ms"] / row["pl"]["median_ms"], 4)
             row["pl_capped_over_propensity"] = round(row["pl_capped"]["median_ms"] / row["propensity_capped"]["median_ms"], 4)
+            row.update(news_side(news, user, rows, lists, base, bases, om, c, a19, gup, order, group, n_groups, cap, args))
             lines.append(row)
             print(json.dumps(row), flush=True)
             del uv, user
