@@ -1384,6 +1384,113 @@ size_t nr_score_expect_news_groups_workspace_bytes(const nr_expect_news_groups_d
 int nr_score_expect_news_groups(const nr_expect_news_groups_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K23  entropy of the served distribution.  With K13's base the device forms x_v = fmaf(s_v - max, 1 / tau, -logsum) = log p_v
+ * and p_v = expf(x_v) exactly as K17 does; per user, over exactly the news K13 sums over (same score bits, pools, CSR lists),
+ *   m0 = sum p,   m1 = sum p x,   m2 = sum p x^2
+ * and three results, each [U] fp32 (metrics.entropy_reference states the contract on the host):
+ *   out_entropy   H = -m1 = -sum_v p(v | u) log p(v | u); exp(H) is the effective number of news the user is exposed to
+ *   out_var       optional: Var_p(log p) = m2 - m1^2 (formed in fp64); dH / dtau = out_var / tau
+ *   out_mass      optional: m0 -- 1 up to rounding when the base matches the arguments (K17's mass)
+ * A pair with p == 0 (not eligible, expf underflowed, a score of -inf) is a term of no sum: 0 log 0 = 0, and 0 * -inf is never
+ * formed.  No [U, V] matrix exists; the pass is K13's stream (grid, segments, slices, user tile, LDS) without the running
+ * maximum -- the base is known.
+ *   base_max, base_logsum, tau, tau_u, lists, pools   K17's fields and meaning
+ *   edge cases  nothing eligible (base_max = -inf, whatever tau_u holds): 0, 0, 0.  A tau_u entry that is <= 0, NaN or infinite,
+ *               or a NaN in the user's base: NaN for that user's three results, nobody else's change.  Exactly one eligible
+ *               news: H == 0.0 and var == 0.0 exactly (x = -logsum = -0, p = 1).
+ * Bits.  Per pair the products p x and (p x) x are formed in fp64 from the fp32 p and x and added to three per-lane fp64 chains
+ * over the lane's news of the slice (which lane sees which id is fixed by V); an xor butterfly leaves one triple per (user,
+ * slice); a second kernel adds the slices in ascending order in fp64 and rounds each result to fp32 once.  For a fixed explicit
+ * `splits` a user's three results depend on that user's inputs and V only -- not on U, the user tile or the place in it.
+ * Error bounds (derived in DESIGN.md section 5; first order in e = 2^-24) against the exact H*, m2* = sum p* x*^2, var* of the
+ * fp32 inputs.  x carries the ABSOLUTE error kappa_x e,
+ *   kappa_x = 2 (N + 1) G + 6 C + 5 ln n + 7 K + 14          (n, C, G, K as in K17)
+ *   |H - H*|     <= ((kappa_x + 8) H* + kappa_x + 1) e + n 2^-119
+ *   |var - var*| <= ((kappa_x + 8) (m2* + 2 H*^2) + 4 kappa_x H* + 1) e + n 2^-112
+ *   |mass - 1|   <= (6 C + 5 ln n + 7 K + 23) e                                   (K17's)
+ * the last terms what weights below the normal range (x < -87) lose.
+ *   ws          nr_score_entropy_workspace_bytes(d): U * slices * 24 bytes (0 = bad descriptor)
+ * Refused before any launch: what K17 refuses of the shared fields; a null base_max / base_logsum / out_entropy; an undersized
+ * workspace.  Layout: nr_logz_desc's fields in its order up to tau_u, then this call's, then the shared tail.                */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 */
+  const float* base_logsum;    /* [U]: out_logsum of K13 */
+  float* out_entropy;          /* [U] */
+  float* out_var;              /* optional [U] */
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_entropy_desc;
+size_t nr_score_entropy_workspace_bytes(const nr_entropy_desc* d);
+int nr_score_entropy(const nr_entropy_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K24  K17 with a per-pair weight that is affine in log p: the gradient of the entropy, and of any loss
+ *   L = sum_t g_t nll(u, t) + h_u H_u:    d L / d user_u = ((sum_t g_t - h H) E - h J - sum_t g_t news[t]) / tau_u
+ * with E = sum_v p_v news_v (K17's) and J = sum_v p_v x_v news_v, x = log p (d H / d user = -(J + H E) / tau).  One contraction,
+ *   out[u] = (sum_v r_v news_v - sum_t sub_w[u, t] news[sub_ids[u, t]]) (* 1 / tau_u),   r_v = p_v fmaf(beta_u, x_v, alpha_u),
+ * so alpha = sum_t g_t - h H, beta = -h, sub_w = g, scale_inv_tau gives that gradient in one call.
+ * metrics.expect_affine_reference states the contract on the host.
+ *   alpha       optional [U] fp32 (NULL = 1);  beta  optional [U] fp32 (NULL = 0).  With alpha = 1, beta = 0 rows and mass are K17's
+ *               (weight NULL) bit for bit at the same explicit `splits`.  A NaN in a user's alpha or beta gives that user a row
+ *               of NaN (where it has a weight at all) and touches nobody else.
+ *   the other fields, the edge cases and the refusals   K17's; r_v = 0 exactly where p_v == 0 (0 * -inf is never formed)
+ *   out_mass    optional [U] fp32: sum_v p_v, K17's mass -- not the sum of r
+ * Stream and finalize are K17's (same user tiles and k-slab counts, same LDS, no scratch), the one difference the value stored to
+ * the P tile; the finalize has no weight multiply.  Bits: K17's rule.  Error bound (derived in DESIGN.md section 5):
+ *   |out_c - out*_c| <= kappa' e A_c,   A_c = sum_v p*_v (|alpha| + |beta| (|x*_v| + 1)) |news_vc|,
+ *   kappa' = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 28      (K17's kappa + 2: the fma of the weight and its product with p)
+ *   ws          nr_score_expect_affine_workspace_bytes(d): K17's size
+ * Layout: nr_expect_desc with `weight` replaced by `alpha`, then `beta`.                                                        */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 */
+  const float* base_logsum;    /* [U]: out_logsum of K13 */
+  const float* alpha;          /* optional [U]; NULL = 1 */
+  const float* beta;           /* optional [U]; NULL = 0 */
+  const int32_t* sub_ids;      /* optional [U, ld_sub]; with sub_w */
+  const float* sub_w;          /* optional [U, ld_sub]; with sub_ids */
+  int ld_sub, T;
+  int scale_inv_tau;
+  float* out;                  /* [U, ld_out] */
+  int ld_out;
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_affine_desc;
+size_t nr_score_expect_affine_workspace_bytes(const nr_expect_affine_desc* d);
+int nr_score_expect_affine(const nr_expect_affine_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +
  * the DataLoader collate, src/dataset.py:44-49, src/main.py:89-103.  Only news INDICES come from the host (once per
  * epoch); the feature rows are gathered here.

@@ -380,6 +380,91 @@ def expect_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None,
     return expect, mass
 
 
+def _log_softmax_rows(a, b, temperature, exclude, prior, stamp, window):
+    """Per user the float64 (ok mask [V], p [n_ok], x = log p [n_ok]) of the full softmax over what logz_reference calls
+    eligible, or None in place of (p, x) for a NaN user (bad temperature, a largest score of +-inf); the shared front of
+    entropy_reference and expect_affine_reference."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        scores = b @ a.T
+    scores, pool = _pooled(scores, prior, stamp, window)
+    U, V = scores.shape
+    tau, tau_ok = _temperatures(temperature, U)
+    rows = []
+    for u in range(U):
+        ok = ~np.isnan(scores[u]) & pool[u]
+        ok[0] = False
+        if exclude is not None:
+            ex = np.asarray(exclude[u], dtype=np.int64).reshape(-1)
+            ok[ex[(ex >= 1) & (ex < V)]] = False
+        s = scores[u, ok]
+        if s.size and (not tau_ok[u] or not np.isfinite(s.max())):
+            rows.append((ok, None, None))
+            continue
+        with np.errstate(divide="ignore"):
+            z = (s - s.max()) / tau[u] if s.size else s
+            x = z - np.log(np.sum(np.exp(z))) if s.size else z
+        rows.append((ok, np.exp(x), x))
+    return rows
+
+
+def entropy_reference(news, user, temperature, exclude=None, prior=None, stamp=None, window=None):
+    """Host statement of the entropy contract (include/nrhip.h, nr_score_entropy); tests check the device against it, no product
+    path calls it.
+
+    `news` [V, N], `user` [U, N]; `exclude` and the pools are logz_reference's, and so is what is eligible (through _pooled).
+    Per user, over its eligible news, in float64 with x_v = log p_v: H = -sum p x, var = sum p x^2 - (sum p x)^2 = Var_p(log p),
+    mass = sum p = 1.  A term with p == 0 (a score of -inf under a finite maximum) is 0: 0 log 0 = 0.  Nothing eligible:
+    (0, 0, 0).  A temperature that is not finite and > 0, or a largest score of +-inf: NaN for that user.
+    Returns (H, var, mass), float64 [U] each."""
+    a = np.asarray(news, dtype=np.float64)
+    b = np.asarray(user, dtype=np.float64)
+    U = b.shape[0]
+    H, var, mass = np.zeros(U), np.zeros(U), np.zeros(U)
+    for u, (ok, p, x) in enumerate(_log_softmax_rows(a, b, temperature, exclude, prior, stamp, window)):
+        if p is None:
+            H[u] = var[u] = mass[u] = np.nan
+            continue
+        xs = np.where(p > 0, x, 0.0)
+        m1 = float(np.sum(p * xs))
+        H[u], var[u], mass[u] = -m1, float(np.sum(p * xs * xs)) - m1 * m1, float(np.sum(p))
+    return H, var, mass
+
+
+def expect_affine_reference(news, user, temperature, exclude=None, prior=None, stamp=None, window=None, alpha=None, beta=None,
+                            sub_ids=None, sub_w=None, scale_inv_tau=False):
+    """Host statement of the affine expected-news-vector contract (include/nrhip.h, nr_score_expect_affine); tests check the
+    device against it, no product path calls it.
+
+    What is eligible, p and x = log p are entropy_reference's.  Per user, in float64,
+    out[u] = sum_v p_v (alpha_u + beta_u x_v) news[v] - sum_t sub_w[u, t] news[sub_ids[u, t]], times 1 / tau_u when scale_inv_tau;
+    alpha None = 1, beta None = 0; a term with p == 0 is 0; named ids outside [1, V) are fill; components of `news` that are not
+    finite count as 0.  mass[u] = sum p.  Nothing eligible: only the named rows, mass 0.  A temperature that is not finite and
+    > 0, or a largest score of +-inf: a row of NaN and mass NaN.  Returns (out float64 [U, N], mass float64 [U])."""
+    a = np.asarray(news, dtype=np.float64)
+    b = np.asarray(user, dtype=np.float64)
+    U, V = b.shape[0], a.shape[0]
+    tau, _ = _temperatures(temperature, U)
+    al = np.ones(U) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(U)
+    be = np.zeros(U) if beta is None else np.asarray(beta, dtype=np.float64).reshape(U)
+    clean = np.where(np.isfinite(a), a, 0.0)
+    out, mass = np.zeros((U, a.shape[1])), np.zeros(U)
+    for u, (ok, p, x) in enumerate(_log_softmax_rows(a, b, temperature, exclude, prior, stamp, window)):
+        if p is None:
+            out[u], mass[u] = np.nan, np.nan
+            continue
+        live = p > 0
+        r = np.where(live, p, 0.0) * (al[u] + be[u] * np.where(live, x, 0.0))
+        out[u], mass[u] = r @ clean[ok], float(np.sum(p))
+        if sub_ids is not None:
+            ids = np.asarray(sub_ids[u], dtype=np.int64).reshape(-1)
+            w = np.asarray(sub_w[u], dtype=np.float64).reshape(-1)
+            real = (ids >= 1) & (ids < V)
+            out[u] -= w[real] @ clean[ids[real]]
+        if scale_inv_tau:
+            out[u] /= tau[u]
+    return out, mass
+
+
 def softmax_matrix_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None):
     """The [U, V] float64 matrix p(v | u) of the full softmax over what logz_reference calls eligible (through _pooled), which
     the device never forms: row u sums to 1 over its eligible news and is 0 elsewhere.  A dead user -- a temperature that is not

@@ -1521,6 +1521,199 @@ def full_softmax_nll(news_vecs, user_vecs, targets, temperature, exclude=None, s
     return FullSoftmaxNLLFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
 
 
+@torch.no_grad()
+def score_entropy(news_vecs, user_vecs, temperature, base, exclude=None, splits=0, prior=None, stamp=None, window=None):
+    """The entropy of the served distribution (nr_score_entropy; include/nrhip.h, K23): per user, with
+    p(v) = exp((score_v - smax) / temperature - logsum) over exactly the news score_logz sums over,
+    entropy = -sum_v p log p, var = Var_p(log p) = sum p log^2 p - (sum p log p)^2 and mass = sum p -- without the [U, V]
+    probability matrix.  exp(entropy) is the effective number of news the user is exposed to under score_sample at this
+    temperature; var / temperature is the derivative of the entropy with respect to the temperature.
+    `base` = (logsum, smax[, count]): what score_logz returned for the SAME vectors, temperature, exclude and pools; the other
+    arguments are score_logz's.  Returns (entropy, var, mass), fp32 [U] each.  A user with nothing eligible gets (0, 0, 0); one
+    with exactly one eligible news entropy == 0 and var == 0 exactly; a bad entry of a temperature tensor, or a NaN base, gives
+    that user NaN.  `splits`: 0 = the library chooses the number of corpus slices by U.  For a fixed splits > 0 a user's results
+    do not depend, bit for bit, on the other users of the call; across different splits they agree to within the bounds of
+    DESIGN.md section 5."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, base[0], base[1])
+    V, N, U, dev = _vector_args("score_entropy", news_vecs, user_vecs)
+    ent = torch.empty(U, dtype=torch.float32, device=dev)
+    var = torch.empty(U, dtype=torch.float32, device=dev)
+    mass = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return ent, var, mass
+    bl, bm = _base_args("score_entropy", base, U, dev)
+    ex_fields, ex_keep = _exclude_args("score_entropy", exclude, U, dev, dense=False)
+    pr, st, win = _pool_args("score_entropy", V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args("score_entropy", temperature, U, dev)
+    d = _lib.EntropyDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                         ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u),
+                         base_max=ptr(bm), base_logsum=ptr(bl), out_entropy=ptr(ent), out_var=ptr(var), out_mass=ptr(mass),
+                         prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_entropy_workspace_bytes(C.byref(d)), dev)   # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_entropy(C.byref(d), _stream()), "nr_score_entropy")
+    return ent, var, mass
+
+
+def _score_expect_affine(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, alpha, beta, sub_ids, sub_w,
+                         scale_inv_tau):
+    """One nr_score_expect_affine call (include/nrhip.h, K24): (out [U, N] fp32, mass [U] fp32)."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, base[0], base[1],
+              alpha, beta, sub_ids, sub_w)
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    out = torch.empty(U, N, dtype=torch.float32, device=dev)
+    mass = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return out, mass
+    bl, bm = _base_args(what, base, U, dev)
+    coef = []
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
+                raise RuntimeError(f"{what}: {name} must be a floating point tensor of shape ({U},) on {dev}")
+            t = t.detach().to(torch.float32).contiguous()
+        coef.append(t)
+    T = 0
+    if sub_ids is not None:
+        if sub_ids.dim() != 2 or sub_ids.shape[0] != U or sub_ids.is_floating_point() or sub_w is None or tuple(sub_w.shape) != tuple(sub_ids.shape):
+            raise RuntimeError(f"{what}: the named rows must be integer ids [U = {U}, T] with weights of the same shape")
+        T = sub_ids.shape[1]
+        sub_ids = sub_ids.detach().to(torch.int32).contiguous()
+        sub_w = sub_w.detach().to(torch.float32).contiguous()
+    ex_fields, ex_keep = _exclude_args(what, exclude, U, dev, dense=False)
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    d = _lib.ExpectAffineDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                              ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits), **ex_fields, tau=tau, tau_u=ptr(tau_u),
+                              base_max=ptr(bm), base_logsum=ptr(bl), alpha=ptr(coef[0]), beta=ptr(coef[1]), sub_ids=ptr(sub_ids),
+                              sub_w=ptr(sub_w), ld_sub=T, T=T, scale_inv_tau=1 if scale_inv_tau else 0, out=ptr(out), ld_out=N,
+                              out_mass=ptr(mass), prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_affine_workspace_bytes(C.byref(d)), dev)   # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_affine(C.byref(d), _stream()), "nr_score_expect_affine")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_affine(news_vecs, user_vecs, temperature, base, exclude=None, splits=0, prior=None, stamp=None, window=None, alpha=None,
+                        beta=None, sub_ids=None, sub_w=None, scale_inv_tau=False):
+    """score_expect with a per-pair weight that is affine in log p (nr_score_expect_affine; include/nrhip.h, K24): per user
+    out = sum_v p(v) (alpha + beta log p(v)) news_vecs[v] - sum_t sub_w[t] news_vecs[sub_ids[t]], times 1 / temperature when
+    scale_inv_tau.  alpha, beta: optional floating point [U] (None = 1 and 0: score_expect's row, bit for bit at the same explicit
+    splits).  With E = score_expect's row and J = sum p log p news, alpha = -H, beta = -1, scale_inv_tau gives the gradient of the
+    entropy H with respect to the user vector, -(J + H E) / temperature.  sub_ids, sub_w: optional named rows, integer ids
+    [U, T <= 128] (0 or out of range = fill) with weights of the same shape.  The other arguments are score_expect's.
+    Returns (out fp32 [U, N], mass fp32 [U]): mass = sum_v p(v), as in score_expect.  A NaN in a user's alpha or beta gives that
+    user a row of NaN and touches nobody else."""
+    return _score_expect_affine("score_expect_affine", news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, alpha, beta,
+                                sub_ids, sub_w, scale_inv_tau)
+
+
+def _tau_users(temperature, U):
+    """A temperature tensor as the kernels take it: a 0-dim tensor becomes [U]."""
+    if isinstance(temperature, torch.Tensor) and temperature.dim() == 0:
+        return temperature.detach().to(torch.float32).expand(U).contiguous()
+    return temperature.detach() if isinstance(temperature, torch.Tensor) else temperature
+
+
+class FullSoftmaxEntropyFunction(Function):
+    """(nll [U, T], valid, entropy [U]) under the full softmax over the corpus, differentiable with respect to the user vectors and,
+    when it is a tensor that requires grad, the temperature."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, temperature, news_vecs, targets, exclude, splits, prior, stamp, window):
+        user = user_vecs.detach()
+        U = user.shape[0]
+        tau = _tau_users(temperature, U)
+        base = score_logz(news_vecs, user, tau, exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+        logp, _ = row_logprob(news_vecs, user, targets, tau, base, False, prior=prior, stamp=stamp, window=window)
+        ent, var, _ = score_entropy(news_vecs, user, tau, base, exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+        V = news_vecs.shape[0]
+        valid = (targets >= 1) & (targets < V) & ~torch.isnan(logp)
+        if isinstance(tau, torch.Tensor):
+            valid &= ((tau > 0) & torch.isfinite(tau))[:, None]
+        nll = torch.where(valid, -logp, torch.zeros_like(logp))
+        ctx.save_for_backward(user, news_vecs, targets, valid, base[0], base[1], logp, ent, var)
+        ctx.rest = (tau, exclude, splits, prior, stamp, window)
+        ctx.tau_grad = isinstance(temperature, torch.Tensor) and temperature.requires_grad
+        ctx.tau_shape = tuple(temperature.shape) if isinstance(temperature, torch.Tensor) else None
+        ctx.tau_dtype = temperature.dtype if isinstance(temperature, torch.Tensor) else None
+        ctx.mark_non_differentiable(valid, base[2])
+        ctx.set_materialize_grads(False)
+        return nll, valid, ent, base[2]
+
+    @staticmethod
+    def backward(ctx, g, _gvalid, h, _gcount):
+        user, news_vecs, targets, valid, bl, bm, logp, ent, var = ctx.saved_tensors
+        tau, exclude, splits, prior, stamp, window = ctx.rest
+        if g is None and h is None:
+            return (None,) * 9
+        dev, U = user.device, user.shape[0]
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        gw = torch.where(valid, g.to(torch.float64), zero) if g is not None else torch.zeros(valid.shape, dtype=torch.float64, device=dev)
+        # the entropy of a user the forward answers with NaN (bad temperature, NaN base) has no gradient: exactly 0, not 0 * NaN
+        hw = torch.where(torch.isnan(ent), zero, h.to(torch.float64)) if h is not None else torch.zeros(U, dtype=torch.float64, device=dev)
+        H = torch.where(torch.isnan(ent), zero, ent.to(torch.float64))
+        grad_user = grad_tau = None
+        with torch.no_grad():
+            if ctx.needs_input_grad[0] and h is None:
+                # no entropy gradient arrived: full_softmax_nll's backward, call for call, so its bits
+                gw32 = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=dev))
+                grad_user, _ = _score_expect("full_softmax_nll_entropy", news_vecs, user, tau, (bl, bm), exclude, splits, prior, stamp, window,
+                                             gw32.sum(dim=1), targets, gw32, True)
+                grad_user = torch.where(valid.any(dim=1)[:, None], grad_user, torch.zeros_like(grad_user))
+            elif ctx.needs_input_grad[0]:
+                alpha = (gw.sum(dim=1) - hw * H).to(torch.float32)
+                grad_user, _ = _score_expect_affine("full_softmax_nll_entropy", news_vecs, user, tau, (bl, bm), exclude, splits, prior, stamp, window,
+                                                    alpha, (-hw).to(torch.float32), targets, gw.to(torch.float32), True)
+                # a user with neither a valid target nor an entropy gradient gets exactly 0
+                grad_user = torch.where((valid.any(dim=1) | (hw != 0))[:, None], grad_user, torch.zeros_like(grad_user))
+            if ctx.tau_grad:
+                # d nll_t / d tau = (logp_t - m1) / tau, d H / d tau = var / tau, m1 = -H: [U] elementwise work in fp64
+                tau64 = (tau if isinstance(tau, torch.Tensor) else torch.full((U,), float(tau), device=dev)).to(torch.float64)
+                good = (tau64 > 0) & torch.isfinite(tau64)
+                lp = torch.where(valid, logp.to(torch.float64), zero)
+                dnll = (gw * (lp + torch.where(valid, H[:, None], zero))).sum(dim=1)
+                dent = hw * torch.where(torch.isnan(var), zero, var.to(torch.float64))
+                per_user = torch.where(good, (dnll + dent) / torch.where(good, tau64, torch.ones_like(tau64)), zero)
+                grad_tau = (per_user.sum() if ctx.tau_shape == () else per_user).to(ctx.tau_dtype)
+        return (grad_user, grad_tau) + (None,) * 7
+
+
+def full_softmax_nll_entropy(news_vecs, user_vecs, targets, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None,
+                             return_count=False):
+    """full_softmax_nll with the entropy of the served distribution as a third, differentiable result, and a gradient for the
+    temperature.  Returns (nll fp32 [U, T], valid bool [U, T], entropy fp32 [U]): nll and valid are full_softmax_nll's, bit for
+    bit; entropy = -sum_v p(v) log p(v) over exactly the news of the softmax (score_entropy; include/nrhip.h, K23): 0 for a user
+    with nothing eligible, NaN for a user whose temperature is not finite and > 0.
+    Forward: score_logz, row_logprob(sequential=False), score_entropy.  Backward: ONE nr_score_expect_affine call on the saved base
+    (K24): for upstream gradients g [U, T] of nll and h [U] of entropy,
+    grad_user = ((sum_t g_t - h H) E - h J - sum_t g_t news[target_t]) / temperature over the valid entries; a user with neither a
+    valid target nor an entropy gradient gets exactly 0.  When the entropy is in no loss (no h arrives) the one call is
+    full_softmax_nll's nr_score_expect call instead, so the gradient then has full_softmax_nll's bits.
+    return_count=True appends score_logz's count (int32 [U], the eligible news per user) as a fourth result.
+    `temperature`: a float, or a floating point tensor, 0-dim or [U].  A tensor that requires grad (an nn.Parameter, say) gets
+    d nll_t / d tau = (logp_t + H) / tau and d H / d tau = Var_p(log p) / tau from the saved forward results, [U] elementwise work
+    in fp64; a 0-dim tensor gets the sum over the users.  Users whose temperature is not finite and > 0 contribute 0.
+    `news_vecs` is a frozen table: one that requires grad is refused.  Prior and the other arguments get no gradient."""
+    if news_vecs.requires_grad:
+        raise RuntimeError("full_softmax_nll_entropy: news_vecs requires grad, but the table is frozen here: its gradient P^T . users is a "
+                           "[V, N] reduction over every user of the call and is not part of this call (detach the table)")
+    if targets.dim() != 2 or targets.shape[0] != user_vecs.shape[0] or targets.is_floating_point():
+        raise RuntimeError(f"full_softmax_nll_entropy: targets must be an integer tensor [U = {user_vecs.shape[0]}, T], got {tuple(targets.shape)} "
+                           f"{targets.dtype}")
+    if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"full_softmax_nll_entropy: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
+    if isinstance(temperature, torch.Tensor) and (temperature.dim() > 1 or not temperature.is_floating_point()
+                                                  or (temperature.dim() == 1 and temperature.shape[0] != user_vecs.shape[0])):
+        raise RuntimeError(f"full_softmax_nll_entropy: a temperature tensor must be floating point, 0-dim or of shape ({user_vecs.shape[0]},), got "
+                           f"{tuple(temperature.shape)} {temperature.dtype}")
+    nll, valid, ent, count = FullSoftmaxEntropyFunction.apply(user_vecs, temperature, news_vecs, targets, exclude, splits, prior, stamp, window)
+    return (nll, valid, ent, count) if return_count else (nll, valid, ent)
+
+
 def _score_expect_news(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, named, scale_inv_tau, rows):
     """One nr_score_expect_news call (include/nrhip.h, K18): (out [V, N] fp32 or None, mass [V] fp32).  named: None or (offsets
     int32 [V + 1], users int32 [n], w fp32 [n]) on the device."""

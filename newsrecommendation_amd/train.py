@@ -603,6 +603,84 @@ def full_softmax_loss(model, news_vecs, hist_idx, mask, targets, temperature, ex
     return total / n.clamp(min=1).to(torch.float32), n
 
 
+@torch.no_grad()
+def policy_entropy(model, news_vecs, hist_idx, mask, temperature, exclude_history=True, batch_size=8192, prior=None, news_time=None, window=None,
+                   seen=None):
+    """The entropy of the distribution recommend_sample serves at `temperature`: per user H = -sum_v p(v) log p(v) over exactly the
+    news log_partition sums over under the same arguments (ops.score_logz, then ops.score_entropy; include/nrhip.h, K13 and K23),
+    and var = Var_p(log p).  exp(H) is the effective number of news a user is exposed to -- the exploration dial of
+    recommend_sample -- and var / temperature is dH / dtemperature, which is what a search for the temperature that gives a wanted
+    entropy needs.  No [U, V] matrix is formed.  The arguments are log_partition's.
+    Returns (entropy fp32 [U], var fp32 [U]) on the device: (0, 0) for a user with nothing or exactly one news eligible, NaN for a
+    temperature that is not finite and > 0."""
+    news_vecs, user, exclude, kw, _ = _recommend_args(model, news_vecs, hist_idx, mask, exclude_history, batch_size, prior, news_time, window,
+                                                      None, None, seen)
+    tau = _device_temperature(temperature, user.shape[0], news_vecs.device)
+    base = ops.score_logz(news_vecs, user, tau, exclude=exclude, **kw)
+    ent, var, _ = ops.score_entropy(news_vecs, user, tau, base, exclude=exclude, **kw)
+    return ent, var
+
+
+def full_softmax_loss_entropy(model, news_vecs, hist_idx, mask, targets, temperature, entropy_weight, exclude_history=True, batch_size=8192,
+                              prior=None, news_time=None, window=None, seen=None):
+    """full_softmax_loss with an entropy bonus and a temperature that may be learned:
+    loss = full_softmax_loss's loss - entropy_weight * mean_entropy, mean_entropy the mean of H_u = -sum_v p(v | u) log p(v | u)
+    over the users with anything eligible (and a temperature that is finite and > 0), the softmax the one the loss is taken over.
+    The bonus keeps a policy trained from logged rows from collapsing onto a few news.  The arguments, the
+    chunking into batch_size users and the valid-entry rules are full_softmax_loss's; forward and backward are fused passes
+    (ops.full_softmax_nll_entropy; include/nrhip.h, K13, K14, K23, K24).
+    temperature: a float, or a floating point tensor, 0-dim or [U] -- an nn.Parameter gets its gradient (of the loss term and of
+    the bonus).  entropy_weight: a float; 0 leaves the entropy out of the graph, and loss and its gradients are then
+    full_softmax_loss's, bit for bit.
+    Returns (loss, n, mean_entropy): loss and n as in full_softmax_loss, mean_entropy a detached 0-dim fp32 tensor."""
+    device = news_vecs.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    news_vecs = news_vecs.detach().float().contiguous()
+    U, V = hist.shape[0], news_vecs.shape[0]
+    tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
+    if tg.dim() != 2 or tg.shape[0] != U:
+        raise RuntimeError(f"full_softmax_loss_entropy: targets must be [U = {U}, T], got {tuple(tg.shape)}")
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    tg = tg.masked_fill(_not_ranked(exclude, tg, V), 0)       # what target_logprob does not score is named as fill: it is in no sum
+    if tg.shape[1] == 0:
+        tg = torch.zeros(U, 1, dtype=torch.int32, device=device)     # no targets at all: one column of fill carries the entropy
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    W = _lib.NR_TOPK_MAX_K
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    ent_total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    n_ent = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.embed_gather(news_vecs, hist[a:b], code), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) and tau.dim() == 1 else tau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        for c in range(0, tg.shape[1], W):
+            nll, valid, ent, count = ops.full_softmax_nll_entropy(news_vecs, user, tg[a:b, c:c + W].contiguous(), tau_b, exclude=ex_b,
+                                                                  return_count=True, **kw_b)
+            if c == 0:                                        # a user's entropy is counted once: with its first block of targets
+                counted = (count > 0) & ~torch.isnan(ent)
+                ent_total = ent_total + torch.where(counted, ent, torch.zeros_like(ent)).sum()
+                n_ent = n_ent + counted.sum()
+            total = total + nll.sum()
+            n = n + valid.sum()
+    loss = total / n.clamp(min=1).to(torch.float32)
+    mean_entropy = ent_total / n_ent.clamp(min=1).to(torch.float32)
+    if float(entropy_weight) != 0.0:
+        loss = loss - float(entropy_weight) * mean_entropy
+    return loss, n, mean_entropy.detach()
+
+
 def full_softmax_loss_joint(model, news_table, hist_idx, mask, targets, temperature, exclude_history=True, batch_size=8192, prior=None,
                             news_time=None, window=None, seen=None):
     """full_softmax_loss with a news-vector table that may require grad: the same loss, the same valid entries, the same
