@@ -54,7 +54,7 @@ int nr_last_error(char* buf, size_t n);
  * configuration; the environment variable NR_<NAME> presets an option once per process.  nr_get_option returns
  * -1 for an unknown name.  Not thread-synchronised with calls in flight: set options between calls.              */
 /* sizeof of the descriptor structs as this library was compiled: out[0..3] = nr_mhsa_desc, nr_conv_desc, nr_pool_desc,
- * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc, with n >= 20 out[18..19] = nr_expect_groups_desc, nr_logprob_capped_grad_desc, with n >= 21 out[20] = nr_expect_news_groups_desc.  A binding compares them with its own layout at
+ * nr_linear_desc, with n >= 6 also out[4..5] = nr_cast_job, nr_pack_job, with n >= 7 out[6] = nr_adam_rows_desc, with n >= 8 out[7] = nr_topk_desc, with n >= 9 out[8] = nr_rank_desc, with n >= 10 out[9] = nr_mmr_desc, with n >= 11 out[10] = nr_sample_desc, with n >= 12 out[11] = nr_logz_desc, with n >= 13 out[12] = nr_logprob_desc, with n >= 14 out[13] = nr_logz_groups_desc, with n >= 15 out[14] = nr_logprob_capped_desc, with n >= 16 out[15] = nr_expect_desc, with n >= 17 out[16] = nr_expect_news_desc, with n >= 18 out[17] = nr_logprob_grad_desc, with n >= 20 out[18..19] = nr_expect_groups_desc, nr_logprob_capped_grad_desc, with n >= 21 out[20] = nr_expect_news_groups_desc, with n >= 23 out[21..22] = nr_entropy_desc, nr_expect_affine_desc, with n >= 24 out[23] = nr_expect_news_affine_desc.  A binding compares them with its own layout at
  * load time (ABI drift -> refuse to run).                                                                              */
 int nr_abi_sizes(size_t* out, int n);
 /* Deterministic mode.  Outputs that several workgroups add into (dW, db, dtable, dpad) are accumulated with fp32 atomics
@@ -1489,6 +1489,72 @@ typedef struct {
 } nr_expect_affine_desc;
 size_t nr_score_expect_affine_workspace_bytes(const nr_expect_affine_desc* d);
 int nr_score_expect_affine(const nr_expect_affine_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K25  K18 with a per-pair weight that is affine in log p: the news side of K24.  For
+ *   L = sum_u (sum_t g_ut nll(u, t) + h_u H_u),   x_uv = log p(v | u),   alpha_u = sum_t g_ut - h_u H_u,   beta_u = -h_u
+ *   d L / d news_v = sum_u (1 / tau_u) p(v | u) (alpha_u + beta_u x_uv) user_u - sum_{(u, t): target = v} (g_ut / tau_u) user_u
+ * (d nll_t / d z_v = p_v - delta_vt, d H / d z_v = -p_v (x_v + H), z = s / tau) over exactly the pairs (u, v) that are terms of
+ * K13's sums.  One contraction,
+ *   out[v] = sum_u r_uv user_u - sum_j named_w[j] (* 1 / tau_user) user[named_user[j]],   r_uv = p_uv fmaf(b_u, x_uv, a_u),
+ *   a_u = alpha_u (* fl(1 / tau_u) if scale_inv_tau),  b_u = beta_u (likewise),
+ * so K24's alpha and beta, named terms (target, g) and scale_inv_tau give that gradient in one call, without the [U, V] matrix.
+ * metrics.expect_news_affine_reference states the contract on the host.
+ *   alpha       optional [U] fp32 (NULL = 1);  beta  optional [U] fp32 (NULL = 0).  With alpha = w (finite, and finite times
+ *               1 / tau) and beta = NULL, rows are K18's with weight = w bit for bit at the same explicit `splits`
+ *               (fmaf(0, x, a) == a).  A user whose a or b is NaN or infinite contributes to NO row through the stream and puts
+ *               no NaN into the table (K22's choice for its bin weights: one user's NaN would otherwise reach every news).
+ *   named_offsets, named_user, named_w, n_named   K18's named terms; gated by K18's rule (a live user, named_w != 0) alone,
+ *               not by alpha or beta
+ *   out         [V, ld_out] fp32, required: there is no mass-only mode (nr_score_expect_news with out = NULL is that)
+ *   out_mass    optional [V] fp32: sum_u p(v | u) over the live users, K18's mass with weight = NULL bit for bit -- not the sum
+ *               of r
+ *   the other fields and the edge cases   K18's; r_uv = 0 exactly where p_uv == 0 (0 * -inf is never formed)
+ * Stream and finalize are K18's rows mode (same news tiles and k-slab counts, same plan of the user axis, same LDS, no
+ * scratch), the one difference the value stored to the P tile.  Bits: K18's rule -- for a fixed explicit `splits`, row v's
+ * bits depend on that row's own inputs, on the users, on U and on `splits`, not on any other news row, nor on the row's place
+ * in the table or the tile.  Error bound (derived in DESIGN.md section 5) against the exact result of the fp32 inputs:
+ *   |out_vc - out*_vc| <= kappa'' 2^-24 A_vc,
+ *   A_vc = sum_u (1 / tau_u) (|alpha_u| + |beta_u| (|x*_uv| + 1)) p*_uv |user_uc| + sum_j |d_j| |user_jc|,
+ *   kappa'' = 2 (N + 1) G + 6 C + 5 ln n + 7 K + L + 31      (K18's kappa + 2: the fma of the weight, and second order; the
+ *               + 1 beside |x*| carries the absolute error of x through beta)
+ *   |mass_v - mass*_v|   K18's bound with weight = 1
+ *   ws          nr_score_expect_news_affine_workspace_bytes(d): K18's rows-mode size, V * slices * (N * 4 + 8) rounded to 8
+ * Refused before any launch: what K18 refuses, read onto this descriptor; a null out.
+ * Layout: nr_expect_news_desc with `weight` replaced by `alpha`, then `beta`.                                                  */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [V + 1]: by news */
+  const int32_t* excl_users;   /* optional [n_excl]: ascending user indices per news */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 */
+  const float* base_logsum;    /* [U]: out_logsum of K13 */
+  const float* alpha;          /* optional [U]; NULL = 1 */
+  const float* beta;           /* optional [U]; NULL = 0 */
+  int scale_inv_tau;
+  const int32_t* named_offsets; /* optional [V + 1]; with named_user and named_w */
+  const int32_t* named_user;    /* optional [n_named] */
+  const float* named_w;         /* optional [n_named] */
+  int n_named;
+  float* out;                  /* [V, ld_out] */
+  int ld_out;
+  float* out_mass;             /* [V] or NULL */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_news_affine_desc;
+size_t nr_score_expect_news_affine_workspace_bytes(const nr_expect_news_affine_desc* d);
+int nr_score_expect_news_affine(const nr_expect_news_affine_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +

@@ -527,6 +527,44 @@ def expect_news_reference(a, b, *, temperature, exclude=None, prior=None, stamp=
     return out, mass
 
 
+def expect_news_affine_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None, alpha=None, beta=None, named=None,
+                                 scale_inv_tau=False):
+    """Host statement of the news side of the entropy-regularised full-softmax gradient (include/nrhip.h,
+    nr_score_expect_news_affine); tests check the device against it, no product path calls it.  float64 throughout.
+
+    expect_news_reference with the per-pair weight affine in x = log p(v | u): with a_u = alpha_u, b_u = beta_u (each / tau_u if
+    scale_inv_tau; alpha None = 1, beta None = 0),
+      out[v]  = sum_u p(v | u) (a_u + b_u x_uv) b[u]  -  sum_j named_w[j] (/ tau_user if scale_inv_tau) b[named_user[j]]
+      mass[v] = sum_u p(v | u)                                            (over the live users; not the sum of the weights)
+    A pair with p == 0 is a term of no sum (0 log 0 = 0).  A user whose alpha or beta is not finite contributes nothing through
+    the sum; its named terms stay (they are gated by the user being live and w != 0 only), and so does its share of the mass.
+    The dead users, the named terms, the cleaning of `b` and rows nobody can be shown are expect_news_reference's.
+    Returns (out float64 [V, N], mass float64 [V])."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    p, live = softmax_matrix_reference(a, b, temperature=temperature, exclude=exclude, prior=prior, stamp=stamp, window=window)
+    U, V = p.shape
+    tau, _ = _temperatures(temperature, U)
+    al = np.ones(U) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(U)
+    be = np.zeros(U) if beta is None else np.asarray(beta, dtype=np.float64).reshape(U)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        it = np.where(live, 1.0 / tau, 0.0) if scale_inv_tau else np.where(live, 1.0, 0.0)
+        fin = live & np.isfinite(al * it) & np.isfinite(be * it)
+        ca, cb = np.where(fin, al * it, 0.0), np.where(fin, be * it, 0.0)
+        x = np.where(p > 0, np.log(np.where(p > 0, p, 1.0)), 0.0)
+    clean = np.where(np.isfinite(b), b, 0.0)
+    out = (p * (ca[:, None] + cb[:, None] * x)).T @ clean
+    mass = p.T @ np.where(live, 1.0, 0.0)
+    if named is not None:
+        off, nu, nw = (np.asarray(t) for t in named)
+        for v in range(V):
+            for j in range(int(off[v]), int(off[v + 1])):
+                u = int(nu[j])
+                if nw[j] != 0 and 0 <= u < U and live[u]:
+                    out[v] -= float(nw[j]) * it[u] * clean[u]
+    return out, mass
+
+
 def row_logprob_reference(a, b=None, *, row_ids, temperature, base, sequential, prior=None, stamp=None, window=None):
     """Host statement of the row log-probability contract (include/nrhip.h, nr_row_logprob); tests check the device against it,
     no product path calls it.

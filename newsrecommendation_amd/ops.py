@@ -1697,10 +1697,12 @@ def full_softmax_nll_entropy(news_vecs, user_vecs, targets, temperature, exclude
     `temperature`: a float, or a floating point tensor, 0-dim or [U].  A tensor that requires grad (an nn.Parameter, say) gets
     d nll_t / d tau = (logp_t + H) / tau and d H / d tau = Var_p(log p) / tau from the saved forward results, [U] elementwise work
     in fp64; a 0-dim tensor gets the sum over the users.  Users whose temperature is not finite and > 0 contribute 0.
-    `news_vecs` is a frozen table: one that requires grad is refused.  Prior and the other arguments get no gradient."""
+    `news_vecs` is a frozen table: one that requires grad is refused (full_softmax_nll_entropy_joint trains it).  Prior and the other
+    arguments get no gradient."""
     if news_vecs.requires_grad:
         raise RuntimeError("full_softmax_nll_entropy: news_vecs requires grad, but the table is frozen here: its gradient P^T . users is a "
-                           "[V, N] reduction over every user of the call and is not part of this call (detach the table)")
+                           "[V, N] reduction over every user of the call and is not part of this call (detach the table, or use "
+                           "full_softmax_nll_entropy_joint, which has that pass)")
     if targets.dim() != 2 or targets.shape[0] != user_vecs.shape[0] or targets.is_floating_point():
         raise RuntimeError(f"full_softmax_nll_entropy: targets must be an integer tensor [U = {user_vecs.shape[0]}, T], got {tuple(targets.shape)} "
                            f"{targets.dtype}")
@@ -1850,6 +1852,140 @@ def full_softmax_nll_joint(news_vecs, user_vecs, targets, temperature, exclude=N
     if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
         raise RuntimeError(f"full_softmax_nll_joint: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
     return FullSoftmaxNLLJointFunction.apply(user_vecs, news_vecs, targets, temperature, exclude, splits, prior, stamp, window)
+
+
+def _score_expect_news_affine(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, alpha, beta, named,
+                              scale_inv_tau):
+    """One nr_score_expect_news_affine call (include/nrhip.h, K25): (out [V, N] fp32, mass [V] fp32).  _score_expect_news with the
+    two coefficient arrays in place of the weight; named: None or (offsets int32 [V + 1], users int32 [n], w fp32 [n]) on the device."""
+    tau_t = temperature if isinstance(temperature, torch.Tensor) else None
+    _need_gpu(news_vecs, user_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window, tau_t, base[0], base[1],
+              alpha, beta, *(named or ()))
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    if U == 0:                                                 # nobody: zeros, nothing to launch
+        return torch.zeros(V, N, dtype=torch.float32, device=dev), torch.zeros(V, dtype=torch.float32, device=dev)
+    out = torch.empty(V, N, dtype=torch.float32, device=dev)  # the finalize writes every row
+    mass = torch.empty(V, dtype=torch.float32, device=dev)
+    bl, bm = _base_args(what, base, U, dev)
+    coef = []
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
+                raise RuntimeError(f"{what}: {name} must be a floating point tensor of shape ({U},) on {dev}")
+            t = t.detach().to(torch.float32).contiguous()
+        coef.append(t)
+    if exclude is not None and not isinstance(exclude, ExclusionLists):
+        if not isinstance(exclude, torch.Tensor) or exclude.dim() != 2 or exclude.shape[0] != U:
+            raise RuntimeError(f"{what}: exclude must be a tensor [U = {U}, E] or an ExclusionLists")
+        exclude = ExclusionLists(exclude)
+    ex_off = ex_users = None
+    if exclude is not None:
+        if exclude.U != U or exclude.device != dev:
+            raise RuntimeError(f"{what}: the exclusion lists are for {exclude.U} users on {exclude.device}, the call has {U} on {dev}")
+        ex_off, ex_users = exclude.by_news(V)
+    n_excl = 0 if ex_users is None else ex_users.numel()
+    n_off = n_user = n_w = None
+    if named is not None:
+        n_off, n_user, n_w = named
+        if tuple(n_off.shape) != (V + 1,) or n_user.dim() != 1 or tuple(n_w.shape) != tuple(n_user.shape):
+            raise RuntimeError(f"{what}: the named terms must be offsets [V + 1 = {V + 1}] with users and weights of one length")
+        n_off, n_user, n_w = n_off.to(torch.int32).contiguous(), n_user.to(torch.int32).contiguous(), n_w.detach().to(torch.float32).contiguous()
+        if n_user.numel() == 0:
+            n_off = n_user = n_w = None
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    d = _lib.ExpectNewsAffineDesc(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                                  ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, splits=int(splits),
+                                  excl_offsets=ptr(ex_off) if n_excl else None, excl_users=ptr(ex_users) if n_excl else None, n_excl=n_excl,
+                                  tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm), base_logsum=ptr(bl), alpha=ptr(coef[0]), beta=ptr(coef[1]),
+                                  scale_inv_tau=1 if scale_inv_tau else 0, named_offsets=ptr(n_off), named_user=ptr(n_user), named_w=ptr(n_w),
+                                  n_named=0 if n_user is None else n_user.numel(), out=ptr(out), ld_out=N, out_mass=ptr(mass),
+                                  prior=ptr(pr), stamp=ptr(st), window=ptr(win), ld_window=2 if win is not None else 0)
+    ws = _ws(_lib.lib().nr_score_expect_news_affine_workspace_bytes(C.byref(d)), dev)   # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_news_affine(C.byref(d), _stream()), "nr_score_expect_news_affine")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_news_affine(news_vecs, user_vecs, temperature, base, exclude=None, splits=0, prior=None, stamp=None, window=None, alpha=None,
+                             beta=None):
+    """score_expect_news with a per-pair weight that is affine in log p (nr_score_expect_news_affine; include/nrhip.h, K25): per news
+    out[v] = sum_u p(v | u) (alpha_u + beta_u log p(v | u)) user_vecs[u], over exactly the pairs score_logz sums over, without the
+    [U, V] probability matrix.  alpha, beta: optional floating point [U] (None = 1 and 0); with beta None the rows are
+    score_expect_news's with weight = alpha, bit for bit at the same explicit splits.  alpha = -H_u, beta = -1 gives the gradient of
+    sum_u temperature H_u with respect to the news vector.  The other arguments are score_expect_news's.
+    Returns (out fp32 [V, N], mass fp32 [V]): mass[v] = sum_u p(v | u) over the live users, score_expect_news's mass without a
+    weight -- not the sum of the affine weights.  A user whose alpha or beta is NaN or infinite contributes to no row (and puts
+    no NaN into the table); the dead users are score_expect_news's.  There is no mass-only mode: score_expect_news(rows=False)
+    is that."""
+    return _score_expect_news_affine("score_expect_news_affine", news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window,
+                                     alpha, beta, None, False)
+
+
+class FullSoftmaxEntropyJointFunction(Function):
+    """FullSoftmaxEntropyFunction, differentiable with respect to the news-vector table as well: (nll [U, T], valid, entropy [U],
+    count).  The forward, grad_user and grad_tau are that function's own code on the detached table; grad_news is one K25 call, or
+    one K18 call when no entropy gradient arrived."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, temperature, news_vecs, targets, exclude, splits, prior, stamp, window):
+        return FullSoftmaxEntropyFunction.forward(ctx, user_vecs, temperature, news_vecs.detach(), targets, exclude, splits, prior, stamp, window)
+
+    @staticmethod
+    def backward(ctx, g, _gvalid, h, _gcount):
+        if g is None and h is None:
+            return (None,) * 9
+        # the user vectors and the temperature: needs_input_grad[0] and ctx.tau_grad decide there what is launched
+        grad_user, grad_tau = FullSoftmaxEntropyFunction.backward(ctx, g, _gvalid, h, _gcount)[:2]
+        grad_news = None
+        if ctx.needs_input_grad[2]:
+            user, news, targets, valid, bl, bm, logp, ent, var = ctx.saved_tensors
+            tau, exclude, splits, prior, stamp, window = ctx.rest
+            dev, U, V = user.device, user.shape[0], news.shape[0]
+            with torch.no_grad():
+                # K18 / K25 take the user slices by their own plan: `splits` is K13's / K24's cut of the news axis and does not apply
+                if h is None:
+                    # no entropy gradient arrived: full_softmax_nll_joint's K18 call, so its bits
+                    gw32 = torch.where(valid, g.to(torch.float32), torch.zeros((), dtype=torch.float32, device=dev))
+                    grad_news, _ = _score_expect_news("full_softmax_nll_entropy_joint", news, user, tau, (bl, bm), exclude, 0, prior, stamp, window,
+                                                      gw32.sum(dim=1), _named_by_news(targets, gw32, V), True, True)
+                else:
+                    # the alpha and beta FullSoftmaxEntropyFunction.backward gives K24, formed the same way
+                    zero = torch.zeros((), dtype=torch.float64, device=dev)
+                    gw = torch.where(valid, g.to(torch.float64), zero) if g is not None else torch.zeros(valid.shape, dtype=torch.float64, device=dev)
+                    hw = torch.where(torch.isnan(ent), zero, h.to(torch.float64))
+                    H = torch.where(torch.isnan(ent), zero, ent.to(torch.float64))
+                    alpha = (gw.sum(dim=1) - hw * H).to(torch.float32)
+                    grad_news, _ = _score_expect_news_affine("full_softmax_nll_entropy_joint", news, user, tau, (bl, bm), exclude, 0, prior, stamp,
+                                                             window, alpha, (-hw).to(torch.float32),
+                                                             _named_by_news(targets, gw.to(torch.float32), V), True)
+        return (grad_user, grad_tau, grad_news) + (None,) * 6
+
+
+def full_softmax_nll_entropy_joint(news_vecs, user_vecs, targets, temperature, exclude=None, splits=0, prior=None, stamp=None, window=None,
+                                   return_count=False):
+    """full_softmax_nll_entropy, differentiable with respect to `user_vecs`, the temperature AND the table `news_vecs`: any of them
+    may require grad.  The forward is full_softmax_nll_entropy's (score_logz, row_logprob(sequential=False), score_entropy), bit
+    for bit, and returns (nll fp32 [U, T], valid bool [U, T], entropy fp32 [U]) as it does (return_count=True appends the count);
+    grad_user and the temperature's gradient are its own, call for call.  grad_news [V, N] is ONE nr_score_expect_news_affine call
+    (include/nrhip.h, K25) on the saved base with the alpha = sum_t g_t - h H and beta = -h that go to K24, the 1 / temperature
+    scale inside, and the valid targets as its named terms:
+      grad_news[v] = sum_u p(v | u) (alpha_u + beta_u log p(v | u)) / tau_u user_u  -  sum_{(u, t): target = v} g_ut / tau_u user_u.
+    When the entropy is in no loss (no h arrives) it is full_softmax_nll_joint's nr_score_expect_news call instead, so the gradient
+    then has that function's bits.  News that are eligible for nobody and named by nobody get an exactly zero row; row 0 always.
+    A pass whose input does not require grad is not launched.  Prior and the other arguments get no gradient."""
+    if targets.dim() != 2 or targets.shape[0] != user_vecs.shape[0] or targets.is_floating_point():
+        raise RuntimeError(f"full_softmax_nll_entropy_joint: targets must be an integer tensor [U = {user_vecs.shape[0]}, T], got "
+                           f"{tuple(targets.shape)} {targets.dtype}")
+    if targets.shape[1] < 1 or targets.shape[1] > _lib.NR_TOPK_MAX_K:
+        raise RuntimeError(f"full_softmax_nll_entropy_joint: T = {targets.shape[1]} targets per user, must be in [1, {_lib.NR_TOPK_MAX_K}]")
+    if isinstance(temperature, torch.Tensor) and (temperature.dim() > 1 or not temperature.is_floating_point()
+                                                  or (temperature.dim() == 1 and temperature.shape[0] != user_vecs.shape[0])):
+        raise RuntimeError(f"full_softmax_nll_entropy_joint: a temperature tensor must be floating point, 0-dim or of shape "
+                           f"({user_vecs.shape[0]},), got {tuple(temperature.shape)} {temperature.dtype}")
+    nll, valid, ent, count = FullSoftmaxEntropyJointFunction.apply(user_vecs, temperature, news_vecs, targets, exclude, splits, prior, stamp, window)
+    return (nll, valid, ent, count) if return_count else (nll, valid, ent)
 
 
 @torch.no_grad()

@@ -633,14 +633,40 @@ def full_softmax_loss_entropy(model, news_vecs, hist_idx, mask, targets, tempera
     the bonus).  entropy_weight: a float; 0 leaves the entropy out of the graph, and loss and its gradients are then
     full_softmax_loss's, bit for bit.
     Returns (loss, n, mean_entropy): loss and n as in full_softmax_loss, mean_entropy a detached 0-dim fp32 tensor."""
+    return _full_softmax_loss_entropy("full_softmax_loss_entropy", False, model, news_vecs, hist_idx, mask, targets, temperature, entropy_weight,
+                                      exclude_history, batch_size, prior, news_time, window, seen)
+
+
+def full_softmax_loss_entropy_joint(model, news_table, hist_idx, mask, targets, temperature, entropy_weight, exclude_history=True, batch_size=8192,
+                                    prior=None, news_time=None, window=None, seen=None):
+    """full_softmax_loss_entropy with a news-vector table that may require grad: the same loss, the same valid entries, the same
+    (loss, n, mean_entropy), and a gradient for `news_table` ([V, news_dim] fp32 on the GPU: a table that is fine-tuned directly, or
+    the output of the news encoder) as well as for the user encoder and a temperature that requires grad -- the entropy bonus and
+    the learnable temperature while the news side trains.  Built from full_softmax_loss_entropy the way full_softmax_loss_joint is
+    built from full_softmax_loss: the table is not detached, the clicked histories are gathered with ops.news_gather (its backward
+    is a scatter-add with fp32 atomics: the last bits of the table gradient depend on the arrival order), and the softmax is
+    ops.full_softmax_nll_entropy_joint: one nr_score_expect_news_affine call per chunk of users whose entropy is in the loss
+    (include/nrhip.h, K25), one nr_score_expect_news call (K18) per chunk otherwise.  entropy_weight = 0 leaves the entropy out of
+    the graph: loss and gradients are then full_softmax_loss_joint's.  A table that does not require grad gives
+    full_softmax_loss_entropy's gradients; the news pass is then not launched."""
+    return _full_softmax_loss_entropy("full_softmax_loss_entropy_joint", True, model, news_table, hist_idx, mask, targets, temperature,
+                                      entropy_weight, exclude_history, batch_size, prior, news_time, window, seen)
+
+
+def _full_softmax_loss_entropy(what, joint, model, news_vecs, hist_idx, mask, targets, temperature, entropy_weight, exclude_history, batch_size,
+                               prior, news_time, window, seen):
+    """The body of full_softmax_loss_entropy (joint False: the table detached, ops.embed_gather, ops.full_softmax_nll_entropy) and
+    of full_softmax_loss_entropy_joint (joint True: the table as it is, ops.news_gather, ops.full_softmax_nll_entropy_joint)."""
     device = news_vecs.device
     hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
     m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
-    news_vecs = news_vecs.detach().float().contiguous()
+    # joint: no detach -- float() and contiguous() are the identity for a contiguous fp32 table
+    news_vecs = news_vecs.float().contiguous() if joint else news_vecs.detach().float().contiguous()
+    gather, nll_entropy = (ops.news_gather, ops.full_softmax_nll_entropy_joint) if joint else (ops.embed_gather, ops.full_softmax_nll_entropy)
     U, V = hist.shape[0], news_vecs.shape[0]
     tg = torch.as_tensor(targets).to(device=device, dtype=torch.int32)
     if tg.dim() != 2 or tg.shape[0] != U:
-        raise RuntimeError(f"full_softmax_loss_entropy: targets must be [U = {U}, T], got {tuple(tg.shape)}")
+        raise RuntimeError(f"{what}: targets must be [U = {U}, T], got {tuple(tg.shape)}")
     exclude = _exclusions(hist, m, exclude_history, seen, device)
     kw = _pool_kwargs(device, prior, news_time, window)
     tau = _device_temperature(temperature, U, device)
@@ -657,7 +683,7 @@ def full_softmax_loss_entropy(model, news_vecs, hist_idx, mask, targets, tempera
     step = max(int(batch_size), 1)
     for a in range(0, U, step):
         b = min(U, a + step)
-        user = model.user_encoder(ops.embed_gather(news_vecs, hist[a:b], code), m[a:b]).float().contiguous()
+        user = model.user_encoder(gather(news_vecs, hist[a:b], code), m[a:b]).float().contiguous()
         kw_b = dict(kw)
         if "window" in kw_b:
             kw_b["window"] = kw_b["window"][a:b].contiguous()
@@ -666,8 +692,7 @@ def full_softmax_loss_entropy(model, news_vecs, hist_idx, mask, targets, tempera
         if exclude is not None and (a, b) != (0, U):
             ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
         for c in range(0, tg.shape[1], W):
-            nll, valid, ent, count = ops.full_softmax_nll_entropy(news_vecs, user, tg[a:b, c:c + W].contiguous(), tau_b, exclude=ex_b,
-                                                                  return_count=True, **kw_b)
+            nll, valid, ent, count = nll_entropy(news_vecs, user, tg[a:b, c:c + W].contiguous(), tau_b, exclude=ex_b, return_count=True, **kw_b)
             if c == 0:                                        # a user's entropy is counted once: with its first block of targets
                 counted = (count > 0) & ~torch.isnan(ent)
                 ent_total = ent_total + torch.where(counted, ent, torch.zeros_like(ent)).sum()
