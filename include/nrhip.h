@@ -788,7 +788,8 @@ int nr_score_logz(const nr_logz_desc* d, nr_stream_t stream);
  *   row_ids      [U, k] int32, row stride ld_ids, k in [1, NR_TOPK_MAX_K]
  *   base_max, base_logsum   [U] fp32 each: out_max and out_logsum of a K13 call for these users, pools and temperatures
  *   tau, tau_u   as in K13; an entry of tau_u that is <= 0, NaN or infinite gives NaN for every real entry of that user's row
- *   out_logp     [U, k] fp32, contiguous;  out_total optional [U] fp32: the fp64 sum of the row, rounded once
+ *   out_logp     [U, k] fp32, contiguous;  out_total optional [U] fp32: the fp64 sum of the row, rounded once (NaN as soon as
+ *               one entry of the row is NaN)
  * sequential = 1: Plackett-Luce without replacement, the law of nr_score_sample's rows.  The base must have been computed
  * with the row's ids LEFT OUT of the sum (the caller merges them into the lists of K13).  With s_i the score of entry i, the
  * mass that is left at step j is the base and the entries j .. k-1:
@@ -953,14 +954,20 @@ int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream);
  *               The pass is two-pass by design: with the base known every weight is p <= 1 and no accumulator is rescaled.
  *               p is formed as expf(fmaf(s - max, 1 / tau, -logsum)), 1 / tau ONE fp32 division per user (s == max: the
  *               argument is -logsum, also where 1 / tau overflows).
- *   weight      optional [U] fp32 (NULL = 1): the row's upstream-gradient scale
+ *   weight      optional [U] fp32 (NULL = 1): the row's upstream-gradient scale.  A NaN weight gives that user a row of NaN; its
+ *               mass and every other user are untouched.
  *   sub_ids, sub_w   optional, both or neither: [U, ld_sub] int32 / fp32, T <= NR_TOPK_MAX_K columns.  Ids outside [1, V) are fill
- *               and skipped; a repeated id is simply two entries.
+ *               and skipped; a repeated id is simply two entries.  A named row is subtracted as it is: a component of it that
+ *               is not finite reaches that column of out[u] (the cleaning below applies to the sum over v only).
  *   scale_inv_tau   nonzero: the finished row is multiplied by 1 / tau_u
  *   out         [U, ld_out] fp32:  out[u] = (weight_u E_u - sum_t sub_w[u, t] news[sub_ids[u, t]]) (* 1 / tau_u): with
- *               weight = sum_t g_t, sub_w = g the whole gradient of sum_t g_t nll(u, t) with respect to user_u in one call
+ *               weight = sum_t g_t, sub_w = g the whole gradient of sum_t g_t nll(u, t) with respect to user_u in one call.
+ *               Columns N .. ld_out - 1 of a row are never written.  A user with nothing eligible still has its named rows
+ *               subtracted (and scaled): out[u] = -sum_t sub_w news[sub_ids], rounded once.
  *   out_mass    optional [U] fp32: sum_v p(v | u) -- 1 up to rounding when the base matches the arguments, a cheap check
- *   edge cases  nothing eligible (base_max = -inf, whatever tau_u holds): E = 0, mass 0.  A tau_u entry that is <= 0, NaN or infinite, or a NaN in the
+ *   edge cases  nothing eligible (base_max = -inf, whatever tau_u holds): E = 0, mass 0.  A largest eligible score of -inf (K13:
+ *               max -inf, a count above 0, logsum NaN) reads the same way here and in K23 / K24: base_max = -inf decides, zeros and
+ *               mass 0, whatever base_logsum holds.  A tau_u entry that is <= 0, NaN or infinite, or a NaN in the
  *               user's base: a row of NaN and mass NaN; every other user is untouched.  Components of a news row that are not
  *               finite count as 0 in E: such a row's score is NaN or infinite for every user, so it has weight 0 (or its
  *               +inf score makes the base, and with it the row, NaN).
@@ -977,7 +984,8 @@ int nr_row_logprob_capped(const nr_logprob_capped_desc* d, nr_stream_t stream);
  * with n the eligible news, C = max_v |s_v| / tau, G = max_v (sum_c |user_c news_vc| + |prior_v|) / tau (the score chain: N fma
  * roundings and the prior's add, twice: numerator and partition), K = 2 * seg / 128 the lane chain of K13's base, and L = 128 *
  * (chunks of the longest slice) the fp32 accumulation chain of the second contraction.
- *   ws          nr_score_expect_workspace_bytes(d): U * slices * (N * 4 + 8) bytes, rounded to 8 (0 = bad descriptor)
+ *   ws          nr_score_expect_workspace_bytes(d): U * slices * (N * 4 + 8) bytes, rounded to 8 (0 = bad descriptor); 8-byte
+ *               alignment is all it needs: the fp32 partial rows behind the U * slices doubles may start 8 mod 16
  * Refused before any launch: what K13 refuses; a null base_max / base_logsum / out; sub_ids without sub_w or the reverse; T
  * outside [1, NR_TOPK_MAX_K] or ld_sub < T when sub_ids is given; ld_out < N or an out that is not 16-byte aligned; an
  * undersized workspace.  Layout: nr_logz_desc's fields in its order up to tau_u, then this call's, then the shared tail.      */
@@ -1448,7 +1456,7 @@ int nr_score_entropy(const nr_entropy_desc* d, nr_stream_t stream);
  * metrics.expect_affine_reference states the contract on the host.
  *   alpha       optional [U] fp32 (NULL = 1);  beta  optional [U] fp32 (NULL = 0).  With alpha = 1, beta = 0 rows and mass are K17's
  *               (weight NULL) bit for bit at the same explicit `splits`.  A NaN in a user's alpha or beta gives that user a row
- *               of NaN (where it has a weight at all) and touches nobody else.
+ *               of NaN (where it has a weight at all) and touches nobody else; that user's out_mass stays sum_v p_v.
  *   the other fields, the edge cases and the refusals   K17's; r_v = 0 exactly where p_v == 0 (0 * -inf is never formed)
  *   out_mass    optional [U] fp32: sum_v p_v, K17's mass -- not the sum of r
  * Stream and finalize are K17's (same user tiles and k-slab counts, same LDS, no scratch), the one difference the value stored to

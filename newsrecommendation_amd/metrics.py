@@ -438,7 +438,7 @@ def expect_affine_reference(news, user, temperature, exclude=None, prior=None, s
     What is eligible, p and x = log p are entropy_reference's.  Per user, in float64,
     out[u] = sum_v p_v (alpha_u + beta_u x_v) news[v] - sum_t sub_w[u, t] news[sub_ids[u, t]], times 1 / tau_u when scale_inv_tau;
     alpha None = 1, beta None = 0; a term with p == 0 is 0; named ids outside [1, V) are fill; components of `news` that are not
-    finite count as 0.  mass[u] = sum p.  Nothing eligible: only the named rows, mass 0.  A temperature that is not finite and
+    finite count as 0 in the sum over v -- a NAMED row is subtracted as it is, its non-finite components included.  mass[u] = sum p.  Nothing eligible: only the named rows, mass 0.  A temperature that is not finite and
     > 0, or a largest score of +-inf: a row of NaN and mass NaN.  Returns (out float64 [U, N], mass float64 [U])."""
     a = np.asarray(news, dtype=np.float64)
     b = np.asarray(user, dtype=np.float64)
@@ -459,7 +459,9 @@ def expect_affine_reference(news, user, temperature, exclude=None, prior=None, s
             ids = np.asarray(sub_ids[u], dtype=np.int64).reshape(-1)
             w = np.asarray(sub_w[u], dtype=np.float64).reshape(-1)
             real = (ids >= 1) & (ids < V)
-            out[u] -= w[real] @ clean[ids[real]]
+            with np.errstate(invalid="ignore"):
+                for t in np.flatnonzero(real):                              # the named rows as they are, as the device subtracts them
+                    out[u] -= w[t] * a[ids[t]]
         if scale_inv_tau:
             out[u] /= tau[u]
     return out, mass
