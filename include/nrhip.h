@@ -911,7 +911,7 @@ int nr_score_logz_groups(const nr_logz_groups_desc* d, nr_stream_t stream);
  *   out_logp    [U, k] fp32 contiguous; out_total optional [U]: the fp64 sum of the row, rounded once
  * Entries: an id that is 0 or outside [1, V) is fill: 0, part of no sum.  A key-0 entry (NaN score, prior -inf, stamp outside the
  * window) gives NaN, is part of no sum and uses up nothing of a cap.  A bad tau_u entry gives NaN for the real entries of the
- * user.  A live entry whose group already has c live entries before it gives -inf (the capped sampler never draws it): it uses up
+ * user; a NaN base gives NaN for every live step at which its bin is still open (a NaN in bin n_groups: every live step).  A live entry whose group already has c live entries before it gives -inf (the capped sampler never draws it): it uses up
  * nothing of a cap, its weight still counts in D_j of every earlier step at which its group was open (the caller left it out of
  * the bases), and out_total is then -inf.  Repeats and membership in the lists are the caller's statement, as in K14.
  * Refused before any launch: what K14 refuses; group_cap outside [1, 128]; n_groups outside [1, NR_RANK_MAX_GROUPS];
@@ -1168,6 +1168,7 @@ int nr_row_logprob_grad(const nr_logprob_grad_desc* d, nr_stream_t stream);
  *   sub_ids, sub_w, ld_sub, T, scale_inv_tau   K17's fields and meaning
  *   out         [U, ld_out] fp32;   out_mass optional [U] fp32: sum_v omega p over the EXACT products, summed in fp64 -- up to
  *               rounding sum of omega_b over the non-empty bins
+ *               Columns N .. ld_out - 1 of an `out` row are never written.
  * Stream: K17's kernel (the scoring tile, the P tile in LDS, out[TU, N] += P[TU, 128] . rows[128, N] on
  * v_mfma_f32_16x16x4_f32, accumulators in registers for the whole slice, nothing rescaled) with rows read through order[] for
  * both contractions and prior / stamp gathered by id.  A position whose id is 0 is padding: weight 0.  A segment never
@@ -1254,7 +1255,8 @@ int nr_score_expect_groups(const nr_expect_groups_desc* d, nr_stream_t stream);
  * fp32 once; a user's outputs depend on that user's inputs only.
  *   row_ids, group, group_cap, n_groups, base_max, base_logsum, ld_base, tau, tau_u, pools   as in K16
  *   g            optional [U, ld_g] fp32, ld_g >= k; NULL = 1 everywhere
- *   out_bin_w    [U, ld_base] fp32: omega; bins 0 .. n_groups all written, 0 for empty bins
+ *   out_bin_w    [U, ld_base] fp32: omega; bins 0 .. n_groups all written, 0 for empty bins; columns n_groups + 1 .. ld_base - 1
+ *                are never written
  *   out_sub_w    [U, k] fp32, contiguous: c
  * Special entries: fill and key-0 entries are no step: c = 0, their g is not read.  A user whose temperature is <= 0, NaN or
  * infinite, or with a NaN in a base (gmax NaN, or logsum NaN in a non-empty bin; every bin is open at step 0, so the row
@@ -1324,6 +1326,7 @@ int nr_row_logprob_capped_grad(const nr_logprob_capped_grad_desc* d, nr_stream_t
  *   named_offsets, named_user, named_w, n_named   K18's named terms, offsets [V + 1] BY NEWS ID
  *   out         [V, ld_out] fp32, required.   out_mass   optional [V] fp32: sum_u omega[u, bin(v)] p over the exact products,
  *               summed in fp64, without 1 / tau.  There is no mass-only mode.
+ *               Columns N .. ld_out - 1 of an `out` row are never written.
  * Live pairs.  A (user, bin) pair is live exactly when tau_u is finite and > 0, gmax and logsum are finite, and omega is finite
  * and != 0.  A pair that is not live contributes exactly nothing and puts no NaN anywhere.  This differs from K20 ON PURPOSE:
  * K20 answers such a user with a row of NaN, which stays with that user; on the news side one NaN would reach every row of the

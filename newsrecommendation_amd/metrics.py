@@ -782,7 +782,8 @@ def expect_groups_reference(a, b, *, temperature, group, n_groups=None, bases=No
     with (logsum, gmax) = bases when given (what logz_groups_reference or the device returned for the same arguments) and the
     bin's own exact softmax when bases is None, and
       expect[u] = sum_b omega_b sum_v p_b(v) a[v],   mass[u] = sum_b omega_b sum_v p_b(v)
-    A bin with omega == 0 contributes exactly nothing whatever its base holds; so does an empty bin.  A user with a non-empty
+    A bin with omega == 0 contributes exactly nothing whatever its base holds; so does an empty bin, and a bin whose largest
+    eligible score is -inf counts as empty (gmax = -inf is how the device knows an empty bin).  A user with a non-empty
     bin and a temperature that is not finite and > 0, or with a non-empty bin whose omega != 0 and whose omega is not finite,
     whose gmax is NaN or +inf or whose logsum is NaN: a row of NaN and mass NaN.  Components of `a` that are not finite count as 0.
     Returns (expect float64 [U, N], mass float64 [U])."""
@@ -812,6 +813,8 @@ def expect_groups_reference(a, b, *, temperature, group, n_groups=None, bases=No
                     if x.size == 0:
                         continue
                     gm = x.max()
+                    if gm == -np.inf:                                          # the device reads a maximum of -inf as an empty bin, whatever the count
+                        continue
                     ls = np.log(np.sum(np.exp((x - gm) / tau[u]))) if tau_ok[u] and np.isfinite(gm) else np.nan
                 else:
                     ls, gm = float(np.asarray(bases[0], dtype=np.float64)[u, bb]), float(np.asarray(bases[1], dtype=np.float64)[u, bb])
@@ -836,7 +839,9 @@ def expect_groups_reference(a, b, *, temperature, group, n_groups=None, bases=No
 def _capped_grad_rows(a, b, row_ids, temperature, bases, group, group_cap, n_groups, g, prior, stamp, window, mutant=None):
     """capped_row_logprob_grad_reference's body.  `mutant` names a deliberately wrong formula (tests/test_capgrad_host.py shows
     that each is caught by finite differences): "q_after_close" (Q at t_b + 1), "blocked_zero" (a blocked entry given c = 0),
-    "closed_full_q" (a closed bin given the full Q)."""
+    "closed_full_q" (a closed bin given the full Q); tests/test_capped_sweep_host.py adds "blocked_after_close" (a blocked entry's
+    weight kept in D_j after its bin closed), "exclusive_scan" (Q_i without the step i itself) and "blocked_g_read" (a blocked
+    entry treated as a step of its own g)."""
     if not 1 <= int(group_cap) <= 128:
         raise ValueError(f"group_cap = {group_cap}, must be in [1, 128]")
     a = np.asarray(a, dtype=np.float64)
@@ -875,21 +880,22 @@ def _capped_grad_rows(a, b, row_ids, temperature, bases, group, group_cap, n_gro
             lD = np.full(k, np.inf)
             for j in steps:
                 open_bins = t_close >= j
-                terms = np.concatenate([lx[j:][live[j:] & open_bins[bn[j:]]], lB[open_bins]])
+                later = open_bins[bn[j:]] | capped[j:] if mutant == "blocked_after_close" else open_bins[bn[j:]]
+                terms = np.concatenate([lx[j:][live[j:] & later], lB[open_bins]])
                 lD[j] = np.logaddexp.reduce(terms)
             gl = np.where(live & ~capped, gs[u], 0.0)
             last = steps[-1]
 
             def q_times(log_num, upto):
                 """sum_{j <= upto, j a live step} g_j exp(log_num - log D_j): every exponent <= 0 where log_num is a term of D_upto"""
-                js = steps[steps <= upto]
+                js = steps[steps < upto] if mutant == "exclusive_scan" else steps[steps <= upto]
                 return float(np.sum(gl[js] * np.exp(log_num - lD[js]))) if js.size else 0.0
 
             for i in range(k):
                 if not live[i]:
                     continue
                 if capped[i]:
-                    sub_w[u, i] = 0.0 if mutant == "blocked_zero" else -q_times(lx[i], t_close[bn[i]])
+                    sub_w[u, i] = 0.0 if mutant == "blocked_zero" else (gs[u, i] if mutant == "blocked_g_read" else 0.0) - q_times(lx[i], t_close[bn[i]])
                 else:
                     sub_w[u, i] = gs[u, i] - q_times(lx[i], i)
             for bb in range(G + 1):
