@@ -1568,6 +1568,144 @@ size_t nr_score_expect_news_affine_workspace_bytes(const nr_expect_news_affine_d
 int nr_score_expect_news_affine(const nr_expect_news_affine_desc* d, nr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * K26  KL divergence of the served distribution to a reference policy.  Two policies over the same table, lists and pools: the
+ * policy p(. | u) from `user` at tau and the reference q(. | u) from `ref` at ref_tau (a logging or teacher checkpoint).  Per
+ * (user, news) pair the device forms
+ *   x_v = log p_v = fmaf(s_v  - max , 1 / tau , -logsum ),   p_v = expf(x_v)                  (K23's formation)
+ *   y_v = log q_v = fmaf(s'_v - max', 1 / tau', -logsum'),   s'_v = fl(<news_v, ref_u> + prior_v)
+ * s' by the same scoring tile and chain as every other score (the reference vectors are further rows of the user tile), so its
+ * bits are what nr_score_logz(news, ref, tau', same lists and pools) sees, and (max', logsum') is that call's base.
+ * d_v = x_v - y_v is formed in fp64 from the two fp32 values.  Per user, over exactly the news K13 sums over for the POLICY,
+ *   m0 = sum p,   m1 = sum p x,   k1 = sum p d,   k2 = sum p d x
+ * and four results, each [U] fp32 (metrics.kl_reference states the contract on the host):
+ *   out_kl        KL(p || q) = k1.  Not clamped: rounding may leave a tiny negative value
+ *   out_entropy   optional: H = -m1 (K23's)
+ *   out_cov       optional: Cov_p(d, x) = k2 - k1 m1 (formed in fp64);  d KL / d tau = -out_cov / tau
+ *   out_mass      optional: m0
+ * A pair with p == 0 is a term of no sum (0 * +-inf is never formed).  No [U, V] matrix exists.
+ *   edge cases  nothing eligible for the policy (base_max = -inf, whatever else holds): 0, 0, 0, 0.  Else a tau_u or ref_tau_u
+ *               entry that is <= 0, NaN or infinite, a NaN in either base, or a reference maximum that is not finite (-inf: the
+ *               reference has nothing eligible while the policy has): NaN for that user's four results, nobody else's change.
+ *               The reference equal to the policy (same vectors, temperature and base): out_kl == 0.0 and out_cov == 0.0
+ *               exactly (x and y are then the same bits).  A pair that is a term for the policy and whose reference score is
+ *               NaN gives y = NaN, and so that user NaN; a reference score of -inf gives KL = +inf.
+ * Bits.  Per pair the products are formed in fp64 from the fp32 p, x and y and added to four per-lane fp64 chains over the lane's
+ * news of the slice (which lane sees which id is fixed by V); an xor butterfly leaves one quadruple per (user, slice); a second
+ * kernel adds the slices in ascending order in fp64 and rounds each result to fp32 once.  For a fixed explicit `splits` a user's
+ * results depend on that user's inputs and V only -- not on U, the user tile or the place in it.
+ * Error bounds (derived in DESIGN.md section 5; first order in e = 2^-24) against the exact values of the fp32 inputs.  x carries
+ * the absolute error kappa_x e (K23's), y carries kappa_y e = the same expression with the reference's (n, C', G'); with
+ * A = sum p* |d*|, B = sum p* |d* x*|, D = max_v |d*_v| + 1 over the terms:
+ *   |KL - KL*|   <= ((kappa_x + 8) A + kappa_x + kappa_y + 1) e + n 2^-126 D
+ *   |cov - cov*| <= ((kappa_x + 8) (B + 2 A H*) + 2 (kappa_x + kappa_y) H* + 2 kappa_x A + 1) e + n 2^-119 D
+ *   |H - H*|, |mass - 1|   K23's
+ *   ws          nr_score_kl_workspace_bytes(d): U * slices * 32 bytes (0 = bad descriptor)
+ * The stream is K13's (segments, slices, LDS) with a tile of 2 x (users per workgroup) rows: 32 users per workgroup up to
+ * N = 480, 16 up to 960, else 8.
+ * Refused before any launch: what K17 refuses of the shared fields; a scalar ref_tau that is not finite and > 0; a null ref,
+ * ref_base_max or ref_base_logsum; an ld_ref that is not a multiple of 4 and >= N, or a ref off a 16-byte boundary; a null
+ * base_max / base_logsum / out_kl; an undersized workspace.
+ * Layout: nr_entropy_desc's fields in its order up to base_logsum, then the reference's, the results, then the shared tail.  */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 for `user` at tau */
+  const float* base_logsum;    /* [U]: out_logsum of K13 for `user` at tau */
+  const float* ref;            /* [U, ld_ref]: the reference user vectors */
+  int ld_ref;
+  float ref_tau;               /* used when ref_tau_u == NULL; finite, > 0 */
+  const float* ref_tau_u;      /* optional [U] */
+  const float* ref_base_max;   /* [U]: out_max of K13 for `ref` at ref_tau */
+  const float* ref_base_logsum; /* [U]: out_logsum of K13 for `ref` at ref_tau */
+  float* out_kl;               /* [U] */
+  float* out_entropy;          /* optional [U] */
+  float* out_cov;              /* optional [U] */
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_kl_desc;
+size_t nr_score_kl_workspace_bytes(const nr_kl_desc* d);
+int nr_score_kl(const nr_kl_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K27  K24 with a weight that is also affine in the reference's log-probability: the gradient of K26.  With x, y, p of K26,
+ *   out[u] = (sum_v r_v news_v - sum_t sub_w[u, t] news[sub_ids[u, t]]) (* 1 / tau_u),
+ *   r_v = p_v fmaf(gamma_u, y_v, fmaf(beta_u, x_v, alpha_u)).
+ * d KL(p || q) / d user = (1 / tau) sum_v p_v (d_v - KL) news_v, so d (kappa KL) / d user is one call with alpha = -kappa KL,
+ * beta = kappa, gamma = -kappa and scale_inv_tau; added to K24's (alpha, beta) it serves sum_t g_t nll_t + h H + kappa KL in one
+ * call.  metrics.expect_kl_reference states the contract on the host.
+ *   alpha, beta optional [U] fp32, K24's (NULL = 1 and 0);  gamma  optional [U] fp32 (NULL = 0)
+ *               A NaN in a user's alpha, beta or gamma gives that user a row of NaN (where it has a weight at all) and touches
+ *               nobody else.  With gamma = 0 (or NULL) and a finite y the weight is K24's; rows then agree with K24's to within
+ *               the two bounds (the user tiles, and so the slices chosen for splits = 0, differ).
+ *   ref, ld_ref, ref_tau, ref_tau_u, ref_base_max, ref_base_logsum   K26's fields and meaning
+ *   the other fields   K24's; r_v = 0 exactly where p_v == 0;  out_mass stays sum_v p_v
+ *   edge cases  K26's: nothing eligible for the policy: only the named rows, mass 0; a bad tau / ref_tau entry, a NaN in either
+ *               base or a reference maximum that is not finite: a row of NaN and mass NaN for that user, nobody else's change.
+ * Stream: K24's with a score tile of twice the rows per user (the scoring tile does twice K24's work per user); the second
+ * contraction is K24's.  32 users per workgroup up to 13 k-slabs of 32 columns (N <= 416), 16 up to 26 (N <= 832), else 8; no
+ * instantiation uses scratch.  Finalize: K24's.  Bits: K17's rule -- for a fixed explicit `splits` a user's row depends on that
+ * user's inputs, V and N only.  Error bound (derived in DESIGN.md section 5):
+ *   |out_c - out*_c| <= kappa'' e A_c,   A_c = sum_v p*_v (|alpha| + |beta| (|x*_v| + 1) + |gamma| (|y*_v| + 1)) |news_vc|,
+ *   kappa'' = max(kappa' + 1, kappa_y)    (K24's kappa' and the rounding of the gamma fma; the + 1 beside |y*| carries the
+ *               absolute error kappa_y e of y through gamma, as the one beside |x*| carries kappa_x <= kappa' through beta)
+ *   ws          nr_score_expect_kl_workspace_bytes(d): U * slices * (N * 4 + 8) rounded to 8 (K17's formula)
+ * Refused before any launch: what K24 refuses, and K26's refusals of the reference fields.
+ * Layout: nr_expect_affine_desc with gamma and K26's six reference fields after `beta`.                                      */
+typedef struct {
+  const float* news_vecs;
+  int ld_news, V;
+  const float* user;
+  int ld_user, U;
+  int N;
+  int splits;
+  const int32_t* excl_offsets; /* optional [U + 1]: as in nr_topk_desc */
+  const int32_t* excl_ids;     /* optional [n_excl]: as in nr_topk_desc */
+  int n_excl;
+  float tau;                   /* used when tau_u == NULL; finite, > 0 */
+  const float* tau_u;          /* optional [U] */
+  const float* base_max;       /* [U]: out_max of K13 for `user` at tau */
+  const float* base_logsum;    /* [U]: out_logsum of K13 for `user` at tau */
+  const float* alpha;          /* optional [U]; NULL = 1 */
+  const float* beta;           /* optional [U]; NULL = 0 */
+  const float* gamma;          /* optional [U]; NULL = 0 */
+  const float* ref;            /* [U, ld_ref]: the reference user vectors */
+  int ld_ref;
+  float ref_tau;               /* used when ref_tau_u == NULL; finite, > 0 */
+  const float* ref_tau_u;      /* optional [U] */
+  const float* ref_base_max;   /* [U]: out_max of K13 for `ref` at ref_tau */
+  const float* ref_base_logsum; /* [U]: out_logsum of K13 for `ref` at ref_tau */
+  const int32_t* sub_ids;      /* optional [U, ld_sub]; with sub_w */
+  const float* sub_w;          /* optional [U, ld_sub]; with sub_ids */
+  int ld_sub, T;
+  int scale_inv_tau;
+  float* out;                  /* [U, ld_out] */
+  int ld_out;
+  float* out_mass;             /* optional [U] */
+  void* ws;
+  size_t ws_bytes;
+  const float* prior;    /* optional [V] */
+  const int32_t* stamp;  /* optional [V]; with window */
+  const int32_t* window; /* optional [U, ld_window]: (lo, hi); with stamp */
+  int ld_window;
+} nr_expect_kl_desc;
+size_t nr_score_expect_kl_workspace_bytes(const nr_expect_kl_desc* d);
+int nr_score_expect_kl(const nr_expect_kl_desc* d, nr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * f1  device-side batch assembly -- DatasetTrain.line_mapper's `news_combined[...]` gathers + the positive splice +
  * the DataLoader collate, src/dataset.py:44-49, src/main.py:89-103.  Only news INDICES come from the host (once per
  * epoch); the feature rows are gathered here.

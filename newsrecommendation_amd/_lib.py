@@ -215,6 +215,27 @@ class ExpectNewsAffineDesc(C.Structure):
                 ("ld_window", C.c_int)]
 
 
+class KlDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("splits", C.c_int), ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int),
+                ("tau", C.c_float), ("tau_u", C.c_void_p), ("base_max", C.c_void_p), ("base_logsum", C.c_void_p),
+                ("ref", C.c_void_p), ("ld_ref", C.c_int), ("ref_tau", C.c_float), ("ref_tau_u", C.c_void_p), ("ref_base_max", C.c_void_p),
+                ("ref_base_logsum", C.c_void_p), ("out_kl", C.c_void_p), ("out_entropy", C.c_void_p), ("out_cov", C.c_void_p),
+                ("out_mass", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
+
+
+class ExpectKlDesc(C.Structure):
+    _fields_ = [("news_vecs", C.c_void_p), ("ld_news", C.c_int), ("V", C.c_int), ("user", C.c_void_p), ("ld_user", C.c_int), ("U", C.c_int),
+                ("N", C.c_int), ("splits", C.c_int), ("excl_offsets", C.c_void_p), ("excl_ids", C.c_void_p), ("n_excl", C.c_int),
+                ("tau", C.c_float), ("tau_u", C.c_void_p), ("base_max", C.c_void_p), ("base_logsum", C.c_void_p), ("alpha", C.c_void_p),
+                ("beta", C.c_void_p), ("gamma", C.c_void_p), ("ref", C.c_void_p), ("ld_ref", C.c_int), ("ref_tau", C.c_float),
+                ("ref_tau_u", C.c_void_p), ("ref_base_max", C.c_void_p), ("ref_base_logsum", C.c_void_p),
+                ("sub_ids", C.c_void_p), ("sub_w", C.c_void_p), ("ld_sub", C.c_int), ("T", C.c_int),
+                ("scale_inv_tau", C.c_int), ("out", C.c_void_p), ("ld_out", C.c_int), ("out_mass", C.c_void_p), ("ws", C.c_void_p),
+                ("ws_bytes", C.c_size_t), ("prior", C.c_void_p), ("stamp", C.c_void_p), ("window", C.c_void_p), ("ld_window", C.c_int)]
+
+
 class PoolDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("L", C.c_int), ("N", C.c_int), ("q", C.c_int), ("dtype", C.c_int), ("x", C.c_void_p),
                 ("mask", C.c_void_p), ("w1", C.c_void_p), ("ldw1", C.c_int), ("b1", C.c_void_p), ("w2", C.c_void_p),
@@ -236,7 +257,8 @@ RESTYPES = {"nr_pool_seq_flags": C.c_void_p, "nr_eval_metrics_workspace_bytes": 
             "nr_score_logz_groups_workspace_bytes": C.c_size_t, "nr_score_expect_workspace_bytes": C.c_size_t,
             "nr_score_expect_news_workspace_bytes": C.c_size_t, "nr_score_expect_groups_workspace_bytes": C.c_size_t,
             "nr_score_expect_news_groups_workspace_bytes": C.c_size_t, "nr_score_entropy_workspace_bytes": C.c_size_t,
-            "nr_score_expect_affine_workspace_bytes": C.c_size_t, "nr_score_expect_news_affine_workspace_bytes": C.c_size_t}
+            "nr_score_expect_affine_workspace_bytes": C.c_size_t, "nr_score_expect_news_affine_workspace_bytes": C.c_size_t,
+            "nr_score_kl_workspace_bytes": C.c_size_t, "nr_score_expect_kl_workspace_bytes": C.c_size_t}
 SIGNATURES = {
     "nr_version": [],
     "nr_last_error": [C.c_char_p, C.c_size_t],
@@ -319,6 +341,10 @@ SIGNATURES = {
     "nr_score_expect_affine": [C.POINTER(ExpectAffineDesc), _vp],
     "nr_score_expect_news_affine_workspace_bytes": [C.POINTER(ExpectNewsAffineDesc)],
     "nr_score_expect_news_affine": [C.POINTER(ExpectNewsAffineDesc), _vp],
+    "nr_score_kl_workspace_bytes": [C.POINTER(KlDesc)],
+    "nr_score_kl": [C.POINTER(KlDesc), _vp],
+    "nr_score_expect_kl_workspace_bytes": [C.POINTER(ExpectKlDesc)],
+    "nr_score_expect_kl": [C.POINTER(ExpectKlDesc), _vp],
     "nr_gemm_nt": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "nr_gemm_tn": [_i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp],
     "nr_dropout_mask": [_vp, _u32, _f, _u32, _vp],
@@ -368,7 +394,8 @@ def lib():
                     fn.restype = RESTYPES.get(name, C.c_int)
                 structs = (MhsaDesc, ConvDesc, PoolDesc, LinearDesc, CastJob, PackJob, AdamRowsDesc, TopkDesc, RankDesc, MmrDesc, SampleDesc, LogzDesc,
                            LogprobDesc, LogzGroupsDesc, LogprobCappedDesc, ExpectDesc, ExpectNewsDesc, LogprobGradDesc, ExpectGroupsDesc,
-                           LogprobCappedGradDesc, ExpectNewsGroupsDesc, EntropyDesc, ExpectAffineDesc, ExpectNewsAffineDesc)
+                           LogprobCappedGradDesc, ExpectNewsGroupsDesc, EntropyDesc, ExpectAffineDesc, ExpectNewsAffineDesc,
+                           KlDesc, ExpectKlDesc)
                 sizes = (C.c_size_t * len(structs))()
                 if L.nr_abi_sizes(sizes, len(structs)) != 0 or list(sizes) != [C.sizeof(t) for t in structs]:
                     raise RuntimeError(f"libnrhip.so descriptor layout {list(sizes)} differs from the ctypes binding "

@@ -496,6 +496,7 @@ int nr_abi_sizes(size_t* out, int n) {
   if (n >= 21) out[20] = sizeof(nr_expect_news_groups_desc);
   if (n >= 23) { out[21] = sizeof(nr_entropy_desc); out[22] = sizeof(nr_expect_affine_desc); }
   if (n >= 24) out[23] = sizeof(nr_expect_news_affine_desc);
+  if (n >= 26) { out[24] = sizeof(nr_kl_desc); out[25] = sizeof(nr_expect_kl_desc); }
   return NR_OK;
 }
 

@@ -467,6 +467,90 @@ def expect_affine_reference(news, user, temperature, exclude=None, prior=None, s
     return out, mass
 
 
+def _kl_rows(news, user, ref, temperature, ref_temperature, exclude, prior, stamp, window):
+    """Per user the float64 (ok mask [V], p, x = log p, y = log q) over the news eligible for the POLICY, the shared front of
+    kl_reference and expect_kl_reference.  p is None for a NaN user: something is eligible for the policy and either side has a
+    temperature that is not finite and > 0 or a largest score of +-inf, or the reference has nothing eligible.  y is NaN where the
+    news is not eligible for the reference (its score there is NaN)."""
+    a = np.asarray(news, dtype=np.float64)
+    rows_p = _log_softmax_rows(a, np.asarray(user, dtype=np.float64), temperature, exclude, prior, stamp, window)
+    rows_q = _log_softmax_rows(a, np.asarray(ref, dtype=np.float64), ref_temperature, exclude, prior, stamp, window)
+    rows = []
+    for (ok, p, x), (okq, q, y) in zip(rows_p, rows_q):
+        if not ok.any():
+            rows.append((ok, np.zeros(0), np.zeros(0), np.zeros(0)))
+        elif p is None or q is None or not okq.any():
+            rows.append((ok, None, None, None))
+        else:
+            full = np.full(ok.shape[0], np.nan)
+            full[okq] = y
+            rows.append((ok, p, x, full[ok]))
+    return rows
+
+
+def kl_reference(news, user, ref, tau, ref_tau, exclude=None, prior=None, stamp=None, window=None):
+    """Host statement of the KL contract (include/nrhip.h, nr_score_kl); tests check the device against it, no product path
+    calls it.
+
+    `news` [V, N], `user` and `ref` [U, N]: the policy p = softmax(scores(user) / tau) and the reference
+    q = softmax(scores(ref) / ref_tau) over what logz_reference calls eligible under the shared `exclude` and pools.  Per user,
+    in float64 with x = log p, y = log q, d = x - y over the policy's eligible news: kl = sum p d = KL(p || q), entropy = -sum p x,
+    cov = sum p d x - (sum p d)(sum p x) = Cov_p(d, x) (d kl / d tau = -cov / tau), mass = sum p = 1.  A term with p == 0 is 0.
+    Nothing eligible for the policy: zeros.  A temperature on either side that is not finite and > 0, a largest score of +-inf on
+    either side, or a reference with nothing eligible: NaN for that user.
+    Returns (kl, entropy, cov, mass), float64 [U] each."""
+    U = np.asarray(user).shape[0]
+    kl, H, cov, mass = np.zeros(U), np.zeros(U), np.zeros(U), np.zeros(U)
+    for u, (ok, p, x, y) in enumerate(_kl_rows(news, user, ref, tau, ref_tau, exclude, prior, stamp, window)):
+        if p is None:
+            kl[u] = H[u] = cov[u] = mass[u] = np.nan
+            continue
+        live = p > 0
+        pl, xs, ds = p[live], x[live], x[live] - y[live]
+        with np.errstate(invalid="ignore"):
+            k1, m1 = float(np.sum(pl * ds)), float(np.sum(pl * xs))
+            kl[u], H[u], cov[u], mass[u] = k1, -m1, float(np.sum(pl * ds * xs)) - k1 * m1, float(np.sum(p))
+    return kl, H, cov, mass
+
+
+def expect_kl_reference(news, user, ref, tau, ref_tau, exclude=None, prior=None, stamp=None, window=None, alpha=None, beta=None,
+                        gamma=None, sub_ids=None, sub_w=None, scale_inv_tau=False):
+    """Host statement of the KL expected-news-vector contract (include/nrhip.h, nr_score_expect_kl); tests check the device against
+    it, no product path calls it.
+
+    What is eligible, p, x = log p and y = log q are kl_reference's.  Per user, in float64,
+    out[u] = sum_v p_v (alpha_u + beta_u x_v + gamma_u y_v) news[v] - sum_t sub_w[u, t] news[sub_ids[u, t]], times 1 / tau_u when
+    scale_inv_tau; alpha None = 1, beta None = 0, gamma None = 0; a term with p == 0 is 0; the named rows and the non-finite
+    components of `news` are expect_affine_reference's.  mass[u] = sum p.  Nothing eligible for the policy: only the named rows,
+    mass 0.  A NaN user of kl_reference: a row of NaN and mass NaN.  Returns (out float64 [U, N], mass float64 [U])."""
+    a = np.asarray(news, dtype=np.float64)
+    U, V = np.asarray(user).shape[0], a.shape[0]
+    t, _ = _temperatures(tau, U)
+    al = np.ones(U) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(U)
+    be = np.zeros(U) if beta is None else np.asarray(beta, dtype=np.float64).reshape(U)
+    ga = np.zeros(U) if gamma is None else np.asarray(gamma, dtype=np.float64).reshape(U)
+    clean = np.where(np.isfinite(a), a, 0.0)
+    out, mass = np.zeros((U, a.shape[1])), np.zeros(U)
+    for u, (ok, p, x, y) in enumerate(_kl_rows(news, user, ref, tau, ref_tau, exclude, prior, stamp, window)):
+        if p is None:
+            out[u], mass[u] = np.nan, np.nan
+            continue
+        live = p > 0
+        with np.errstate(invalid="ignore"):
+            r = np.where(live, p, 0.0) * (al[u] + be[u] * np.where(live, x, 0.0) + ga[u] * np.where(live, y, 0.0))
+            out[u], mass[u] = r @ clean[ok], float(np.sum(p))
+        if sub_ids is not None:
+            ids = np.asarray(sub_ids[u], dtype=np.int64).reshape(-1)
+            w = np.asarray(sub_w[u], dtype=np.float64).reshape(-1)
+            real = (ids >= 1) & (ids < V)
+            with np.errstate(invalid="ignore"):
+                for j in np.flatnonzero(real):                              # the named rows as they are, as the device subtracts them
+                    out[u] -= w[j] * a[ids[j]]
+        if scale_inv_tau:
+            out[u] /= t[u]
+    return out, mass
+
+
 def softmax_matrix_reference(a, b, *, temperature, exclude=None, prior=None, stamp=None, window=None):
     """The [U, V] float64 matrix p(v | u) of the full softmax over what logz_reference calls eligible (through _pooled), which
     the device never forms: row u sums to 1 over its eligible news and is 0 elsewhere.  A dead user -- a temperature that is not

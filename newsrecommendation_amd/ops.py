@@ -1716,6 +1716,214 @@ def full_softmax_nll_entropy(news_vecs, user_vecs, targets, temperature, exclude
     return (nll, valid, ent, count) if return_count else (nll, valid, ent)
 
 
+def _ref_args(what, ref_vecs, N, U, dev):
+    """The reference user vectors of a KL call: [U, N] fp32 with contiguous rows on the call's device."""
+    if (not isinstance(ref_vecs, torch.Tensor) or ref_vecs.dim() != 2 or ref_vecs.dtype != torch.float32 or tuple(ref_vecs.shape) != (U, N)
+            or ref_vecs.stride(1) != 1 or (U > 1 and ref_vecs.stride(0) < N) or ref_vecs.device != dev):
+        got = f"{tuple(ref_vecs.shape)} {ref_vecs.dtype} on {ref_vecs.device}" if isinstance(ref_vecs, torch.Tensor) else type(ref_vecs).__name__
+        raise RuntimeError(f"{what}: ref_vecs must be a 2-D fp32 tensor of shape ({U}, {N}) with contiguous rows on {dev}, got {got}")
+    return ref_vecs.detach()
+
+
+def _kl_fields(what, news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp, window):
+    """The descriptor fields K26 and K27 share, and the tensors they point into (kept alive by the caller)."""
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    ref = _ref_args(what, ref_vecs, N, U, dev)
+    bl, bm = _base_args(what, base, U, dev)
+    rbl, rbm = _base_args(what + " (reference)", ref_base, U, dev)
+    ex_fields, ex_keep = _exclude_args(what, exclude, U, dev, dense=False)
+    pr, st, win = _pool_args(what, V, U, dev, prior, stamp, window)
+    tau, tau_u = _tau_args(what, temperature, U, dev)
+    rtau, rtau_u = _tau_args(what + " (reference)", ref_temperature, U, dev)
+    fields = dict(news_vecs=ptr(news_vecs), ld_news=news_vecs.stride(0) if V > 1 else N, V=V, user=ptr(user_vecs),
+                  ld_user=user_vecs.stride(0) if U > 1 else N, U=U, N=N, **ex_fields, tau=tau, tau_u=ptr(tau_u), base_max=ptr(bm),
+                  base_logsum=ptr(bl), ref=ptr(ref), ld_ref=ref.stride(0) if U > 1 else N, ref_tau=rtau, ref_tau_u=ptr(rtau_u),
+                  ref_base_max=ptr(rbm), ref_base_logsum=ptr(rbl), prior=ptr(pr), stamp=ptr(st), window=ptr(win),
+                  ld_window=2 if win is not None else 0)
+    return fields, (ref, bl, bm, rbl, rbm, ex_keep, pr, st, win, tau_u, rtau_u)
+
+
+def _kl_need_gpu(news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp, window, *more):
+    _need_gpu(news_vecs, user_vecs, ref_vecs, exclude.ids if isinstance(exclude, ExclusionLists) else exclude, prior, stamp, window,
+              temperature if isinstance(temperature, torch.Tensor) else None,
+              ref_temperature if isinstance(ref_temperature, torch.Tensor) else None, base[0], base[1], ref_base[0], ref_base[1], *more)
+
+
+@torch.no_grad()
+def score_kl(news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude=None, splits=0, prior=None, stamp=None,
+             window=None):
+    """KL divergence of the served distribution to a reference policy (nr_score_kl; include/nrhip.h, K26): per user, with
+    p(v) = exp((score_v - smax) / temperature - logsum) from `user_vecs` and q(v) the same statement from `ref_vecs` at
+    `ref_temperature`, over exactly the news score_logz sums over for `user_vecs` (lists and pools are shared by the two),
+    kl = sum p (log p - log q), entropy = -sum p log p, cov = Cov_p(log p - log q, log p) and mass = sum p -- without the two
+    [U, V] matrices.  -cov / temperature is the derivative of kl with respect to the policy's temperature.
+    `base` = score_logz(news_vecs, user_vecs, temperature, ...), `ref_base` = score_logz(news_vecs, ref_vecs, ref_temperature, ...) for
+    the SAME exclude and pools; temperatures are floats or floating point [U] tensors.  Returns (kl, entropy, cov, mass), fp32 [U]
+    each; kl is not clamped (rounding may leave a tiny negative value).  A user with nothing eligible gets zeros; a bad entry of
+    either temperature tensor, a NaN in either base, or a reference with nothing eligible gives that user NaN; a reference equal to
+    the policy gives kl == 0 and cov == 0 exactly.  `splits`: 0 = the library chooses the number of corpus slices by U.  For a
+    fixed splits > 0 a user's results do not depend, bit for bit, on the other users of the call."""
+    _kl_need_gpu(news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp, window)
+    V, N, U, dev = _vector_args("score_kl", news_vecs, user_vecs)
+    kl, ent, cov, mass = (torch.empty(U, dtype=torch.float32, device=dev) for _ in range(4))
+    if U == 0:
+        return kl, ent, cov, mass
+    fields, keep = _kl_fields("score_kl", news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp,
+                              window)
+    d = _lib.KlDesc(splits=int(splits), out_kl=ptr(kl), out_entropy=ptr(ent), out_cov=ptr(cov), out_mass=ptr(mass), **fields)
+    ws = _ws(_lib.lib().nr_score_kl_workspace_bytes(C.byref(d)), dev)        # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_kl(C.byref(d), _stream()), "nr_score_kl")
+    return kl, ent, cov, mass
+
+
+def _score_expect_kl(what, news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, splits, prior, stamp, window,
+                     alpha, beta, gamma, sub_ids, sub_w, scale_inv_tau):
+    """One nr_score_expect_kl call (include/nrhip.h, K27): (out [U, N] fp32, mass [U] fp32)."""
+    _kl_need_gpu(news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp, window, alpha, beta, gamma,
+                 sub_ids, sub_w)
+    V, N, U, dev = _vector_args(what, news_vecs, user_vecs)
+    out = torch.empty(U, N, dtype=torch.float32, device=dev)
+    mass = torch.empty(U, dtype=torch.float32, device=dev)
+    if U == 0:
+        return out, mass
+    coef = []
+    for name, t in (("alpha", alpha), ("beta", beta), ("gamma", gamma)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or not t.is_floating_point() or t.device != dev:
+                raise RuntimeError(f"{what}: {name} must be a floating point tensor of shape ({U},) on {dev}")
+            t = t.detach().to(torch.float32).contiguous()
+        coef.append(t)
+    T = 0
+    if sub_ids is not None:
+        if sub_ids.dim() != 2 or sub_ids.shape[0] != U or sub_ids.is_floating_point() or sub_w is None or tuple(sub_w.shape) != tuple(sub_ids.shape):
+            raise RuntimeError(f"{what}: the named rows must be integer ids [U = {U}, T] with weights of the same shape")
+        T = sub_ids.shape[1]
+        sub_ids = sub_ids.detach().to(torch.int32).contiguous()
+        sub_w = sub_w.detach().to(torch.float32).contiguous()
+    fields, keep = _kl_fields(what, news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, prior, stamp, window)
+    d = _lib.ExpectKlDesc(splits=int(splits), alpha=ptr(coef[0]), beta=ptr(coef[1]), gamma=ptr(coef[2]), sub_ids=ptr(sub_ids), sub_w=ptr(sub_w),
+                          ld_sub=T, T=T, scale_inv_tau=1 if scale_inv_tau else 0, out=ptr(out), ld_out=N, out_mass=ptr(mass), **fields)
+    ws = _ws(_lib.lib().nr_score_expect_kl_workspace_bytes(C.byref(d)), dev)  # 0 for a bad descriptor: the call below says why
+    d.ws, d.ws_bytes = ptr(ws) if ws.numel() else None, ws.numel() * 4
+    check(_lib.lib().nr_score_expect_kl(C.byref(d), _stream()), "nr_score_expect_kl")
+    return out, mass
+
+
+@torch.no_grad()
+def score_expect_kl(news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude=None, splits=0, prior=None, stamp=None,
+                    window=None, alpha=None, beta=None, gamma=None, sub_ids=None, sub_w=None, scale_inv_tau=False):
+    """score_expect_affine with a weight that is also affine in the reference's log-probability (nr_score_expect_kl;
+    include/nrhip.h, K27): per user
+    out = sum_v p(v) (alpha + beta log p(v) + gamma log q(v)) news_vecs[v] - sum_t sub_w[t] news_vecs[sub_ids[t]], times
+    1 / temperature when scale_inv_tau; p, q, the bases and the temperatures are score_kl's.  alpha, beta, gamma: optional floating
+    point [U] (None = 1, 0, 0).  alpha = -kl, beta = 1, gamma = -1, scale_inv_tau gives the gradient of score_kl's kl with respect to
+    the user vector.  The other arguments are score_expect_affine's.  Returns (out fp32 [U, N], mass fp32 [U] = sum_v p(v)).  A NaN
+    in a user's alpha, beta or gamma, or on the user's reference side, gives that user a row of NaN and touches nobody else."""
+    return _score_expect_kl("score_expect_kl", news_vecs, user_vecs, ref_vecs, temperature, base, ref_temperature, ref_base, exclude, splits, prior,
+                            stamp, window, alpha, beta, gamma, sub_ids, sub_w, scale_inv_tau)
+
+
+class PolicyKLFunction(Function):
+    """(kl [U], valid [U]) between the served distribution of `user_vecs` and that of the constant `ref_vecs`, differentiable with
+    respect to the user vectors and, in the reverse mode, a temperature tensor that requires grad."""
+
+    @staticmethod
+    def forward(ctx, user_vecs, temperature, news_vecs, ref_vecs, ref_temperature, reverse, exclude, splits, prior, stamp, window):
+        user, ref = user_vecs.detach(), ref_vecs.detach()
+        U = user.shape[0]
+        tau = _tau_users(temperature, U)
+        rtau = tau if ref_temperature is None else _tau_users(ref_temperature, U)
+        kw = dict(exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+        base = score_logz(news_vecs, user, tau, **kw)
+        rbase = score_logz(news_vecs, ref, rtau, **kw)
+        if reverse:
+            kl, _, cov, _ = score_kl(news_vecs, user, ref, tau, base, rtau, rbase, **kw)
+        else:
+            kl, _, cov, _ = score_kl(news_vecs, ref, user, rtau, rbase, tau, base, **kw)
+        # not valid: nothing eligible, or what K26 answers with NaN (a bad temperature entry or a NaN base on either side)
+        valid = (base[2] > 0) & (rbase[2] > 0) & ~torch.isnan(kl)
+        out = torch.where(valid, kl, torch.zeros_like(kl))
+        ctx.save_for_backward(user, ref, news_vecs, valid, base[0], base[1], rbase[0], rbase[1], kl, cov)
+        ctx.rest = (tau, rtau, reverse, exclude, splits, prior, stamp, window)
+        ctx.tau_grad = isinstance(temperature, torch.Tensor) and temperature.requires_grad
+        ctx.tau_shape = tuple(temperature.shape) if isinstance(temperature, torch.Tensor) else None
+        ctx.tau_dtype = temperature.dtype if isinstance(temperature, torch.Tensor) else None
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return out, valid
+
+    @staticmethod
+    def backward(ctx, g, _gvalid):
+        user, ref, news_vecs, valid, bl, bm, rbl, rbm, kl, cov = ctx.saved_tensors
+        tau, rtau, reverse, exclude, splits, prior, stamp, window = ctx.rest
+        if g is None:
+            return (None,) * 11
+        dev, U = user.device, user.shape[0]
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        kap = torch.where(valid, g.to(torch.float64), zero)           # an invalid user contributes exactly nothing, not 0 * NaN
+        live = (valid & (kap != 0))[:, None]
+        grad_user = grad_tau = None
+        with torch.no_grad():
+            if ctx.needs_input_grad[0] and reverse:
+                KL = torch.where(valid, kl.to(torch.float64), zero)
+                k32 = kap.to(torch.float32)
+                grad_user, _ = _score_expect_kl("policy_kl", news_vecs, user, ref, tau, (bl, bm), rtau, (rbl, rbm), exclude, splits, prior, stamp,
+                                                window, (-kap * KL).to(torch.float32), k32, -k32, None, None, True)
+                grad_user = torch.where(live, grad_user, torch.zeros_like(grad_user))
+            elif ctx.needs_input_grad[0]:
+                # d KL(q || p) / d user = (E_p - E_q) / tau: two score_expect calls
+                kw = dict(exclude=exclude, splits=splits, prior=prior, stamp=stamp, window=window)
+                e_p, _ = score_expect(news_vecs, user, tau, (bl, bm), **kw)
+                e_q, _ = score_expect(news_vecs, ref, rtau, (rbl, rbm), **kw)
+                tau64 = (tau if isinstance(tau, torch.Tensor) else torch.full((U,), float(tau), device=dev)).to(torch.float64)
+                rows = (e_p.to(torch.float64) - e_q.to(torch.float64)) * (kap / torch.where(valid, tau64, torch.ones_like(tau64)))[:, None]
+                grad_user = torch.where(live, rows, zero).to(torch.float32)
+            if ctx.tau_grad:
+                # d KL(p || q) / d tau = -Cov_p(log p - log q, log p) / tau: [U] elementwise work in fp64
+                tau64 = (tau if isinstance(tau, torch.Tensor) else torch.full((U,), float(tau), device=dev)).to(torch.float64)
+                per_user = torch.where(valid, -kap * torch.where(valid, cov.to(torch.float64), zero) / torch.where(valid, tau64, torch.ones_like(tau64)),
+                                       zero)
+                grad_tau = (per_user.sum() if ctx.tau_shape == () else per_user).to(ctx.tau_dtype)
+        return (grad_user, grad_tau) + (None,) * 9
+
+
+def policy_kl(news_vecs, user_vecs, ref_vecs, temperature, ref_temperature=None, mode="reverse", exclude=None, splits=0, prior=None, stamp=None,
+              window=None):
+    """The KL divergence between the served distribution p of `user_vecs` (at `temperature`) and the distribution q of a constant
+    reference policy `ref_vecs` (at `ref_temperature`; None = the policy's temperature VALUE, a constant) over the full corpus,
+    differentiable with respect to `user_vecs`: the trust region of off-policy training, the distillation loss between two user
+    encoders, and the drift between two checkpoints.  Lists and pools are shared by the two policies.
+    Returns (kl fp32 [U], valid bool [U]); kl = 0 where not valid: nothing eligible, or a temperature entry on either side that is
+    not finite and > 0 (or a NaN base).  Such users contribute no gradient.
+    mode="reverse": KL(p || q).  Forward: two score_logz calls and one score_kl call (include/nrhip.h, K26).  Backward: ONE
+    nr_score_expect_kl call (K27), grad_user = (g / tau) sum_v p_v (log p_v - log q_v - KL) news_v; a temperature tensor (0-dim or
+    [U]) that requires grad gets -g cov / tau, [U] elementwise work in fp64 (a 0-dim tensor the sum over the users).
+    mode="forward": KL(q || p), the distillation direction.  The value is score_kl with the roles swapped;
+    grad_user = g (E_p - E_q) / tau from two score_expect calls.  A temperature that requires grad is refused in this mode.
+    `ref_vecs` and `news_vecs` are constants: one that requires grad is refused."""
+    if mode not in ("reverse", "forward"):
+        raise RuntimeError(f"policy_kl: mode must be 'reverse' (KL(p || q)) or 'forward' (KL(q || p)), got {mode!r}")
+    if isinstance(ref_vecs, torch.Tensor) and ref_vecs.requires_grad:
+        raise RuntimeError("policy_kl: ref_vecs requires grad, but the reference policy is a constant here (detach it); training both sides "
+                           "is a later policy_kl_joint, not part of this call")
+    if news_vecs.requires_grad:
+        raise RuntimeError("policy_kl: news_vecs requires grad, but the table is frozen here: its gradient is a [V, N] reduction over every "
+                           "user of the call and is not part of this call (detach the table; a later policy_kl_joint would have that pass)")
+    for name, t in (("temperature", temperature), ("ref_temperature", ref_temperature)):
+        if isinstance(t, torch.Tensor) and (t.dim() > 1 or not t.is_floating_point() or (t.dim() == 1 and t.shape[0] != user_vecs.shape[0])):
+            raise RuntimeError(f"policy_kl: a {name} tensor must be floating point, 0-dim or of shape ({user_vecs.shape[0]},), got "
+                               f"{tuple(t.shape)} {t.dtype}")
+    if isinstance(ref_temperature, torch.Tensor) and ref_temperature.requires_grad:
+        raise RuntimeError("policy_kl: ref_temperature requires grad, but the reference policy is a constant here (detach it)")
+    if mode == "forward" and isinstance(temperature, torch.Tensor) and temperature.requires_grad:
+        raise RuntimeError("policy_kl: temperature requires grad, which mode='forward' (KL(q || p)) does not serve: its temperature gradient "
+                           "needs moments under q that no pass here forms (use mode='reverse', or detach the temperature)")
+    _vector_args("policy_kl", news_vecs, user_vecs)
+    return PolicyKLFunction.apply(user_vecs, temperature, news_vecs, ref_vecs, ref_temperature, mode == "reverse", exclude, splits, prior, stamp,
+                                  window)
+
+
 def _score_expect_news(what, news_vecs, user_vecs, temperature, base, exclude, splits, prior, stamp, window, weight, named, scale_inv_tau, rows):
     """One nr_score_expect_news call (include/nrhip.h, K18): (out [V, N] fp32 or None, mass [V] fp32).  named: None or (offsets
     int32 [V + 1], users int32 [n], w fp32 [n]) on the device."""

@@ -621,6 +621,63 @@ def policy_entropy(model, news_vecs, hist_idx, mask, temperature, exclude_histor
     return ent, var
 
 
+def policy_kl(model, ref, news_vecs, hist_idx, mask, temperature, ref_temperature=None, mode="reverse", exclude_history=True, batch_size=8192,
+              prior=None, news_time=None, window=None, seen=None):
+    """The mean KL divergence, over the full corpus, between the distribution `model` serves and that of a reference policy: the
+    trust region of off-policy training (loss + kl_weight * mean_kl against the logging checkpoint), the distillation loss of one
+    user encoder into another (mode="forward"), and, under torch.no_grad(), the drift monitor between two checkpoints.
+    `ref`: a second model of the same class, whose user vectors are formed under no_grad from the same histories (a logged or
+    teacher checkpoint), or a [U, news_dim] tensor of logged user vectors.  The two policies share the table, the histories'
+    exclusions and the pools; they differ in user vectors and temperature (ref_temperature None = temperature's value).
+    mode="reverse": KL(served || reference); mode="forward": KL(reference || served).  The arguments, the chunking into batch_size
+    users and the accumulation are full_softmax_loss_entropy's; per chunk the work is ops.policy_kl (include/nrhip.h, K13, K26,
+    K27), differentiable with respect to the user encoder and, in the reverse mode, a temperature that requires grad.
+    Returns (mean_kl, n): the mean over the n valid users (something eligible, temperatures finite and > 0), n a device tensor."""
+    device = news_vecs.device
+    hist = torch.as_tensor(hist_idx).to(device=device, dtype=torch.int32)
+    m = torch.as_tensor(mask).to(device=device, dtype=torch.float32)
+    news_vecs = news_vecs.detach().float().contiguous()
+    U, N = hist.shape[0], news_vecs.shape[1]
+    ref_vecs = None
+    if isinstance(ref, torch.Tensor):
+        if tuple(ref.shape) != (U, N):
+            raise RuntimeError(f"policy_kl: logged user vectors must be [U = {U}, news_dim = {N}], got {tuple(ref.shape)}")
+        ref_vecs = ref.detach().to(device=device, dtype=torch.float32).contiguous()
+    elif not hasattr(ref, "user_encoder"):
+        raise RuntimeError(f"policy_kl: ref must be a model with a user_encoder or a [U, news_dim] tensor, got {type(ref).__name__}")
+    exclude = _exclusions(hist, m, exclude_history, seen, device)
+    kw = _pool_kwargs(device, prior, news_time, window)
+    tau = _device_temperature(temperature, U, device)
+    rtau = None if ref_temperature is None else _device_temperature(ref_temperature, U, device)
+    margs = getattr(model, "args", None)
+    code = ops.dtype_code(getattr(margs, "compute_dtype", "fp32")) if getattr(margs, "user_log_mask", False) else ops.NR_F32
+    total = torch.zeros((), dtype=torch.float32, device=device)
+    n = torch.zeros((), dtype=torch.int64, device=device)
+    step = max(int(batch_size), 1)
+    for a in range(0, U, step):
+        b = min(U, a + step)
+        user = model.user_encoder(ops.embed_gather(news_vecs, hist[a:b], code), m[a:b]).float().contiguous()
+        if ref_vecs is not None:
+            ref_b = ref_vecs[a:b]
+        else:
+            with torch.no_grad():
+                rargs = getattr(ref, "args", None)
+                rcode = ops.dtype_code(getattr(rargs, "compute_dtype", "fp32")) if getattr(rargs, "user_log_mask", False) else ops.NR_F32
+                ref_b = ref.user_encoder(ops.embed_gather(news_vecs, hist[a:b], rcode), m[a:b]).float().contiguous()
+        kw_b = dict(kw)
+        if "window" in kw_b:
+            kw_b["window"] = kw_b["window"][a:b].contiguous()
+        tau_b = tau[a:b].contiguous() if isinstance(tau, torch.Tensor) and tau.dim() == 1 else tau
+        rtau_b = rtau[a:b].contiguous() if isinstance(rtau, torch.Tensor) and rtau.dim() == 1 else rtau
+        ex_b = exclude
+        if exclude is not None and (a, b) != (0, U):
+            ex_b = exclude.take(torch.arange(a, b, device=device)) if isinstance(exclude, ops.ExclusionLists) else exclude[a:b].contiguous()
+        kl, valid = ops.policy_kl(news_vecs, user, ref_b, tau_b, rtau_b, mode=mode, exclude=ex_b, **kw_b)
+        total = total + kl.sum()
+        n = n + valid.sum()
+    return total / n.clamp(min=1).to(torch.float32), n
+
+
 def full_softmax_loss_entropy(model, news_vecs, hist_idx, mask, targets, temperature, entropy_weight, exclude_history=True, batch_size=8192,
                               prior=None, news_time=None, window=None, seen=None):
     """full_softmax_loss with an entropy bonus and a temperature that may be learned:
